@@ -40,8 +40,13 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="skip the extra hipGraph-replay timing")
     ap.add_argument("--no-s1", action="store_true", help="skip the secondary S = 1 timing")
     ap.add_argument("--blocks", type=int, default=5,
-                    help="timed blocks of --steps steps each (barrier + synchronize around every block); value = steps / "
-                         "median block, min / max reported")
+                    help="the --steps timed steps are split into this many blocks (at most --steps; barrier + "
+                         "synchronize around every block); value = steps / total time of the blocks, the per-step min / "
+                         "max over blocks reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, forward outputs, parameters "
+                         "after the update and their gradients) as DIR/<name>.npy, at most 64 MB in all: arrays beyond "
+                         "their share are cut to a fixed seeded sample of their elements")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the config1 / config3 extra keys (BASELINE configs 1 and 3 on this GPU)")
     ap.add_argument("--headline-only", action="store_true",
@@ -75,6 +80,8 @@ def parse():
                     help="diagnostic: time rank 0's share of a K-way row sharding on ONE GPU (no all-reduce); "
                          "the line is then NOT the contract metric")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.fixed, args.latent, args.warp = None, None, "rbf"
     if args.headline_only:
         args.no_s1 = args.no_graph = args.no_extras = args.no_cpu_baseline = True
@@ -363,7 +370,7 @@ def extra_workload(which, args):
 
     # (config 1's step is ~0.6 ms of ~60 tiny launches: the first ~1000 steps of a process run 30-70 % slow on these
     #  boxes (clocks), so its child warms up for 1000 steps and times blocks of at least 200)
-    steps, warm = (max(args.steps, 200), max(args.warmup, 1000)) if which == "1" else (args.steps, args.warmup)
+    steps, warm = (max(args.steps, 600), max(args.warmup, 1000)) if which == "1" else (args.steps, args.warmup)
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", which, "--steps", str(steps), "--warmup",
            str(warm), "--blocks", "3"]
     try:
@@ -490,6 +497,46 @@ def stop_smi_sampler(smp, t0, t1):
                        "4 samples/s, those inside the sustained run's wall-clock window")
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, model, loss, fwd):
+    """--dump-outputs: what the last timed step computed - its loss, the forward's four outputs (the draws as a caller
+    sees them after the step), every parameter after the optimiser's update and its gradient - as DIR/<name>.npy in
+    float32 / float64.  Past DUMP_LIMIT_BYTES in all, the smallest arrays are kept whole and the rest share what is
+    left equally: each of those is cut to a sample of its flattened elements at sorted positions drawn by a generator
+    seeded with 0, the same for the same shape in every run"""
+    import numpy as np
+
+    arrays = {"loss": loss}
+    for key, per_mod in fwd.items():
+        for m, t in per_mod.items():
+            arrays[f"{key}.{m}"] = t
+    for n, p in model.named_parameters():
+        arrays[f"param.{n}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{n}"] = p.grad
+    with torch.no_grad():
+        arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items() if v is not None}
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_LIMIT_BYTES - 128 * len(arrays)  # (the .npy header of a file is 128 bytes)
+    written, sampled = 0, {}
+    names = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, k in enumerate(names):
+        a = arrays[k]
+        share = left // (len(names) - i)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            sampled[k] = dict(shape=list(a.shape), kept=int(n))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, n))]
+        left -= a.nbytes
+        path = os.path.join(dirname, k + ".npy")
+        np.save(path, a)
+        written += os.path.getsize(path)
+    return dict(dir=os.path.abspath(dirname), arrays=len(names), bytes=written, sampled=sampled)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -610,8 +657,10 @@ def main():
     opt = FusedAdam(model.parameters(), lr=1e-2)  # torch.optim.Adam's update as one HIP launch
     reducer = out_reducer if out_reducer is not None else GradAllReducer(
         model.parameters(), overlap=args.overlap_reduce and world > 1, model=model)
-    timer = KernelTimer(model, args.steps * max(1, args.blocks))
+    timer = KernelTimer(model, args.steps)
     timer.S = args.S
+
+    kept = {}  # --dump-outputs: the forward's outputs of the last timed step (``armed`` by time_blocks for that step)
 
     def reference_step(S):
         # the reference's two calls and its loop order (examples/grid_example.py:62-78: forward, loss_fn, zero_grad,
@@ -625,6 +674,9 @@ def main():
         loss.backward()
         reducer()
         opt.step()
+        if kept.get("armed"):
+            kept.update(armed=False, out=dict(G_means=G_means, G_samples=G_samples, F_latent_samples=F_latent_samples,
+                                              F_samples=F_samples))
         return loss
 
     vopt = [None]
@@ -647,8 +699,10 @@ def main():
     def helper_step(S):  # the same loop body as the package's helper (seed gradient kept on the device)
         return train_step(model, opt, dd, view_idx, Ns, S=S, reducer=reducer, static_grads=args.static_grads)
 
-    def time_blocks(step, S, blocks, before=None):
-        """``blocks`` x (barrier + synchronize, --steps steps, synchronize + barrier), MAX over ranks per block"""
+    def time_blocks(step, S, blocks, before=None, keep_last=False):
+        """--steps steps in ``blocks`` blocks of (barrier + synchronize, the block's steps, synchronize + barrier), MAX
+        over ranks per block -> ([(seconds, steps) per block], last loss); ``keep_last``: the last step keeps its
+        forward's outputs in ``kept``"""
         for _ in range(args.warmup):
             step(S)
         # host hygiene, once per process: the construction garbage of torch and the model (~74k objects) otherwise
@@ -659,15 +713,19 @@ def main():
             gc.collect()
             gc.freeze()
             _GC_DONE.append(True)
+        blocks = max(1, min(blocks, args.steps))
+        sizes = [args.steps // blocks + (b < args.steps % blocks) for b in range(blocks)]
         out, loss = [], None
-        for b in range(blocks):
+        for b, n in enumerate(sizes):
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
             if before is not None and b == 0:
                 before()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for i in range(n):
+                if keep_last and b == blocks - 1 and i == n - 1:
+                    kept["armed"] = True
                 loss = step(S)
             torch.cuda.synchronize()
             if world > 1:
@@ -675,25 +733,30 @@ def main():
             t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
             if world > 1:
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            out.append(float(t.item()))
+            out.append((float(t.item()), n))
         return out, loss
 
     def summary(ts):
-        srt = sorted(ts)
-        med = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
-        return dict(value=args.steps / med, unit="steps/s", ms_per_step=1e3 * med / args.steps, blocks=len(ts),
-                    steps_per_block=args.steps, ms_per_step_min=1e3 * srt[0] / args.steps,
-                    ms_per_step_max=1e3 * srt[-1] / args.steps,
-                    ms_per_step_blocks=[round(1e3 * t / args.steps, 4) for t in ts])
+        total = sum(t for t, _ in ts)
+        per = [t / n for t, n in ts]
+        return dict(value=args.steps / total, unit="steps/s", ms_per_step=1e3 * total / args.steps, blocks=len(ts),
+                    steps_per_block=[n for _, n in ts], ms_per_step_min=1e3 * min(per),
+                    ms_per_step_max=1e3 * max(per), ms_per_step_blocks=[round(1e3 * p, 4) for p in per])
 
     nblk = max(1, args.blocks)
     # (with the engine's hipGraph cache asked for - GPSA_STEP_GRAPH=1, config 1's extra leg - no kernel-timing events: the
     #  engine does not replay with them on)
     cache_on = os.environ.get("GPSA_STEP_GRAPH") == "1"
-    times, loss = time_blocks(reference_step, args.S, nblk, before=None if cache_on else timer.start)
+    times, loss = time_blocks(reference_step, args.S, nblk, before=None if cache_on else timer.start,
+                              keep_last=args.dump_outputs is not None)
     head = summary(times)
-    dt = args.steps / head["value"]  # the median block
+    dt = args.steps / head["value"]  # all timed steps
     final_loss = float(loss.item())
+    dumped = None
+    if args.dump_outputs is not None:  # before any later leg moves the parameters on
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, model, loss, kept.pop("out"))
+        kept.clear()
     # the contraction kernels' HIP-event timings of exactly these blocks (read now: the later legs run the same plan)
     ks_head = None
     if rank == 0:
@@ -929,10 +992,13 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps,
-            "timing": {"protocol": f"{head['blocks']} blocks of {args.steps} steps, barrier + synchronize around each, max "
-                                   "over ranks per block; value / ms_per_step = the MEDIAN block; one gc.collect() + "
-                                   "gc.freeze() after the warm-up steps (the collector stays on)",
-                       **{k: head[k] for k in ("blocks", "ms_per_step_min", "ms_per_step_max", "ms_per_step_blocks")}},
+            "timing": {"protocol": f"{args.steps} timed steps in {head['blocks']} blocks, barrier + synchronize around "
+                                   "each, max over ranks per block; value / ms_per_step = all timed steps over the sum of "
+                                   "the blocks' times; one gc.collect() + gc.freeze() after the warm-up steps (the "
+                                   "collector stays on)",
+                       **{k: head[k] for k in ("blocks", "steps_per_block", "ms_per_step_min", "ms_per_step_max",
+                                               "ms_per_step_blocks")}},
+            "dump_outputs": dumped,
             # the timed loop is the reference's two calls in the reference's order with FusedAdam and no per-step host
             # read of the loss (bench.py reference_step); "verbatim_loop": examples/grid_example.py:59-78 exactly
             # (torch.optim.Adam + loss.item()); "helper_loop": the same step through train.train_step

@@ -318,12 +318,14 @@ def test_lmc_loglik_fused_refuses_more_than_64_latent_outputs(hip):
         hip.lmc_loglik_fused(rnd(1, 8, 65).to(DEV), rnd(65, 4).to(DEV), rnd(8, 4).to(DEV), torch.tensor([0.0]).to(DEV))
 
 
-def test_lmc_loglik_mfma_equals_vector_kernel(hip, monkeypatch):
+def test_lmc_loglik_mfma_equals_vector_kernel(hip, monkeypatch, tmp_path):
     """round 5's matrix-core kernel against round 4's vector-pipe kernel on BASELINE config 3's shape (to rounding:
     different summation orders), with its time next to it"""
+    import os
     import subprocess
     import sys
 
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = (
         "import torch, time, sys; sys.path.insert(0, '.'); sys.path.insert(0, 'tests')\n"
         "from spatial_alignment_amd.ops import get_ops\n"
@@ -337,9 +339,10 @@ def test_lmc_loglik_mfma_equals_vector_kernel(hip, monkeypatch):
         "torch.save([o.cpu() for o in out], sys.argv[1])\n")
     res = {}
     for mode in ("1", "0"):
-        path = f"/tmp/lmc_{mode}.pt"
-        env = dict(__import__("os").environ, GPSA_LMC_MFMA=mode)
-        r = subprocess.run([sys.executable, "-c", code, path], env=env, capture_output=True, text=True, timeout=600)
+        path = str(tmp_path / f"lmc_{mode}.pt")
+        env = dict(os.environ, GPSA_LMC_MFMA=mode)
+        r = subprocess.run([sys.executable, "-c", code, path], env=env, cwd=root, capture_output=True, text=True,
+                           timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         res[mode] = (torch.load(path), [ln for ln in r.stdout.splitlines() if ln.startswith("MS")][0])
     print("lmc likelihood, 5 x 40000 spots, 10 -> 500 outputs: matrix cores", res["1"][1], "vector pipe", res["0"][1])

@@ -297,3 +297,38 @@ def test_bench_smi_sample_parsing(tmp_path):
     assert res["samples"] == 2
     assert res["sclk_mhz"] == dict(min=2390, mean=2392.0, max=2394)
     assert res["power_w"] == dict(min=990.0, mean=1000.0, max=1010.0)
+
+
+def test_bench_dump_outputs_cap_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array; past the cap the small arrays stay whole and the
+    large ones become the same seeded sample of their elements in every run, the files within the cap in all"""
+    import importlib.util
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    model = torch.nn.Linear(4, 3)
+    model.weight.grad = torch.randn(3, 4, generator=g)
+    F = torch.randn(5, 300, 20, generator=g)
+    fwd = dict(G_means={"m": torch.randn(300, 2, generator=g, dtype=torch.float64)}, F_samples={"m": F})
+    loss = torch.tensor(2.5)
+
+    res = bench.dump_outputs(str(tmp_path / "full"), model, loss, fwd)
+    files = sorted(os.listdir(tmp_path / "full"))
+    assert files == ["F_samples.m.npy", "G_means.m.npy", "grad.weight.npy", "loss.npy", "param.bias.npy",
+                     "param.weight.npy"]
+    assert res["sampled"] == {} and res["bytes"] == sum(os.path.getsize(tmp_path / "full" / f) for f in files)
+    assert np.array_equal(np.load(tmp_path / "full" / "F_samples.m.npy"), F.numpy())
+    assert np.load(tmp_path / "full" / "G_means.m.npy").dtype == np.float64
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    a = bench.dump_outputs(str(tmp_path / "a"), model, loss, fwd)
+    b = bench.dump_outputs(str(tmp_path / "b"), model, loss, fwd)
+    assert list(a["sampled"]) == ["F_samples.m"] and a["bytes"] <= 20000
+    sa, sb = np.load(tmp_path / "a" / "F_samples.m.npy"), np.load(tmp_path / "b" / "F_samples.m.npy")
+    assert sa.dtype == np.float32 and 0 < sa.size < F.numel() and np.array_equal(sa, sb)
+    assert np.isin(sa, F.numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "G_means.m.npy"), fwd["G_means"]["m"].numpy())

@@ -1,5 +1,5 @@
 import os, sys, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from spatial_alignment_amd.optim import FusedAdam
 from spatial_alignment_amd.synthetic import make_grid_problem, make_model
 dev = torch.device("cuda:0")

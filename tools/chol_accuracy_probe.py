@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from spatial_alignment_amd.ops import get_ops
 o = get_ops()
 torch.manual_seed(0)
