@@ -207,6 +207,20 @@ int gpsa_quadform_elbo_delta_f32(int omega_dtype, const float* alpha, const void
                                  const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
                                  float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
                                  void* stream);
+/* The same two passes with the contraction Omega_l alpha on the bf16 matrix instructions: every fp32 operand split
+ * into three bf16 pieces, the six products a_i b_j with i + j <= 4 accumulated in fp32 (as accurate as the fp32
+ * instruction on the headline operands; the opt-in mode gpsa_step_desc.contraction = 1).  Same arguments, same
+ * outputs, same GPSA_EUNSUPPORTED cases; their own workspace. */
+long long gpsa_quadform_elbo_x3_f32_workspace(int M, long long C, int L);
+int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                              const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                              long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
+                              float* FT, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_quadform_elbo_delta_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                    const float* delta, const double* q, const float* var_u, const float* eps,
+                                    const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                    float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
+                                    void* stream);
 /* dOmega[l] = sum_c g[l,c] * alpha[:,c] alpha[:,c]^T  (full symmetric [L,M,M]), stored as out_dtype
  * (out_dtype != dtype only on the fp32 MFMA path, whose partial sums are widened while they are added:
  * GPSA_EUNSUPPORTED otherwise, and the caller converts) */
@@ -223,6 +237,17 @@ int gpsa_quadform_bwd_omega_takes_delta(int M, long long C);
 int gpsa_quadform_bwd_omega_delta_f32(int out_dtype, const float* alpha, const float* g, const float* dmeanT, int M,
                                       long long C, int L, void* dOmega, float* ddelta, double dbeta, void* workspace,
                                       long long workspace_bytes, void* stream);
+/* The two Gram calls above with the contraction on the bf16 matrix instructions: alpha split into three bf16 pieces
+ * (an image written once per call), the g-scaled row fragment split in registers, six products a_i b_j with i + j <= 4
+ * accumulated in fp32 (the opt-in mode gpsa_step_desc.contraction = 1).  M <= 256 and dtype GPSA_F32 only
+ * (GPSA_EUNSUPPORTED otherwise: gpsa_quadform_bwd_omega_x3_workspace returns 0 there); the delta form where row M is a
+ * padding row of the last tile row.  Deterministic: partials added in a fixed order. */
+long long gpsa_quadform_bwd_omega_x3_workspace(int M, long long C, int L);
+int gpsa_quadform_bwd_omega_x3(int dtype, int out_dtype, const void* alpha, const void* g, int M, long long C, int L,
+                               void* dOmega, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_quadform_bwd_omega_delta_x3(int out_dtype, const float* alpha, const float* g, const float* dmeanT, int M,
+                                     long long C, int L, void* dOmega, float* ddelta, double dbeta, void* workspace,
+                                     long long workspace_bytes, void* stream);
 
 /* alpha = Kinv Kuf on the fp64 matrix cores, with Kinv [M,M] = K_uu^-1 (fp64, from gpsa_chol_inv_f64 +
  * L^-T L^-1) and Kuf [M,C] stored as in_dtype (widened on the fly); alpha [M,C] is stored as alpha_dtype
@@ -517,6 +542,10 @@ typedef struct gpsa_step_desc {
                                                are neither factorised nor inverted.  kl_own_hi <= 0: every term (one
                                                process, or the 1/world weighting).  Summed over ranks whose ranges
                                                partition the terms, loss and gradients are the full ELBO's. */
+  int contraction;                          /* the data GPs' fused ELBO pass: 0 = fp32 matrix instructions; 1 = bf16x3
+                                               (gpsa_quadform_elbo_x3_f32: every operand in three bf16 pieces); any
+                                               other value is refused.  LMC modalities, M > 256 and every other kernel
+                                               are unaffected: gpsa_step_contraction says what runs */
 } gpsa_step_desc;
 
 typedef struct gpsa_step_params {           /* device pointers, fp32, the reference's parameter layout */
@@ -620,6 +649,9 @@ void gpsa_step_destroy(void* plan);
 long long gpsa_step_saved_bytes(const void* plan);
 long long gpsa_step_saved_bytes_nokeep(const void* plan);  /* arena of a forward with io.keep_products == 0 */
 int gpsa_step_fused(const void* plan, int m);         /* 1: modality m's training pass can run the fused ELBO kernel */
+int gpsa_step_contraction(const void* plan, int m);   /* bit mask of modality m's bf16x3 kernels in a training step: 1 =
+                                                         the fused ELBO pass (when gpsa_step_io.fuse_elbo is set: the
+                                                         unfused path runs the fp32 kernels), 2 = the data GP's Gram */
 long long gpsa_step_scratch_bytes(const void* plan);
 long long gpsa_step_bwd_acc_bytes(const void* plan);  /* gpsa_step_io.bwd_acc */
 int gpsa_step_n_kl(const void* plan);                 /* V*D + sum_m L_m */

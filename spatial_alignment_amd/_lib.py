@@ -43,6 +43,9 @@ SIGNATURES = {
     "gpsa_quadform_bwd_omega": (_i, [_i, _i, _vp, _vp, _i, _ll, _i, _vp, _vp, _ll, _vp]),
     "gpsa_quadform_bwd_omega_takes_delta": (_i, [_i, _ll]),
     "gpsa_quadform_bwd_omega_delta_f32": (_i, [_i, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _d, _vp, _ll, _vp]),
+    "gpsa_quadform_bwd_omega_x3_workspace": (_ll, [_i, _ll, _i]),
+    "gpsa_quadform_bwd_omega_x3": (_i, [_i, _i, _vp, _vp, _i, _ll, _i, _vp, _vp, _ll, _vp]),
+    "gpsa_quadform_bwd_omega_delta_x3": (_i, [_i, _vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _d, _vp, _ll, _vp]),
     "gpsa_whiten_workspace": (_ll, [_i]),
     "gpsa_whiten_f64": (_i, [_vp, _i, _vp, _i, _ll, _i, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_panel_mm": (_i, [_i, _i, _i, _vp, _vp, _i, _ll, _vp, _vp, _vp, _ll, _vp]),
@@ -81,7 +84,7 @@ class StepDesc(C.Structure):
         ("n_latent", _i * MAX_MODS), ("n_out", _i * MAX_MODS), ("has_lmc", _i * MAX_MODS),
         ("n_rows", _ll * MAX_MODS), ("s_test", _i), ("n_test", _ll * MAX_MODS), ("want_kl", _i),
         ("view_fixed", C.POINTER(_i)), ("view_rows", C.POINTER(_ll)), ("keep_budget_bytes", _ll),
-        ("exact_inducing_grad", _i), ("kl_own_lo", _i), ("kl_own_hi", _i),
+        ("exact_inducing_grad", _i), ("kl_own_lo", _i), ("kl_own_hi", _i), ("contraction", _i),
     ]
 
 
@@ -167,6 +170,11 @@ SIGNATURES.update({
     "gpsa_quadform_elbo_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _ll, _vp]),
     "gpsa_quadform_elbo_takes_delta": (_i, [_i]),
+    "gpsa_quadform_elbo_x3_f32_workspace": (_ll, [_i, _ll, _i]),
+    "gpsa_quadform_elbo_x3_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_quadform_elbo_delta_x3_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_quadform_elbo_delta_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp, _ll, _vp]),
     "gpsa_step_scratch_bytes": (_ll, [_vp]),
@@ -193,6 +201,7 @@ SIGNATURES.update({
                                       _d, _pp, _pp, _vp, _i, _vp, _vp, _ll, _vp]),
     "gpsa_elbo_fused_post": (_i, [_vp, _vp, _vp, _i, _ll, _i, _vp, _vp, _i, _vp, _vp, _ll, _vp]),
     "gpsa_step_fused": (_i, [_vp, _i]),
+    "gpsa_step_contraction": (_i, [_vp, _i]),
     "gpsa_adam_step": (_i, [_i, _pp, _pp, _pp, _pp, C.POINTER(_ll), _d, _d, _d, _d, _vp, _vp]),
 })
 

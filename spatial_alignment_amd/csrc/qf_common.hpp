@@ -379,6 +379,22 @@ extern template __global__ void panel_elbo_kernel<13, 2, 4, true>(ElboArgs);
 extern template __global__ void panel_elbo_kernel<13, 2, 2, true, true>(ElboArgs);
 extern template __global__ void panel_elbo_kernel<13, 2, 4, true, true>(ElboArgs);
 
+// the same pass with the contraction on the bf16 matrix instructions in three pieces (qf_x3.hip; gpsa_step_desc.contraction
+// = 1): Ppk is then pack_x3_kernel's three-plane bf16 image of Omega
+template <int MB, int NCT>
+__global__ void __launch_bounds__(256, 1) panel_elbo_x3_kernel(ElboArgs a);
+#define GPSA_ELBO_X3_SHAPES(X) X(2, 2) X(4, 2) X(7, 2) X(13, 1) X(16, 1)
+#define GPSA_ELBO_X3_EXTERN(MB, NCT) extern template __global__ void panel_elbo_x3_kernel<MB, NCT>(ElboArgs);
+#define GPSA_ELBO_X3_DEFINE(MB, NCT) template __global__ void panel_elbo_x3_kernel<MB, NCT>(ElboArgs);
+GPSA_ELBO_X3_SHAPES(GPSA_ELBO_X3_EXTERN)
+template <typename TS>
+__global__ void __launch_bounds__(256) pack_x3_kernel(const TS* __restrict__ src, int M, int MB, int KB, int L,
+                                                       unsigned short* __restrict__ dst, const float* __restrict__ drow);
+extern template __global__ void pack_x3_kernel<float>(const float* __restrict__, int, int, int, int,
+                                                      unsigned short* __restrict__, const float* __restrict__);
+extern template __global__ void pack_x3_kernel<double>(const double* __restrict__, int, int, int, int,
+                                                       unsigned short* __restrict__, const float* __restrict__);
+
 // ---- symmetric quadratic form: qf_sym.hip
 template <int MB, int NCT, int RL>
 __global__ void __launch_bounds__(256, (MB * NCT >= 24) ? 1 : 2) quad_sym_mfma_kernel(const float* __restrict__ Ppk, const float* __restrict__ X, int M, long long C, int L, float* __restrict__ out);
@@ -397,6 +413,40 @@ constexpr int GR_KC = 64;  // columns per staged chunk (four 16-deep MFMA K bloc
 template <int MB, bool ALIGNED, int NL>
 __global__ void __launch_bounds__(256, (MB >= 13 || NL > 1) ? 1 : 2) gram_mfma_kernel(const float* __restrict__ alpha, const float* __restrict__ g, long long gstride, int M, long long C, int L, int nsplit, float* __restrict__ part, const float* __restrict__ dmean);
 #define GPSA_GRAM_SIG (const float* __restrict__ alpha, const float* __restrict__ g, long long gstride, int M, long long C, int L, int nsplit, float* __restrict__ part, const float* __restrict__ dmean)
+// Ownership of the lower-triangle tiles: whole tile ROWS are dealt to the 4 waves (longest row first,
+// first fit: 23 / 23 / 23 / 22 tiles at MB = 13), so that a wave loads and g-scales the A fragment of a row once per K block
+// and then only streams the B fragments of that row's columns: half the LDS fragment reads of a
+// tile-by-tile deal, and no separate scaling pass over the chunk.
+template <int MB>
+struct GramPlan {
+  static constexpr int NT = MB * (MB + 1) / 2;
+  int cnt[4];
+  int rr[4][NT], cc[4][NT];
+  constexpr GramPlan() : cnt{}, rr{}, cc{} {
+    const int cap = (NT + 3) / 4;  // first fit, longest row first, into waves of ceil(NT / 4) tiles
+    for (int r = MB - 1; r >= 0; --r) {
+      int best = -1;
+      for (int w = 0; w < 4 && best < 0; ++w)
+        if (cnt[w] + r + 1 <= cap) best = w;
+      if (best < 0) {
+        best = 0;
+        for (int w = 1; w < 4; ++w)
+          if (cnt[w] < cnt[best]) best = w;
+      }
+      for (int c = 0; c <= r; ++c) {
+        rr[best][cnt[best]] = r;
+        cc[best][cnt[best]] = c;
+        ++cnt[best];
+      }
+    }
+  }
+  constexpr int max_cnt() const {
+    int m = 0;
+    for (int w = 0; w < 4; ++w) m = cnt[w] > m ? cnt[w] : m;
+    return m;
+  }
+};
+
 #define GPSA_GRAM_SHAPES(X) X(2, 2) X(4, 2) X(7, 2) X(13, 2) X(2, 1) X(4, 1) X(7, 1) X(13, 1) X(16, 1)
 #define GPSA_GRAM_EXTERN(MB, NL)                                                \
   extern template __global__ void gram_mfma_kernel<MB, true, NL> GPSA_GRAM_SIG; \
@@ -410,5 +460,19 @@ __global__ void gram_reduce_kernel(const float* __restrict__ part, int M, int MP
                                    float* __restrict__ ddelta, float dbeta);
 extern template __global__ void gram_reduce_kernel<float>(const float* __restrict__, int, int, int, int, float* __restrict__, float* __restrict__, float);
 extern template __global__ void gram_reduce_kernel<double>(const float* __restrict__, int, int, int, int, double* __restrict__, float* __restrict__, float);
+
+// dOmega_l = sum_c g[l,c] alpha_c alpha_c^T with the contraction on the bf16 matrix instructions in three pieces (qf_x3.hip;
+// gpsa_step_desc.contraction = 1): alpha as split_image_kernel's three-plane bf16 image, partials as gram_mfma_kernel's
+template <int MB>
+__global__ void __launch_bounds__(256, 1) gram_x3_kernel(const unsigned short* __restrict__ img, const float* __restrict__ g,
+                                                         const float* __restrict__ dmean, int M, long long C, int L,
+                                                         int nsplit, float* __restrict__ part);
+#define GPSA_GRAM_X3_SHAPES(X) X(2) X(4) X(7) X(13) X(16)
+#define GPSA_GRAM_X3_EXTERN(MB)                                                                                          \
+  extern template __global__ void gram_x3_kernel<MB>(const unsigned short* __restrict__, const float* __restrict__,       \
+                                                     const float* __restrict__, int, long long, int, int, float* __restrict__);
+GPSA_GRAM_X3_SHAPES(GPSA_GRAM_X3_EXTERN)
+__global__ void __launch_bounds__(256) split_image_kernel(const float* __restrict__ X, int M, int MB, long long C, long long KBc,
+                                                          unsigned short* __restrict__ dst);
 
 }  // namespace gpsa

@@ -16,40 +16,6 @@ __device__ __attribute__((aligned(16))) const float gram_zero16[4] = {0.f, 0.f, 
 // kernel (deterministic).
 // ------------------------------------------------------------------------------------------------
 
-// Ownership of the lower-triangle tiles: whole tile ROWS are dealt to the 4 waves (longest row first,
-// first fit: 23 / 23 / 23 / 22 tiles at MB = 13), so that a wave loads and g-scales the A fragment of a row once per K block
-// and then only streams the B fragments of that row's columns: half the LDS fragment reads of a
-// tile-by-tile deal, and no separate scaling pass over the chunk.
-template <int MB>
-struct GramPlan {
-  static constexpr int NT = MB * (MB + 1) / 2;
-  int cnt[4];
-  int rr[4][NT], cc[4][NT];
-  constexpr GramPlan() : cnt{}, rr{}, cc{} {
-    const int cap = (NT + 3) / 4;  // first fit, longest row first, into waves of ceil(NT / 4) tiles
-    for (int r = MB - 1; r >= 0; --r) {
-      int best = -1;
-      for (int w = 0; w < 4 && best < 0; ++w)
-        if (cnt[w] + r + 1 <= cap) best = w;
-      if (best < 0) {
-        best = 0;
-        for (int w = 1; w < 4; ++w)
-          if (cnt[w] < cnt[best]) best = w;
-      }
-      for (int c = 0; c <= r; ++c) {
-        rr[best][cnt[best]] = r;
-        cc[best][cnt[best]] = c;
-        ++cnt[best];
-      }
-    }
-  }
-  constexpr int max_cnt() const {
-    int m = 0;
-    for (int w = 0; w < 4; ++w) m = cnt[w] > m ? cnt[w] : m;
-    return m;
-  }
-};
-
 // one staged chunk (NKB K blocks of 16 columns) of wave W's tiles:
 //     acc[s] += (g-scaled row fragment) x (column fragment)
 // Tiles go in groups of GR_G with their MFMAs interleaved, so that an accumulator is touched again only

@@ -1245,6 +1245,90 @@ int gpsa_quadform_elbo_delta_f32(int omega_dtype, const float* alpha, const void
                      part, FT, workspace, workspace_bytes, stream);
 }
 
+/* ---- the same pass with the bf16x3 contraction (panel_elbo_x3_kernel, qf_x3.hip) ------------------------------- */
+// one column tile per wave at MB >= 13: at two, the alpha planes (2 x 7 x 12) and the product's accumulators (104) do not
+// fit the 256 arch VGPRs together and the allocator spills
+static inline int elbo_x3_nct_for(int MB) { return MB >= 13 ? 1 : 2; }
+static inline long long elbo_x3_pack_bytes(int M, int L) {
+  const int MB = gpsa::mfma_mb_for(M), KB = (MB + 1) / 2;
+  return (((long long)L * KB * MB * 3 * 1024) + 255) / 256 * 256;
+}
+
+long long gpsa_quadform_elbo_x3_f32_workspace(int M, long long C, int L) {
+  if (M < 1 || C < 1 || L < 1 || !elbo_path(M) || C > GPSA_PANEL_MAX_C) return 0;
+  const int MB = gpsa::mfma_mb_for(M), nct = elbo_x3_nct_for(MB);
+  const long long G = gpsa::num_cus();
+  // behind the packed operand: the slabs, and two chunks of slack for the ring stages that walk past the last chunk
+  return elbo_x3_pack_bytes(M, L) + G * 2 * (long long)MB * 16 * 64 * nct * 4 + 2LL * MB * 3 * 1024;
+}
+
+static int elbo_x3_launch(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                          const float* meanT, const float* delta, const double* q, const float* var_u, const float* eps,
+                          const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
+                          double* part, float* FT, void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (M < 1 || C < 1 || L < 1 || N < 1 || S < 1 || !alpha || !Omega || (!meanT && !delta) || !q || !var_u || !eps || !Y ||
+      !noise_u || !g || !dmeanT || !abar || !part)
+    return GPSA_EINVAL;
+  if (omega_dtype != GPSA_F32 && omega_dtype != GPSA_F64) return GPSA_EINVAL;
+  if (delta != nullptr && !elbo_delta_ok(M)) return GPSA_EUNSUPPORTED;
+  if (!elbo_path(M) || C > GPSA_PANEL_MAX_C) return GPSA_EUNSUPPORTED;
+  if (workspace_bytes < gpsa_quadform_elbo_x3_f32_workspace(M, C, L)) return GPSA_EWORKSPACE;
+  hipStream_t st = as_stream(stream);
+  const int MB = mfma_mb_for(M), KB = (MB + 1) / 2;
+  unsigned short* Ppk = (unsigned short*)workspace;
+  float* slab = (float*)((char*)workspace + elbo_x3_pack_bytes(M, L));
+  const long long nthr = (long long)L * KB * MB * 64;
+  if (omega_dtype == GPSA_F64)
+    pack_x3_kernel<double><<<(unsigned)cdiv(nthr, 256), 256, 0, st>>>((const double*)Omega, M, MB, KB, L, Ppk, delta);
+  else
+    pack_x3_kernel<float><<<(unsigned)cdiv(nthr, 256), 256, 0, st>>>((const float*)Omega, M, MB, KB, L, Ppk, delta);
+  GPSA_LAUNCH_CHECK();
+  if (delta != nullptr) meanT = nullptr;
+  const int gmax = gpsa_quadform_elbo_parts();
+  ElboArgs a{(const float*)Ppk, alpha, M, C, L, meanT, q, var_u, eps, Y, noise_u, N, S, g, dmeanT, FT, abar, slab, part, gmax};
+#define GPSA_ELBO_X3_CASE(MBV, NCTV)                                                                   \
+  case MBV: {                                                                                          \
+    const long long ntiles = cdiv(C, 64 * NCTV), T = ntiles * L;                                       \
+    long long grid = num_cus(); /* one workgroup per CU: the ring takes most of the LDS */             \
+    if (grid > T) grid = T;                                                                            \
+    panel_elbo_x3_kernel<MBV, NCTV><<<(unsigned)grid, 256, 0, st>>>(a);                                \
+    dim3 rg((unsigned)ntiles, ntiles >= 512 ? 8 : (ntiles >= 128 ? 16 : 32));                          \
+    panel_slab_reduce_kernel<<<rg, 256, 0, st>>>(slab, M, MBV * 16, 64 * NCTV, C, L, ntiles, (int)grid, abar); \
+  } break;
+  switch (MB) {
+    GPSA_ELBO_X3_CASE(2, 2)
+    GPSA_ELBO_X3_CASE(4, 2)
+    GPSA_ELBO_X3_CASE(7, 2)
+    GPSA_ELBO_X3_CASE(13, 1)
+    GPSA_ELBO_X3_CASE(16, 1)
+    default:
+      return GPSA_EUNSUPPORTED;
+  }
+#undef GPSA_ELBO_X3_CASE
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                              const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                              long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
+                              float* FT, void* workspace, long long workspace_bytes, void* stream) {
+  if (!meanT) return GPSA_EINVAL;
+  return elbo_x3_launch(omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
+                        abar, part, FT, workspace, workspace_bytes, stream);
+}
+
+int gpsa_quadform_elbo_delta_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                    const float* delta, const double* q, const float* var_u, const float* eps,
+                                    const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                    float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
+                                    void* stream) {
+  if (!delta) return GPSA_EINVAL;
+  return elbo_x3_launch(omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
+                        abar, part, FT, workspace, workspace_bytes, stream);
+}
+
 int gpsa_quadform_bwd_alpha_kept_f32(const float* W, const float* g, int M, long long C, int L, const float* dcT,
                                      const float* dmeanT, float* dalpha, void* stream) {
   using namespace gpsa;
@@ -1431,6 +1515,85 @@ int gpsa_quadform_bwd_omega_delta_f32(int out_dtype, const float* alpha, const f
   if (workspace_bytes < gram_ws_bytes(MB, C, L)) return GPSA_EWORKSPACE;
   return gram_mfma_launch(MB, alpha, g, M, C, L, dOmega, out_dtype, (float*)workspace, as_stream(stream), dmeanT, ddelta,
                           (float)dbeta);
+}
+
+/* ---- dOmega with the bf16x3 contraction (gram_x3_kernel, qf_x3.hip) ------------------------------------------ */
+// workgroups per output: the 32-column chunks dealt so that L x nsplit workgroups fill the chip about once (gram_nsplit's rule)
+static inline int gram_x3_nsplit(long long C, int L) {
+  using namespace gpsa;
+  const long long nch = cdiv(C, 32);
+  long long W = num_cus() / (L > 0 ? L : 1);
+  if (W < 1) W = 1;
+  const long long c = cdiv(nch, W);
+  long long ns = cdiv(nch, c);
+  return (int)(ns > 256 ? 256 : (ns < 1 ? 1 : ns));
+}
+static inline long long gram_x3_img_bytes(int MB, long long C) { return cdiv(C, 32) * MB * 3 * 1024; }
+
+long long gpsa_quadform_bwd_omega_x3_workspace(int M, long long C, int L) {
+  using namespace gpsa;
+  if (M < 1 || C < 1 || L < 1 || L > 65535) return 0;
+  const int MB = gram_mb_for(M);
+  if (!MB || force_generic()) return 0;
+  return gram_x3_img_bytes(MB, C) + (long long)L * gram_x3_nsplit(C, L) * MB * 16 * MB * 16 * 4;
+}
+
+static int gram_x3_launch(int out_dtype, const float* alpha, const float* g, const float* dmean, int M, long long C, int L,
+                          void* dOmega, float* ddelta, float dbeta, void* workspace, long long workspace_bytes,
+                          hipStream_t st) {
+  using namespace gpsa;
+  const long long need = gpsa_quadform_bwd_omega_x3_workspace(M, C, L);
+  if (need == 0) return GPSA_EUNSUPPORTED;
+  if (workspace_bytes < need) return GPSA_EWORKSPACE;
+  const int MB = gram_mb_for(M), ns = gram_x3_nsplit(C, L);
+  const long long KBc = cdiv(C, 32);
+  unsigned short* img = (unsigned short*)workspace;
+  float* part = (float*)((char*)workspace + gram_x3_img_bytes(MB, C));
+  split_image_kernel<<<(unsigned)cdiv(KBc * MB * 64, 256), 256, 0, st>>>(alpha, M, MB, C, KBc, img);
+  GPSA_LAUNCH_CHECK();
+  dim3 grid((unsigned)L, (unsigned)ns);
+  switch (MB) {
+#define GPSA_GX3_CASE(MBV) \
+  case MBV: gram_x3_kernel<MBV><<<grid, 256, 0, st>>>(img, g, dmean, M, C, L, ns, part); break;
+    GPSA_GX3_CASE(2)
+    GPSA_GX3_CASE(4)
+    GPSA_GX3_CASE(7)
+    GPSA_GX3_CASE(13)
+    GPSA_GX3_CASE(16)
+#undef GPSA_GX3_CASE
+    default:
+      return GPSA_EUNSUPPORTED;
+  }
+  GPSA_LAUNCH_CHECK();
+  dim3 rgrid((unsigned)cdiv(M, 32), (unsigned)cdiv(M + (ddelta != nullptr ? 1 : 0), 8), (unsigned)L);
+  if (out_dtype == GPSA_F64)
+    gram_reduce_kernel<double><<<rgrid, 256, 0, st>>>(part, M, MB * 16, L, ns, (double*)dOmega, ddelta, dbeta);
+  else
+    gram_reduce_kernel<float><<<rgrid, 256, 0, st>>>(part, M, MB * 16, L, ns, (float*)dOmega, ddelta, dbeta);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+int gpsa_quadform_bwd_omega_x3(int dtype, int out_dtype, const void* alpha, const void* g, int M, long long C, int L,
+                               void* dOmega, void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (M < 1 || C < 1 || L < 1 || !alpha || !g || !dOmega) return GPSA_EINVAL;
+  if (out_dtype != GPSA_F32 && out_dtype != GPSA_F64) return GPSA_EINVAL;
+  if (dtype != GPSA_F32) return GPSA_EUNSUPPORTED;
+  return gram_x3_launch(out_dtype, (const float*)alpha, (const float*)g, nullptr, M, C, L, dOmega, nullptr, 0.f, workspace,
+                        workspace_bytes, as_stream(stream));
+}
+
+int gpsa_quadform_bwd_omega_delta_x3(int out_dtype, const float* alpha, const float* g, const float* dmeanT, int M,
+                                     long long C, int L, void* dOmega, float* ddelta, double dbeta, void* workspace,
+                                     long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (M < 1 || C < 1 || L < 1 || !alpha || !g || !dmeanT || !dOmega || !ddelta) return GPSA_EINVAL;
+  if (out_dtype != GPSA_F32 && out_dtype != GPSA_F64) return GPSA_EINVAL;
+  const int MB = gram_mb_for(M);
+  if (!MB || !(M > 16 * (MB - 1) && M < 16 * MB)) return GPSA_EUNSUPPORTED;  // row M must be a padding row of the last tile row
+  return gram_x3_launch(out_dtype, alpha, g, dmeanT, M, C, L, dOmega, ddelta, (float)dbeta, workspace, workspace_bytes,
+                        as_stream(stream));
 }
 
 /* batched fp64 forms of the two calls above and of gpsa_col_axpy: ``batch`` layers with contiguous operands

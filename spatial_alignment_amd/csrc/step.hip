@@ -563,6 +563,8 @@ struct Pass {  // one evaluation of the data GP: a modality's own spots, or its 
   // fused ELBO (gpsa_quadform_elbo_f32): g_ext [L+1][C], dmeanT [L][C], abar [Mg][C] live from the forward to the
   // backward (-1: this pass cannot run fused: a test pass, LMC, more than 13 row tiles)
   long long o_fuse = -1;
+  bool x3 = false;   // the fused ELBO pass runs panel_elbo_x3_kernel (gpsa_step_desc.contraction = 1)
+  bool gx3 = false;  // the data GP's Gram runs gram_x3_kernel (the same)
   bool fused(const gpsa_step_io& io) const { return io.fuse_elbo != 0 && o_fuse >= 0 && io.Y[m] != nullptr; }
 };
 
@@ -685,6 +687,7 @@ static Plan* make_plan(const gpsa_step_desc* dsc, bool host_only = false) {
   if (V < 1 || D < 1 || D > MAXD || nm < 1 || nm > MAXMODS || S < 0 || dsc->m_x < 1 || dsc->m_g < 1)
     return nullptr;
   if (dsc->view_fixed == nullptr || dsc->view_rows == nullptr) return nullptr;
+  if (dsc->contraction != 0 && dsc->contraction != 1) return nullptr;
   Plan* p = new (std::nothrow) Plan();
   if (p == nullptr) return nullptr;
   p->d = *dsc;
@@ -792,8 +795,11 @@ static Plan* make_plan(const gpsa_step_desc* dsc, bool host_only = false) {
     q.o_sigma = take((long long)dsc->n_latent[q.m] * q.C * 4);
     if (dsc->exact_inducing_grad) q.o_alpha64 = take((long long)p->Mg * q.C * 8);
     const int Lq = dsc->n_latent[q.m];
-    if (!q.test && !dsc->has_lmc[q.m] && gpsa_quadform_elbo_f32_workspace(p->Mg, q.C, Lq) > 0)
+    if (!q.test && !dsc->has_lmc[q.m] && gpsa_quadform_elbo_f32_workspace(p->Mg, q.C, Lq) > 0) {
       q.o_fuse = take((2LL * Lq + 1 + p->Mg) * q.C * 4);
+      q.x3 = dsc->contraction == 1 && gpsa_quadform_elbo_x3_f32_workspace(p->Mg, q.C, Lq) > 0;
+    }
+    q.gx3 = !q.test && dsc->contraction == 1 && gpsa_quadform_bwd_omega_x3_workspace(p->Mg, q.C, Lq) > 0;
   }
   p->o_apk_w = take(gpsa_whiten_workspace(p->Mx) * (long long)(p->nf > 0 ? p->nf : 1));
   p->o_apk_d = take(gpsa_whiten_workspace(p->Mg));
@@ -1399,11 +1405,19 @@ static int data_pass_fwd(Ctx& c, const Pass& ps) {
     float* g_ext = c.sv<float>(ps.o_fuse);
     float* dmeanT = g_ext + (long long)(L + 1) * C;
     float* abar = dmeanT + (long long)L * C;
-    const long long wsb = gpsa_quadform_elbo_f32_workspace(Mg, C, L);
+    const long long wsb = ps.x3 ? gpsa_quadform_elbo_x3_f32_workspace(Mg, C, L) : gpsa_quadform_elbo_f32_workspace(Mg, C, L);
     void* ws = c.sc.get<char>(wsb);
     const bool timed = !dry && !c.quiet && &ps == &P.passes[0];
     if (timed) P.tick(0, 0, true, c.st);
-    if (mean_in_product)
+    if (ps.x3 && mean_in_product)
+      GPSA_RUN(gpsa_quadform_elbo_delta_x3_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
+                                               c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
+                                               c.io.ll_part[m], c.io.F_fused_T[m], ws, wsb, c.stv()));
+    else if (ps.x3)
+      GPSA_RUN(gpsa_quadform_elbo_x3_f32(GPSA_F64, alpha, Om, Mg, C, L, meanT, q, c.prm.data_var, eps, c.io.Y[m],
+                                         (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar, c.io.ll_part[m],
+                                         c.io.F_fused_T[m], ws, wsb, c.stv()));
+    else if (mean_in_product)
       GPSA_RUN(gpsa_quadform_elbo_delta_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
                                             c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
                                             c.io.ll_part[m], c.io.F_fused_T[m], ws, wsb, c.stv()));
@@ -1656,7 +1670,8 @@ static int data_pass_bwd(Ctx& c, const Pass& ps, int pass_idx, const float* dFl_
   // dOmega_l = sum_c g_l alpha alpha^T (fp32 matrix cores, fp64 result)
   {
     const long long mk2 = c.sc.mark();
-    const long long wsb = gpsa_quadform_workspace(GPSA_F32, Mg, C, L);
+    long long wsb = gpsa_quadform_workspace(GPSA_F32, Mg, C, L);
+    if (ps.gx3 && gpsa_quadform_bwd_omega_x3_workspace(Mg, C, L) > wsb) wsb = gpsa_quadform_bwd_omega_x3_workspace(Mg, C, L);
     void* ws = c.sc.get<char>(wsb);
     double* dst = first_for_mod ? dOm : c.sc.get<double>((long long)L * mm);
     const bool timed = !dry && !c.quiet && &ps == &P.passes[0];
@@ -1670,15 +1685,19 @@ static int data_pass_bwd(Ctx& c, const Pass& ps, int pass_idx, const float* dFl_
       c.sc.release(mk3);
     }
     if (!dry && ddelta_in_gram) {
-      rc = gpsa_quadform_bwd_omega_delta_f32(GPSA_F64, alpha, g_ext, dmeanT, Mg, C, L, dst, B.ddc_F[m],
-                                             first_for_mod ? 0.0 : 1.0, ws, wsb, c.stv());
+      rc = ps.gx3 ? gpsa_quadform_bwd_omega_delta_x3(GPSA_F64, alpha, g_ext, dmeanT, Mg, C, L, dst, B.ddc_F[m],
+                                                     first_for_mod ? 0.0 : 1.0, ws, wsb, c.stv())
+                  : gpsa_quadform_bwd_omega_delta_f32(GPSA_F64, alpha, g_ext, dmeanT, Mg, C, L, dst, B.ddc_F[m],
+                                                      first_for_mod ? 0.0 : 1.0, ws, wsb, c.stv());
       if (rc == GPSA_EUNSUPPORTED) {  // (operand alignment): the product after all, then the plain call
         GPSA_CK(gemm32(c, 0, 1, Mg, L, C, 1.0, alpha, C, 0, dmeanT, C, 0, first_for_mod ? 0.0 : 1.0, B.ddc_F[m], L, 0, 1,
                        splitk_for(C, Mg, L)));
-        rc = gpsa_quadform_bwd_omega(GPSA_F32, GPSA_F64, alpha, g_ext, Mg, C, L, dst, ws, wsb, c.stv());
+        rc = ps.gx3 ? gpsa_quadform_bwd_omega_x3(GPSA_F32, GPSA_F64, alpha, g_ext, Mg, C, L, dst, ws, wsb, c.stv())
+                    : gpsa_quadform_bwd_omega(GPSA_F32, GPSA_F64, alpha, g_ext, Mg, C, L, dst, ws, wsb, c.stv());
       }
     } else if (!dry) {
-      rc = gpsa_quadform_bwd_omega(GPSA_F32, GPSA_F64, alpha, g_ext, Mg, C, L, dst, ws, wsb, c.stv());
+      rc = ps.gx3 ? gpsa_quadform_bwd_omega_x3(GPSA_F32, GPSA_F64, alpha, g_ext, Mg, C, L, dst, ws, wsb, c.stv())
+                  : gpsa_quadform_bwd_omega(GPSA_F32, GPSA_F64, alpha, g_ext, Mg, C, L, dst, ws, wsb, c.stv());
     }
     if (rc == GPSA_EUNSUPPORTED) {  // generic path stores in the compute type: convert
       float* tmp = c.sc.get<float>((long long)L * mm);
@@ -2413,6 +2432,12 @@ int gpsa_step_fused(const void* plan, int m) {
   if (!plan) return 0;
   for (const gpsa::Pass& q : reinterpret_cast<const gpsa::Plan*>(plan)->passes)
     if (q.m == m && !q.test) return q.o_fuse >= 0 ? 1 : 0;
+  return 0;
+}
+int gpsa_step_contraction(const void* plan, int m) {
+  if (!plan) return 0;
+  for (const gpsa::Pass& q : reinterpret_cast<const gpsa::Plan*>(plan)->passes)
+    if (q.m == m && !q.test) return ((q.o_fuse >= 0 && q.x3) ? 1 : 0) | (q.gx3 ? 2 : 0);
   return 0;
 }
 long long gpsa_step_bwd_acc_bytes(const void* plan) { return plan ? reinterpret_cast<const gpsa::Plan*>(plan)->bwd_acc_bytes : -1; }

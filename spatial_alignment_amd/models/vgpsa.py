@@ -144,6 +144,10 @@ class VariationalGPSA(GPSA):
         # every output are unaffected: its K_uu and K_uf shares cancel to 1e-4 .. 1e-5 of their size), the step is one
         # M x M x C fp64 product and some fp64 panel traffic cheaper (bench.py reports both: "exact_inducing_grad").
         self.exact_inducing_grad = None
+        # the contraction of the data GP's fused ELBO pass (gpsa_step_desc.contraction): "fp32" - the fp32 matrix
+        # instructions, the default and the headline - or "bf16x3", every operand in three bf16 pieces on the bf16 ones
+        # (opt-in; step_engine.py: plan.contraction says which modalities got it).  None: GPSA_CONTRACTION, else "fp32".
+        self.contraction = None
         self._noise = None  # injected Gaussian noise (tests / reproducibility), see inject_noise()
         self._cache = None
 

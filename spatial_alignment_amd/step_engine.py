@@ -33,6 +33,19 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+CONTRACTIONS = {"fp32": 0, "bf16x3": 1}
+
+
+def contraction_mode(model):
+    """the model's contraction mode: its ``contraction`` attribute, else GPSA_CONTRACTION, else fp32"""
+    mode = getattr(model, "contraction", None)
+    if mode is None:
+        mode = os.environ.get("GPSA_CONTRACTION") or "fp32"
+    if mode not in CONTRACTIONS:
+        raise ValueError(f"contraction must be one of {sorted(CONTRACTIONS)} (or None), not {mode!r}")
+    return mode
+
+
 class StepPlan:
     """a ``gpsa_step_create`` handle + the shape it was made for"""
 
@@ -258,9 +271,10 @@ def get_plan(model, rows, S, test_shapes, want_kl):
     if exact is None:  # the default: every gradient within 1e-4 of the reference's fp64 run
         exact = True
     exact = int(bool(exact))
+    contraction = contraction_mode(model)
     own = kl_own_range(model)
     key = (V, D, len(mods), int(S), int(model.Xtilde.shape[1]), int(model.Gtilde.shape[0]), kw, kd, L, P, lmc, N,
-           s_test, n_test, int(bool(want_kl)), fixed, rows, model.Xtilde.device.index, keep_gb, exact, own)
+           s_test, n_test, int(bool(want_kl)), fixed, rows, model.Xtilde.device.index, keep_gb, exact, own, contraction)
     cache = model.__dict__.setdefault("_step_plans", {})
     plan = cache.get(key)
     if plan is not None:
@@ -275,6 +289,7 @@ def get_plan(model, rows, S, test_shapes, want_kl):
     vr = (C.c_longlong * len(rows))(*rows)
     d.view_fixed, d.view_rows = vf, vr
     d.exact_inducing_grad = exact
+    d.contraction = CONTRACTIONS[contraction]
     d.kl_own_lo, d.kl_own_hi = own if own is not None else (0, 0)
     d.keep_budget_bytes = keep_budget_bytes(model, d, keep_gb)
     with torch.cuda.device(model.Xtilde.device):
@@ -282,6 +297,9 @@ def get_plan(model, rows, S, test_shapes, want_kl):
     plan.mods, plan.V, plan.D, plan.S, plan.L, plan.P, plan.lmc, plan.N = mods, V, D, int(S), L, P, lmc, N
     plan.s_test, plan.n_test, plan.fixed, plan.rows = s_test, n_test, fixed, rows
     plan.exact, plan.kl_own = bool(exact), own  # (what the plan was built with: bench.py reports the timed mode)
+    # which kernels really run bf16x3, per modality (gpsa_step_contraction: 1 = the fused ELBO pass); 0 where the mode
+    # does not apply (LMC, M > 256) or is not asked for
+    plan.contraction = {m: int(plan.lib.gpsa_step_contraction(plan.handle, i)) for i, m in enumerate(mods)}
     cache[key] = plan
     return plan
 
