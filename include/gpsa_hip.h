@@ -628,6 +628,14 @@ typedef struct gpsa_step_io {
    * event is recorded at the very end when the early order is not available (a microbatched step, the side stream, a
    * shape the long-K kernel does not cover).  NULL: the ordinary order. */
   void* f_event;
+  /* Data-parallel loss slot (parallel.GradAllReducer(with_loss=True)): with both given, the backward's closing kernel
+   * (the finalisation of the small gradients) copies the fp32 scalar *loss_src to *loss_dst - a float in the spare room
+   * behind the caller's gradients, so that the gradient all-reduce sums the ranks' partial losses with no launch and no
+   * collective of its own.  *loss_src must be final when gpsa_step_backward is enqueued (the loss is written by the
+   * ELBO launches in front of it on the same stream).  Either NULL: nothing is written.  Only a backward that closes
+   * (bwd_acc_mode 0 or 3) writes it. */
+  const float* loss_src;
+  float* loss_dst;
 } gpsa_step_io;
 
 typedef struct gpsa_step_out_grads {        /* gradients of the caller's scalar wrt the forward's outputs */

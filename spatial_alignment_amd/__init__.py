@@ -4,6 +4,7 @@ Same public names as the reference package (gpsa/__init__.py:1-10) for the parts
 """
 from .kernels import matern12_kernel, matern32_kernel, rbf_kernel
 from .models import GPSA, VariationalGPSA
+from .parallel import fit
 from .util import (
     ConvergenceChecker,
     LossNotDecreasingChecker,
@@ -23,5 +24,6 @@ __all__ = [
     "get_st_coordinates",
     "LossNotDecreasingChecker",
     "ConvergenceChecker",
+    "fit",
 ]
 __version__ = "0.1.0"

@@ -113,7 +113,7 @@ class StepIO(C.Structure):
         ("F_obs_test", _vp * MAX_MODS), ("mu_z", _vp), ("kl", _vp), ("flag", _vp), ("keep_products", _i),
         ("reuse_mm", _i), ("fuse_elbo", _i), ("Y", _vp * MAX_MODS), ("noise_u", _vp * MAX_MODS),
         ("ll_part", _vp * MAX_MODS), ("F_fused_T", _vp * MAX_MODS), ("bwd_acc", _vp), ("bwd_acc_mode", _i),
-        ("f_event", _vp),
+        ("f_event", _vp), ("loss_src", _vp), ("loss_dst", _vp),
     ]
 
 

@@ -410,6 +410,8 @@ struct FinalArgs {
   const double* dD_d;                                          // [sum L, Mg] or NULL
   int L[MAXMODS], Loff[MAXMODS];
   gpsa_step_param_grads out;
+  const float* loss_src;  // gpsa_step_io.loss_src / loss_dst: the rank's loss into the all-reduce bucket (or NULL)
+  float* loss_dst;
 };
 
 __global__ void __launch_bounds__(256) step_finalize_kernel(FinalArgs a) {
@@ -418,6 +420,8 @@ __global__ void __launch_bounds__(256) step_finalize_kernel(FinalArgs a) {
   long long e = blockIdx.x * 256LL + threadIdx.x;
   const long long nsmall = nX + 2LL * a.V + (long long)a.Mg * D + 2;  // everything in front of delta_F
   if (a.part == 1) e += nsmall;          // (the launch covers the delta_F entries only)
+  // the loss slot rides the closing launch (part 0, or 2 in the early order: part 1 is never the last): thread 0
+  if (a.part != 1 && e == 0 && a.loss_dst != nullptr) *a.loss_dst = *a.loss_src;
   if (a.part == 2 && e >= nsmall) return;
   // --- Xtilde / delta_G
   if (e < nX) {
@@ -2168,6 +2172,10 @@ static int step_backward(Plan& P, const gpsa_step_params& prm, const gpsa_step_i
       nF += (long long)Mg * P.d.n_latent[m];
     }
     a.out = out;
+    if (part != 1 && io.loss_src != nullptr && io.loss_dst != nullptr) {
+      a.loss_src = io.loss_src;
+      a.loss_dst = io.loss_dst;
+    }
     const long long tot = part == 1 ? nF : (part == 2 ? nsmall : nsmall + nF);
     if (!dry && tot > 0) {
       step_finalize_kernel<<<(unsigned)cdiv(tot, 256), 256, 0, st>>>(a);

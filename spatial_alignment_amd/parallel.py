@@ -12,6 +12,8 @@ For many outputs (L = P in the thousands: BASELINE.json configs 4/5) the L axis 
 every rank runs the (cheap, identical) warp GPs, and only the gradients of the shared parameters
 (a few MB) are all-reduced.
 """
+import inspect
+
 import torch
 import torch.distributed as dist
 
@@ -83,7 +85,7 @@ def shared_parameters(model):
     return [p for n, p in model.named_parameters() if not n.startswith(OUTPUT_LOCAL_PREFIXES)]
 
 
-def setup_output_sharding(model, rank, world, seed=0):
+def setup_output_sharding(model, rank, world, seed=0, with_loss=False):
     """Turn a model built on ``shard_outputs(data_dict, rank, world)`` into rank ``rank`` of an
     output-sharded job (no latent mixing: n_latent_gps None, so outputs are independent given G):
 
@@ -93,7 +95,8 @@ def setup_output_sharding(model, rank, world, seed=0):
       aligned coordinates), the output draws from one seeded per rank;
     * shared parameters are broadcast from rank 0 (construction may have consumed the RNG differently).
 
-    Returns the GradAllReducer over the shared parameters: call it between backward() and step()."""
+    Returns the GradAllReducer over the shared parameters (``with_loss``: it sums the ranks' losses too): call it
+    between backward() and step()."""
     for m in model.modality_names:
         if model.n_latent_gps[m] is not None:
             raise ValueError("output sharding needs independent outputs (n_latent_gps[mod] = None)")
@@ -111,7 +114,7 @@ def setup_output_sharding(model, rank, world, seed=0):
                 dist.broadcast(p, src=0)
             for name, b in model.named_buffers():
                 dist.broadcast(b, src=0)
-    return GradAllReducer(shared)
+    return GradAllReducer(shared, with_loss=with_loss)
 
 
 class GradAllReducer:
@@ -122,9 +125,14 @@ class GradAllReducer:
     (step_engine.StepFn.backward), with spare room at its end: when that is what the parameters hold, the
     few gradients from elsewhere (the likelihood's noise parameter) are copied into the spare room and the
     buffer itself is reduced in place - no pack, no unpack.  Otherwise: pack, reduce, unpack.
-    Every call inside it (copies, the RCCL all-reduce) is capturable into a hipGraph."""
+    Every call inside it (copies, the RCCL all-reduce) is capturable into a hipGraph.
 
-    def __init__(self, params, always=False, overlap=False, model=None):
+    ``with_loss=True``: the rank's loss rides the same all-reduce - ``reducer(loss)`` - in the spare room's LAST float
+    (behind the outsiders; on the engine path the backward's closing kernel has already put it there:
+    gpsa_step_io.loss_dst, handed over by train.train_step) or in one extra element of the packed buffer, and
+    ``reducer.loss`` is then the sum over the ranks: the global loss, a one-element device tensor of its own."""
+
+    def __init__(self, params, always=False, overlap=False, model=None, with_loss=False):
         """``overlap`` (with ``model``, a VariationalGPSA on the step engine): the data GP's span of the flat gradient
         buffer (Omega_sqt_F, delta_F, W: 97 % of the bytes at the headline configuration) is reduced on a side stream
         while the rest of the backward - the warp GPs' backward, the priors' covariance backward - still runs; the
@@ -134,6 +142,8 @@ class GradAllReducer:
         self.numel = sum(p.numel() for p in self.params)
         self.flat = None
         self.always = always  # reduce even in a 1-rank group (tests of the capture path)
+        self.with_loss = bool(with_loss)
+        self.loss = None      # with_loss: the last call's loss summed over the ranks ([1], on the loss's device)
         self.overlap = bool(overlap) and model is not None and self.params and self.params[0].is_cuda
         self._early = None    # (flat, lo, hi) of the span whose all-reduce is in flight on the side stream
         if self.overlap:
@@ -176,7 +186,7 @@ class GradAllReducer:
         # the views are padded to 256-byte boundaries: the bucket is the whole span (padding included: its content
         # is reduced too and never read)
         used = LAST_USED.get(p0.device.index, sum(p.numel() for p in inside))
-        if sum(p.numel() for p in outside) > flat.numel() - used:
+        if sum(p.numel() for p in outside) > flat.numel() - used - (1 if self.with_loss else 0):
             return None
         # The buffer may also hold gradients that are NOT this reducer's (output sharding: the per-output parameters'
         # gradients, gigabytes at BASELINE config 4, must stay on their rank): reduce only the spans our parameters
@@ -196,31 +206,55 @@ class GradAllReducer:
             return flat, used, outside, None          # everything in the buffer is ours
         return flat, used, outside, [(a, min(b, used)) for a, b in merged]
 
-    def __call__(self):
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        if dist.get_world_size() == 1 and not self.always:
+    def _loss_in(self, flat, loss):
+        """the rank's loss into ``flat``'s last float, unless the step engine's closing kernel has put it there"""
+        from .step_engine import LAST_LOSS
+
+        done = LAST_LOSS.get(flat.device.index)  # (set by the backward that set the bucket: step_engine.LAST_FLAT)
+        if done is None or done.data_ptr() != loss.data_ptr():
+            flat[-1:].copy_(loss.detach().reshape(1))
+
+    def _tail(self, flat, used, outside):
+        """the spare room's part that is reduced: the outsiders' gradients (copied in), and the loss slot behind them"""
+        n = sum(p.numel() for p in outside)
+        if outside:
+            torch.cat([p.grad.view(-1) for p in outside], out=flat[used: used + n])
+        return flat[used:] if self.with_loss else flat[used: used + n]
+
+    def _tail_out(self, flat, used, outside):
+        if outside:
+            tail = flat[used: used + sum(p.numel() for p in outside)]
+            torch._foreach_copy_([p.grad.view(-1) for p in outside], list(tail.split([p.numel() for p in outside])))
+        if self.with_loss:
+            self.loss = flat[-1:].clone()
+
+    def __call__(self, loss=None):
+        if self.with_loss != (loss is not None):
+            raise ValueError("GradAllReducer: pass the rank's loss exactly when the reducer was built with_loss=True")
+        if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size() == 1 and not self.always):
+            if loss is not None:
+                self.loss = loss.detach().reshape(1).clone()
             return
         for p in self.params:  # a parameter the step did not touch contributes zeros
             if p.grad is None:
                 p.grad = torch.zeros_like(p)
         bucket = self._engine_bucket()
+        if bucket is not None and loss is not None:
+            self._loss_in(bucket[0], loss)
         if self._early is not None:
             eflat, lo, hi = self._early
             self._early = None
             main = torch.cuda.current_stream(eflat.device)
             if bucket is not None and bucket[0] is eflat and bucket[3] is None:
                 # the rest of the buffer - the small parameters and Omega_sqt_G in front of the early span, the
-                # outsiders behind it - on this stream, then the join
+                # outsiders (and the loss) behind it - on this stream, then the join
                 flat, used, outside, _ = bucket
                 if lo > 0:
                     dist.all_reduce(flat[:lo], op=dist.ReduceOp.SUM)
-                if outside:
-                    tail = flat[used: used + sum(p.numel() for p in outside)]
-                    torch.cat([p.grad.view(-1) for p in outside], out=tail)
+                tail = self._tail(flat, used, outside)
+                if tail.numel():
                     dist.all_reduce(tail, op=dist.ReduceOp.SUM)
-                    torch._foreach_copy_([p.grad.view(-1) for p in outside],
-                                         list(tail.split([p.numel() for p in outside])))
+                self._tail_out(flat, used, outside)
                 main.wait_stream(self._side)
                 return
             # Not the layout the shortcut knows (StepFn.backward declines the early reduce when it can tell beforehand;
@@ -232,40 +266,135 @@ class GradAllReducer:
             a, b = eflat.data_ptr() + lo * es, eflat.data_ptr() + hi * es
             rest = [p for p in self.params
                     if not (p.grad.is_contiguous() and p.grad.dtype == eflat.dtype and a <= p.grad.data_ptr() < b)]
-            if rest:
-                tmp = torch.cat([p.grad.reshape(-1).to(eflat.dtype) for p in rest])
+            if rest or loss is not None:
+                extra = [loss.detach().reshape(1).to(eflat.dtype)] if loss is not None else []
+                tmp = torch.cat([p.grad.reshape(-1).to(eflat.dtype) for p in rest] + extra)
                 dist.all_reduce(tmp, op=dist.ReduceOp.SUM)
                 for p, t in zip(rest, tmp.split([p.numel() for p in rest])):
                     p.grad.copy_(t.view_as(p.grad))
+                if loss is not None:
+                    self.loss = tmp[-1:].clone()
             return
         if bucket is not None and bucket[3] is not None:
             flat, used, outside, spans = bucket
             for a, b in spans:
                 dist.all_reduce(flat[a:b], op=dist.ReduceOp.SUM)
-            if outside:
-                tail = flat[used: used + sum(p.numel() for p in outside)]
-                torch.cat([p.grad.view(-1) for p in outside], out=tail)
+            tail = self._tail(flat, used, outside)
+            if tail.numel():
                 dist.all_reduce(tail, op=dist.ReduceOp.SUM)
-                torch._foreach_copy_([p.grad.view(-1) for p in outside],
-                                     list(tail.split([p.numel() for p in outside])))
+            self._tail_out(flat, used, outside)
             return
         if bucket is not None:
             flat, used, outside, _ = bucket
-            if outside:
-                tail = flat[used: used + sum(p.numel() for p in outside)]
-                torch.cat([p.grad.view(-1) for p in outside], out=tail)
-                dist.all_reduce(flat[: used + tail.numel()], op=dist.ReduceOp.SUM)
-                torch._foreach_copy_([p.grad.view(-1) for p in outside],
-                                     list(tail.split([p.numel() for p in outside])))
-            else:
-                dist.all_reduce(flat[:used], op=dist.ReduceOp.SUM)
+            tail = self._tail(flat, used, outside)
+            dist.all_reduce(flat[: used + tail.numel()], op=dist.ReduceOp.SUM)
+            self._tail_out(flat, used, outside)
             return
         p0 = self.params[0]
-        if self.flat is None or self.flat.device != p0.device:
-            self.flat = torch.empty(self.numel, dtype=p0.dtype, device=p0.device)
-            self.views = list(self.flat.split([p.numel() for p in self.params]))
+        extra = 1 if loss is not None else 0
+        if self.flat is None or self.flat.device != p0.device or self.flat.numel() != self.numel + extra:
+            self.flat = torch.empty(self.numel + extra, dtype=p0.dtype, device=p0.device)
+            self.views = list(self.flat[: self.numel].split([p.numel() for p in self.params]))
         # pack (one batched launch), reduce, unpack (one batched launch): not one copy per parameter
         # view(-1), not reshape(-1): a non-contiguous .grad must raise here, not be reduced into a temporary
-        torch.cat([p.grad.view(-1) for p in self.params], out=self.flat)
+        torch.cat([p.grad.view(-1) for p in self.params], out=self.flat[: self.numel])
+        if loss is not None:
+            self.flat[-1:].copy_(loss.detach().reshape(1))
         dist.all_reduce(self.flat, op=dist.ReduceOp.SUM)
         torch._foreach_copy_([p.grad.view(-1) for p in self.params], self.views)
+        if loss is not None:
+            self.loss = self.flat[-1:].clone()
+
+
+SHARDS = ("rows", "outputs")
+KL_MODES = ("owner", "replicated")
+
+
+def _rank_seed(seed, rank, which):
+    """the seed of rank ``rank``'s generator ``which`` (0: warp draws, 1: data-GP draws) of a row-sharded job"""
+    return (int(seed) * 1000003 + 7919 * (int(rank) + 1) + 104729 * which) % (2 ** 63)
+
+
+def _fit_signature(model, shard, kl, n_epochs, fit_kwargs, world):
+    """what every rank of one data-parallel fit must agree on (compared before the first step)"""
+    from . import train
+
+    defaults = {k: v.default for k, v in inspect.signature(train.fit).parameters.items()
+                if v.default is not inspect.Parameter.empty}
+    get = lambda k: fit_kwargs.get(k, defaults.get(k))
+    checker = get("checker")
+    settings = None
+    if checker is not None:
+        settings = (type(checker).__name__,
+                    sorted((k, v) for k, v in vars(checker).items() if isinstance(v, (bool, int, float, str))))
+    params = model.named_parameters() if shard == "rows" else \
+        ((n, p) for n, p in model.named_parameters() if not n.startswith(OUTPUT_LOCAL_PREFIXES))
+    return dict(world=int(world), shard=shard, kl=kl, n_epochs=int(n_epochs), S=get("S"), sync_every=get("sync_every"),
+                lr=get("lr"), checker=settings, params=[(n, tuple(p.shape)) for n, p in params])
+
+
+def fit(model, data_dict, n_epochs, shard="rows", kl="owner", seed=0, **fit_kwargs):
+    """Data-parallel ``train.fit``: one call per rank, under ``torchrun`` or any initialised process group.
+
+    * ``shard="rows"``: ``model`` is built alike on every rank from the FULL ``data_dict``; its parameters and buffers
+      are broadcast from rank 0 (k-means initialisation may differ between ranks), every rank keeps its contiguous
+      slice of each view's rows (``shard_data_dict``) and draws its noise from generators of its own, seeded from
+      ``(seed, rank)`` - the shards draw independent noise, as one process on the full problem would.
+      ``kl="owner"``: each rank evaluates its own range of the KL terms at weight 1 (``own_kl_terms``);
+      ``"replicated"``: every rank all of them at weight 1 / world.
+    * ``shard="outputs"``: ``model`` and ``data_dict`` are this rank's ``shard_outputs`` slice
+      (``setup_output_sharding``: shared warp draws, per-rank output draws; ``kl`` must stay "owner").
+
+    Before the first step one ``all_gather_object`` compares what the ranks must agree on (world, shard, kl, n_epochs,
+    S, sync_every, lr, the checker's class and settings, the shared parameters' names and shapes): on a mismatch EVERY
+    rank raises ValueError.  Each step's gradients and loss are summed by one all-reduce
+    (``GradAllReducer(with_loss=True)``), so the returned trace - ``train.fit``'s - is the global negative ELBO,
+    bit-identical on every rank, and an early stop (``checker``) happens on the same step everywhere.  A rank that
+    raises in the middle of the run (e.g. a non-positive-definite covariance in its own KL range) leaves the others
+    waiting in the all-reduce until the launcher tears the job down.
+
+    World size 1 (or no process group): exactly ``train.fit(model, data_dict, n_epochs, **fit_kwargs)``."""
+    from . import train
+
+    if shard not in SHARDS:
+        raise ValueError(f"parallel.fit: shard must be one of {SHARDS}, not {shard!r}")
+    if kl not in KL_MODES:
+        raise ValueError(f"parallel.fit: kl must be one of {KL_MODES}, not {kl!r}")
+    if shard == "outputs" and kl != "owner":
+        raise ValueError("parallel.fit: kl applies to row sharding (output-sharded ranks own their outputs' KL terms)")
+    if "reducer" in fit_kwargs:
+        raise ValueError("parallel.fit builds the reducer itself")
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return train.fit(model, data_dict, n_epochs, **fit_kwargs)
+    if fit_kwargs.get("graphed"):
+        raise ValueError("parallel.fit: graphed=True (a captured all-reduce) is not supported")
+    rank, world = dist.get_rank(), dist.get_world_size()
+    mine = _fit_signature(model, shard, kl, n_epochs, fit_kwargs, world)
+    every = [None] * world
+    dist.all_gather_object(every, mine)
+    bad = [(r, k) for r, theirs in enumerate(every) for k in mine if theirs[k] != every[0][k]]
+    if bad:
+        r, k = bad[0]
+        raise ValueError(f"parallel.fit: the ranks disagree on {k!r} (rank 0: {every[0][k]!r}, rank {r}: "
+                         f"{every[r][k]!r}); every rank must pass the same arguments")
+    if shard == "outputs":
+        reducer = setup_output_sharding(model, rank, world, seed=seed, with_loss=True)
+        return train.fit(model, data_dict, n_epochs, reducer=reducer, **fit_kwargs)
+    with torch.no_grad():
+        for p in model.parameters():
+            dist.broadcast(p, src=0)
+        for b in model.buffers():
+            dist.broadcast(b, src=0)
+    sdd = shard_data_dict(data_dict, rank, world)
+    if kl == "owner":
+        own_kl_terms(model, rank, world)
+    else:
+        model.kl_scale = 1.0 / world
+    dev = model.Xtilde.device
+    gens = {}
+    for which, key in enumerate(("G", "F")):
+        gens[key] = torch.Generator(device=dev)
+        gens[key].manual_seed(_rank_seed(seed, rank, which))
+    model.noise_generators = gens
+    reducer = GradAllReducer(model.parameters(), with_loss=True)
+    return train.fit(model, sdd, n_epochs, reducer=reducer, **fit_kwargs)

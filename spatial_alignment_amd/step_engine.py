@@ -23,6 +23,7 @@ from .kernels import builtin_kind
 STATS = {"mm_reused": 0}  # forwards that skipped their M x M stage (io.reuse_mm): tests look at it
 LAST_FLAT = {}
 LAST_USED = {}  # floats of LAST_FLAT the gradient views span (each view starts on a 256-byte boundary)
+LAST_LOSS = {}  # the loss tensor the closing kernel copied into LAST_FLAT's last float (gpsa_step_io.loss_dst), or None
 
 MAXM = _lib.MAX_MODS
 KINDS = _ops_mod.KINDS
@@ -343,6 +344,12 @@ def placeholder_grad(dev, n):
     return d
 
 
+def _grad_bucket(n, dev):
+    """the flat fp32 gradient buffer of one backward (uninitialised; its own function so that a test can hand the
+    engine a filled one and see what the backward writes)"""
+    return torch.empty(n, dtype=torch.float32, device=dev)
+
+
 class StepFn(torch.autograd.Function):
     """(parameters) -> G_means[m].., G_samples[m].., F_latent[m].., F_obs[m] (LMC).., test draws.., kl [T].
     ``aux``: everything that is not differentiated (plan, coordinates, draws, stream policy)."""
@@ -581,7 +588,7 @@ class StepFn(torch.autograd.Function):
         for n in sizes:
             offs.append(used)
             used += (n + 63) // 64 * 64
-        flat = torch.empty(used + 64, dtype=f32, device=dev)  # spare room: see parallel.GradAllReducer
+        flat = _grad_bucket(used + 64, dev)  # spare room: see parallel.GradAllReducer
         views = [flat[o: o + n] for o, n in zip(offs, sizes)]
         grads = _lib.StepParamGrads()
         (grads.Xtilde, grads.delta_G, grads.Omega_sqt_G, grads.warp_ls, grads.warp_var, grads.Gtilde, grads.data_ls,
@@ -634,6 +641,18 @@ class StepFn(torch.autograd.Function):
             ctx.io.f_event = early.event_handle()
         else:
             ctx.io.f_event = None
+        # the data-parallel loss slot (parallel.GradAllReducer(with_loss=True); train.train_step hands the loss over
+        # before backward): the closing kernel copies the rank's loss into the flat buffer's last float, where the
+        # gradient all-reduce sums it with the other ranks' - no launch of its own
+        lo = model.__dict__.get("_loss_slot") if (model is not None and closes) else None
+        lo = lo.detach() if lo is not None else None
+        if lo is not None and not (lo.dtype == f32 and lo.numel() == 1 and lo.is_contiguous() and lo.device == dev):
+            lo = None  # (the reducer copies it in itself)
+        if lo is not None:
+            keep.append(lo)
+            ctx.io.loss_src, ctx.io.loss_dst = lo.data_ptr(), flat.data_ptr() + (flat.numel() - 1) * flat.element_size()
+        else:
+            ctx.io.loss_src, ctx.io.loss_dst = None, None
         call = TO.stash(dict(lib=lib, handle=plan.handle, prm=ctx.prm, io=ctx.io, og=og, grads=grads))
         try:
             torch.ops.gpsa.step_backward(list(tensors), keep, ctx.arena, flat, scratch, call)
@@ -646,6 +665,7 @@ class StepFn(torch.autograd.Function):
             out.append(views[i].view(t.shape) if (ctx.needs_input_grad[1 + i] and closes) else None)
         LAST_FLAT[dev.index] = flat
         LAST_USED[dev.index] = used
+        LAST_LOSS[dev.index] = lo
         # the arena (gigabytes when the data GPs keep their products) goes back to the allocator NOW: the node sits
         # in a reference cycle (model -> outputs -> grad_fn -> ctx -> aux -> model) that only the cyclic collector
         # would break, steps later

@@ -22,13 +22,23 @@ def backward(loss):
 def train_step(model, optimizer, data_dict, view_idx, Ns, S=5, reducer=None, static_grads=False):
     """forward(S) + loss_fn + backward + optimizer step; returns the loss tensor (no host sync).
     ``static_grads``: keep the .grad buffers (zeroed, accumulated into) instead of letting autograd hand
-    over fresh ones: needed under graph capture, ~one extra launch per parameter otherwise."""
+    over fresh ones: needed under graph capture, ~one extra launch per parameter otherwise.
+    A ``reducer`` built ``with_loss=True`` (parallel.GradAllReducer) also sums the ranks' losses: the step engine's
+    backward writes this rank's into the gradient bucket (gpsa_step_io.loss_dst), and ``reducer.loss`` is the sum."""
     Xs = {m: d["spatial_coords"] for m, d in data_dict.items()}
     out = model.forward(Xs, view_idx=view_idx, Ns=Ns, S=S)
     loss = model.loss_fn(data_dict, out[3])
     optimizer.zero_grad(set_to_none=not static_grads)
-    backward(loss)
-    if reducer is not None:
+    with_loss = reducer is not None and getattr(reducer, "with_loss", False)
+    if with_loss:
+        model.__dict__["_loss_slot"] = loss  # (read by step_engine.StepFn.backward)
+    try:
+        backward(loss)
+    finally:
+        model.__dict__.pop("_loss_slot", None)
+    if with_loss:
+        reducer(loss)
+    elif reducer is not None:
         reducer()
     optimizer.step()
     return loss
@@ -182,7 +192,7 @@ class Microbatches:
 
 
 def fit(model, data_dict, n_epochs, lr=1e-2, S=5, optimizer=None, checker=None, sync_every=10,
-        callback=None, graphed=False):
+        callback=None, graphed=False, reducer=None):
     """The reference's training loop (examples/grid_example.py:59-78 and the convergence test of
     gpsa/util/util.py:257-278 used by the experiment scripts) as one call.
 
@@ -191,7 +201,18 @@ def fit(model, data_dict, n_epochs, lr=1e-2, S=5, optimizer=None, checker=None, 
     every ``sync_every`` steps only, so the queue is not drained at each iteration; ``checker`` (a
     ``LossNotDecreasingChecker``) is evaluated on the synced values and stops the loop early;
     ``callback(step, model, loss_trace)`` is called at every sync.  ``graphed=True`` replays the step as
-    one hipGraph (single GPU)."""
+    one hipGraph (single GPU).
+
+    ``reducer`` (a ``parallel.GradAllReducer(..., with_loss=True)``; ``parallel.fit`` builds it): one rank of a
+    data-parallel job.  Every step's gradients AND loss are summed over the ranks by the one all-reduce, and the
+    trace holds the summed loss - the global negative ELBO, bit-identical on every rank - so ``checker`` and
+    ``callback`` decide alike everywhere and an early stop happens on the same step on every rank."""
+    if reducer is not None:
+        if graphed:
+            raise ValueError("fit: graphed=True with a reducer (a captured all-reduce) is not supported")
+        if not getattr(reducer, "with_loss", False):
+            raise ValueError("fit: the reducer must carry the loss (GradAllReducer(..., with_loss=True)): the ranks' "
+                             "traces and stopping decisions are made on the summed loss")
     model.train()
     view_idx, Ns, _, _ = model.create_view_idx_dict(data_dict)
     if optimizer is None:
@@ -217,7 +238,9 @@ def fit(model, data_dict, n_epochs, lr=1e-2, S=5, optimizer=None, checker=None, 
         pending.clear()
 
     for it in range(n_epochs):
-        loss = stepper.step() if graphed else train_step(model, optimizer, data_dict, view_idx, Ns, S)
+        loss = stepper.step() if graphed else train_step(model, optimizer, data_dict, view_idx, Ns, S, reducer=reducer)
+        if reducer is not None:
+            loss = reducer.loss.reshape(())  # (the summed loss: a tensor of its own, copied out of the bucket)
         pending.append(loss.detach().clone() if graphed else loss.detach())
         if (it + 1) % sync_every == 0 or it + 1 == n_epochs:
             first = len(trace)
