@@ -1,6 +1,7 @@
 """Headline benchmark: GPSA training steps/sec on the 2-view x 10k-spot, M=200, 50-output grid.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full     (every extra leg as well: minutes)
     python bench.py --gpus N ...          (starts its own N ranks through torch.distributed.run), or under a launcher:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -9,6 +10,12 @@ One step = forward(S) + loss_fn + backward + Adam update (the reference loop,
 examples/grid_example.py:62-78) on synthetic inputs already resident in HBM.  N > 1: the rows of
 every view are sharded over the ranks (strong scaling: total problem fixed), one RCCL all-reduce of the
 flattened gradient per step.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: its roofline comes from
+the HIP events of those very steps, its traffic from the committed profiles/pmc_traffic.json.  --full adds the legs
+that take runs of their own: the helper / verbatim / exact-mode / S = 1 / sustained timings, the hipGraph replay, the
+live rocprofv3 traffic passes, the CPU baseline and the parity check at the bench size, BASELINE configs 1 and 3, the
+bf16 split experiment and the emulated shards.
 """
 import argparse
 import json
@@ -47,17 +54,22 @@ def parse():
                     help="after the timed steps, write what the last one computed (loss, forward outputs, parameters "
                          "after the update and their gradients) as DIR/<name>.npy, at most 64 MB in all: arrays beyond "
                          "their share are cut to a fixed seeded sample of their elements")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beyond the headline figure as well (helper / verbatim / exact-mode / S = 1 / "
+                         "sustained timings, graph replay, live traffic passes, CPU baseline and parity, configs 1 and 3, "
+                         "bf16 split, emulated shards); without it the run is the headline blocks alone")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the config1 / config3 extra keys (BASELINE configs 1 and 3 on this GPU)")
+                    help="--full: skip the config1 / config3 extra keys (BASELINE configs 1 and 3 on this GPU)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="profiling: only the headline blocks (no helper / verbatim / exact-mode / S = 1 / graph / config "
-                         "legs, no CPU baseline)")
+                    help="only the headline blocks (no helper / verbatim / exact-mode / S = 1 / graph / config legs, no "
+                         "CPU baseline): what a run without --full does, and it wins over --full")
     ap.add_argument("--overlap-reduce", action="store_true",
                     help="N > 1: reduce the data GP's span of the gradient buffer on a side stream while the rest of the "
                          "backward runs (parallel.GradAllReducer(overlap=True)); off by default: never run on N > 1 "
                          "distinct devices by the builder")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the live rocprofv3 --pmc passes for roofline.traffic (the committed file is quoted instead)")
+                    help="--full: skip the live rocprofv3 --pmc passes for roofline.traffic (the committed file is quoted "
+                         "instead, as in a run without --full)")
     ap.add_argument("--graph-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--static-grads", action="store_true", help="diagnostic: zero_grad(set_to_none=False)")
     ap.add_argument("--overlap", action="store_true", help="diagnostic: per-view side streams in eager mode too")
@@ -74,8 +86,8 @@ def parse():
                          "(factorises only its variational covariances; the all-reduce sums the shares), 'scaled' = "
                          "every rank evaluates all of them at weight 1/world (rounds 1-5)")
     ap.add_argument("--sustained", type=int, default=1000,
-                    help="extra (default line only): that many consecutive headline steps after the timed blocks, with "
-                         "the clock and power rocm-smi saw meanwhile (0: skip)")
+                    help="--full, default workload only: that many consecutive headline steps after the timed blocks, "
+                         "with the clock and power rocm-smi saw meanwhile (0: skip)")
     ap.add_argument("--emulate-shard", type=int, default=1,
                     help="diagnostic: time rank 0's share of a K-way row sharding on ONE GPU (no all-reduce); "
                          "the line is then NOT the contract metric")
@@ -83,8 +95,6 @@ def parse():
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     args.fixed, args.latent, args.warp = None, None, "rbf"
-    if args.headline_only:
-        args.no_s1 = args.no_graph = args.no_extras = args.no_cpu_baseline = True
     if args.workload == "1":    # examples/grid_example.py: 2 views x 100 spots, 30 outputs, M = 25, fixed_view_idx = 0
         args.side, args.views, args.outputs, args.M, args.fixed = 10, 2, 30, 25, 0
     elif args.workload == "3":  # 4 views x 10k spots, 500 outputs through 10 latent GPs, Matern-1/2 warp, M = 200
@@ -97,6 +107,10 @@ def parse():
         args.no_s1 = args.no_extras = True
         args.no_cpu_baseline = args.workload != "1"  # (config 1 is BASELINE's "CPU reference" configuration)
         args.no_graph = args.workload != "1"
+    if not args.full:
+        args.headline_only = True
+    if args.headline_only:  # (after the workload's defaults: config 1 turns its CPU and graph legs on)
+        args.no_s1 = args.no_graph = args.no_extras = args.no_cpu_baseline = True
     return args
 
 
@@ -371,7 +385,7 @@ def extra_workload(which, args):
     # (config 1's step is ~0.6 ms of ~60 tiny launches: the first ~1000 steps of a process run 30-70 % slow on these
     #  boxes (clocks), so its child warms up for 1000 steps and times blocks of at least 200)
     steps, warm = (max(args.steps, 600), max(args.warmup, 1000)) if which == "1" else (args.steps, args.warmup)
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", which, "--steps", str(steps), "--warmup",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", which, "--steps", str(steps), "--warmup",
            str(warm), "--blocks", "3"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
@@ -611,7 +625,8 @@ def main():
     else:
         model = make_model(dd_full, **mkw)  # identical on every rank (seeded)
         dd = shard_data_dict(dd_full, rank, world * emu)
-    state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if args.workload in ("1", "2") else {}
+    state = ({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+             if args.workload in ("1", "2") and not args.no_cpu_baseline else {})  # (the CPU baseline's start)
     dd = {m: {"spatial_coords": d["spatial_coords"].to(dev), "outputs": d["outputs"].to(dev),
               "n_samples_list": d["n_samples_list"]} for m, d in dd.items()}
     out_reducer = None
@@ -991,6 +1006,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": not args.headline_only,  # (False: the legs beyond the headline figure are null or absent)
             "ms_per_step": 1e3 * dt / args.steps,
             "timing": {"protocol": f"{args.steps} timed steps in {head['blocks']} blocks, barrier + synchronize around "
                                    "each, max over ranks per block; value / ms_per_step = all timed steps over the sum of "

@@ -332,3 +332,58 @@ def test_bench_dump_outputs_cap_and_sample(tmp_path, monkeypatch):
     assert sa.dtype == np.float32 and 0 < sa.size < F.numel() and np.array_equal(sa, sb)
     assert np.isin(sa, F.numpy()).all()
     assert np.array_equal(np.load(tmp_path / "a" / "G_means.m.npy"), fwd["G_means"]["m"].numpy())
+
+
+def _bench_module():
+    import importlib.util
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_is_the_headline_alone_full_runs_every_leg(monkeypatch):
+    """bench.py without --full: the headline blocks alone; --full: every other leg as before (config 1 with its CPU and
+    graph legs), and --headline-only wins over --full"""
+    bench = _bench_module()
+
+    def parse(*argv):
+        monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "3", *argv])
+        return bench.parse()
+
+    legs = ("no_s1", "no_graph", "no_extras", "no_cpu_baseline")
+    for argv in ((), ("--workload", "1"), ("--full", "--headline-only"), ("--full", "--workload", "1", "--headline-only")):
+        a = parse(*argv)
+        assert a.headline_only and all(getattr(a, k) for k in legs), argv
+        assert (a.steps, a.warmup) == (20, 3)
+    a = parse("--full")
+    assert not a.headline_only and not any(getattr(a, k) for k in legs)
+    a = parse("--full", "--workload", "1")
+    assert not a.headline_only and not a.no_cpu_baseline and not a.no_graph and a.no_s1 and a.no_extras
+    a = parse("--full", "--no-cpu-baseline", "--no-graph")
+    assert not a.headline_only and a.no_cpu_baseline and a.no_graph and not a.no_s1 and not a.no_extras
+
+
+def test_bench_full_asks_its_config_children_for_their_full_lines(monkeypatch):
+    """the config1 / config3 keys of a --full line come from child runs of bench.py that run their own extra legs
+    (config 1's verbatim loop, CPU baseline and graph replay): the children are started with --full as well"""
+    import json
+    import subprocess
+    import types
+
+    bench = _bench_module()
+    seen = []
+    child = dict(config=dict(workload="w"), value=1.0, ms_per_step=1.0, timing=dict(ms_per_step_min=1.0, ms_per_step_max=1.0))
+
+    def run(cmd, **kw):
+        seen.append(cmd)
+        return types.SimpleNamespace(returncode=0, stdout=json.dumps(child) + "\n", stderr="")
+
+    monkeypatch.setattr(subprocess, "run", run)
+    args = types.SimpleNamespace(steps=20, warmup=3)
+    for which in ("1", "3"):
+        assert "error" not in bench.extra_workload(which, args)
+    assert len(seen) == 3 and all("--full" in cmd for cmd in seen)  # (config 1 twice: with the step-graph cache on)

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 for rep in 1 2 3; do
   for m in scaled owner; do
-    python3 bench.py --no-cpu-baseline --no-extras --blocks 5 --emulate-shard ${1:-8} --kl-share $m 2>/dev/null | python3 -c "
+    python3 bench.py --full --no-cpu-baseline --no-extras --blocks 5 --emulate-shard ${1:-8} --kl-share $m 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 g=d.get('graph_replay') or {}

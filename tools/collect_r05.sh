@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-5 evidence for profiles/ (GPU box, repo root):  bash tools/collect_r05.sh [tag]  -> gpurun_out/r05/
-#   <tag>_default_bench_line.json        the plain `python bench.py` line (the reference's two-call loop)
+#   <tag>_default_bench_line.json        the `python bench.py --full` line (the reference's two-call loop)
 #   <tag>_default_bench_kernel_stats.csv rocprofv3 --kernel-trace --stats of the same command (shorter run)
 #   <tag>_pmc_fetch_write_summary.txt    HBM-side FETCH_SIZE / WRITE_SIZE, separate --pmc passes (profiles/pmc_summarize.py)
 #   <tag>_pmc_clock_mfma_busy.txt        GRBM_GUI_ACTIVE + SQ_VALU_MFMA_BUSY_CYCLES per kernel
@@ -13,7 +13,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r05
 mkdir -p $O
 cd $R
-python3 bench.py > $O/${T}_default_bench_line.json 2> $O/${T}_bench.log
+python3 bench.py --full > $O/${T}_default_bench_line.json 2> $O/${T}_bench.log
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py --headline-only --blocks 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $B --steps 10 --warmup 2 > $O/stats.log 2>&1
@@ -29,7 +29,7 @@ python3 tools/pmc_by_kernel.py $(find $O/busy -name "*counter_collection.csv" | 
 bash tools/timeline.sh > /dev/null 2>&1
 cp gpurun_out/tl/k1.timeline.txt $O/${T}_step_timeline_k1.txt
 cp gpurun_out/tl/s8.timeline.txt $O/${T}_step_timeline_shard8.txt
-for k in 1 2 4 8; do python3 bench.py --no-cpu-baseline --no-extras --no-graph --blocks 3 --emulate-shard $k 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('shard 1/$k  ms_per_step', round(d['ms_per_step'],3), ' S=1', round(d['secondary_S1']['ms_per_step'],3))"; done > $O/${T}_strong_scaling_emulation.txt
+for k in 1 2 4 8; do python3 bench.py --full --no-cpu-baseline --no-extras --no-graph --blocks 3 --emulate-shard $k 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readline()); print('shard 1/$k  ms_per_step', round(d['ms_per_step'],3), ' S=1', round(d['secondary_S1']['ms_per_step'],3))"; done > $O/${T}_strong_scaling_emulation.txt
 cp profiles/pmc_traffic.json $O/${T}_pmc_traffic.json
 {
   echo "# full step with Adam, one MI355X (tools/run_config.py; config 3: bench.py --workload 3 above)"
