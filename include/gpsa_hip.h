@@ -761,6 +761,37 @@ int gpsa_adam_step(int n, float* const* params, const float* const* grads, float
                    float* const* exp_avg_sq, const long long* numel, double lr, double beta1, double beta2,
                    double eps, float* step, void* stream);
 
+/* ---- minibatch (stochastic variational) training (csrc/minibatch.hip; opt-in) --------------------------------------
+ * gpsa_row_sample_gather: draw step t's batch of every (modality m, view v) and gather it, in one launch plus a one-wave
+ * launch that advances the step counter (counter[0] += 1 on the device: a replayed graph draws the next batch).
+ * n_views[m] views per modality; n_rows / batch: N_{m,v} and B_{m,v} (1 <= B <= N) flattened over (m, v) in order
+ * (at most 64 pairs); the views of modality m are consecutive row blocks of X[m] [sum_v N, D[m]] / Y[m] [sum_v N, P[m]].
+ * With K = N div B, e = t div K, k = t mod K, row j < B of the batch of (m, v) is
+ *     view start + pi_{seed,m,v,e}(k B + j),
+ * pi a keyed bijection of [0, N) (a 6-round alternating Feistel network on ceil(log2 N) bits with cycle-walking; the
+ * package's minibatch.feistel_perm restates it).  Outputs (views one after the other, batch order):
+ * rows[m] [sum_v B] int64 (row numbers of X[m]), Xb[m] [sum_v B, D[m]], Yb[m] [sum_v B, P[m]] (bit-exact copies). */
+int gpsa_row_sample_gather(int n_mods, const int* n_views, const long long* n_rows, const long long* batch,
+                           unsigned long long seed, long long* counter, const float* const* X, const int* D,
+                           const float* const* Y, const int* P, long long* const* rows, float* const* Xb,
+                           float* const* Yb, void* stream);
+/* gpsa_elbo_loss_fwd / _bwd with per-view weights:
+ *   loss[0] = -(sum_i LL_i) + kl_scale * sum_t kl[t],  LL_i = sum_v w_i[v] sum_{rows of v} log N(Y_i; F_i, s_i) / S_i
+ * view v of term i = rows view_off[i][v] .. view_off[i][v + 1] (host array of n_views[i] + 1 offsets, 0 .. N_i;
+ * n_views[i] <= 64); w[i]: DEVICE array of n_views[i] doubles.  ll_out[i] = the weighted LL_i.  The backward's dF_i rows
+ * carry their view's weight, dnoise[i] sums the views' parts with their weights; otherwise as gpsa_elbo_loss_bwd.
+ * workspace >= 8 * 4100 * n_ll bytes. */
+int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                                const int* S, const long long* N, const int* P, const int* n_views,
+                                const long long* const* view_off, const double* const* w, const double* kl, int n_kl,
+                                double kl_scale, float* loss, double* ll_out, void* workspace,
+                                long long workspace_bytes, void* stream);
+int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                                const int* S, const long long* N, const int* P, const int* n_views,
+                                const long long* const* view_off, const double* const* w, const float* gloss, int n_kl,
+                                double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all,
+                                int n_noise, double* dkl, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,12 @@ SIGNATURES.update({
     "gpsa_step_fused": (_i, [_vp, _i]),
     "gpsa_step_contraction": (_i, [_vp, _i]),
     "gpsa_adam_step": (_i, [_i, _pp, _pp, _pp, _pp, C.POINTER(_ll), _d, _d, _d, _d, _vp, _vp]),
+    "gpsa_row_sample_gather": (_i, [_i, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_ll), C.c_ulonglong, _vp, _pp,
+                                    C.POINTER(_i), _pp, C.POINTER(_i), _pp, _pp, _pp, _vp]),
+    "gpsa_elbo_loss_weighted_fwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i),
+                                         C.POINTER(_i), _pp, _pp, _vp, _i, _d, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_elbo_loss_weighted_bwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i),
+                                         C.POINTER(_i), _pp, _pp, _vp, _i, _d, _pp, _pp, _vp, _i, _vp, _vp, _ll, _vp]),
 })
 
 _lib = None

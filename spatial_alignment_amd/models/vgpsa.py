@@ -902,6 +902,39 @@ class VariationalGPSA(GPSA):
             return kl[: V * D].sum() * self.kl_weight_G + kl[V * D:].sum()
         return kl.sum()
 
+    def _view_weights(self, data_dict):
+        """``{"n_views", "view_off", "weights"}`` for WeightedElboLossFn when any modality of ``data_dict`` carries
+        ``"view_weights"`` (one weight per entry of its ``n_samples_list``; a modality without them weighs 1), else
+        None.  The weights go to the kernels as device fp64 tensors: a tensor that already is one is used as it is (a
+        minibatch.RowSampler's batch: the same pointer at every step)."""
+        mods = self.modality_names
+        if not any("view_weights" in data_dict[m] for m in mods):
+            return None
+        dev = self.Xtilde.device
+        n_views, view_off, weights = [], [], []
+        for m in mods:
+            sizes = [int(n) for n in data_dict[m]["n_samples_list"]]
+            w = data_dict[m].get("view_weights")
+            if w is None:
+                ones = self.__dict__.setdefault("_unit_weights", {})
+                w = ones.get((len(sizes), dev))
+                if w is None:
+                    w = ones[(len(sizes), dev)] = torch.ones(len(sizes), dtype=torch.float64, device=dev)
+            else:
+                w = torch.as_tensor(w)
+                if w.dim() != 1 or w.numel() != len(sizes):
+                    raise ValueError(f"loss_fn: view_weights of modality {m!r} has shape {tuple(w.shape)}, "
+                                     f"expected ({len(sizes)},) (one weight per view)")
+                if w.dtype != torch.float64 or w.device != dev or not w.is_contiguous():
+                    w = w.to(device=dev, dtype=torch.float64).contiguous()
+            off = [0]
+            for n in sizes:
+                off.append(off[-1] + n)
+            n_views.append(len(sizes))
+            view_off += off
+            weights.append(w)
+        return dict(n_views=n_views, view_off=view_off, weights=weights)
+
     # ------------------------------------------------------------------------------------------
     def loss_fn(self, data_dict, F_samples):
         """Negative (approximate) ELBO (vgpsa.py:491-540).  Valid only after ``forward`` on the same
@@ -910,6 +943,7 @@ class VariationalGPSA(GPSA):
         if cache is None:
             raise AttributeError("loss_fn called before forward (no factorisations cached)")
         V, D = self.n_views, self.n_spatial_dims
+        weighted = self._view_weights(data_dict)  # minibatch training: per-view likelihood weights (or None)
         if cache.kl is not None:  # forward ran through the step engine: the KL terms came out of its node
             kl = cache.kl if self.kl_scale != 0 else None  # (a slice without a KL share: no KL backward either)
             if kl is not None and self.kl_weight_G != 1.0:  # output-sharded rank: its share of the warp GPs' terms
@@ -918,6 +952,13 @@ class VariationalGPSA(GPSA):
             aux = dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
                        noise_idx=[nn_ - self.n_modalities + i for i in range(self.n_modalities)],  # quirk 5
                        kl_scale=self.kl_scale)
+            if weighted is not None:
+                # weighted terms take the separate kernels: lazy draws / LMC products materialise (the fused closings
+                # have no per-view weights)
+                Fs = [F.materialize() if isinstance(F, (LazyDraws, LazyProduct)) else F
+                      for F in (F_samples[m] for m in self.modality_names)]
+                aux.update(weighted)
+                return SE.WeightedElboLossFn.apply(aux, self.noise_variance, kl, *Fs).to(self.Xtilde.dtype)
             fuse = getattr(cache, "fuse", None)
             Fs, eff, run_i, run_Y, run_parts = [], [], [], [], []
             lmc_terms, Ws, shapes = {}, [], [None] * self.n_modalities
@@ -1002,9 +1043,18 @@ class VariationalGPSA(GPSA):
                                              cache.Omega_F_fac[m]), l_first, 1).sum()
                 l_first += int(self.n_latent_outputs[m])
                 kl = term if kl is None else kl + term
+            if weighted is not None:
+                continue
             noise_u = self.noise_variance[-self.n_modalities + i]  # quirk 5 (used as a std)
             Y = data_dict[m]["outputs"]
             lls.append(E.LogLikFn.apply(F_samples[m], Y, noise_u))
+        if weighted is not None:
+            nn_ = self.noise_variance.numel()
+            aux = dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
+                       noise_idx=[nn_ - self.n_modalities + i for i in range(self.n_modalities)],  # quirk 5
+                       kl_scale=self.kl_scale, **weighted)
+            Fs = [F_samples[m] for m in self.modality_names]
+            return SE.WeightedElboLossFn.apply(aux, self.noise_variance, kl, *Fs).to(self.Xtilde.dtype)
         ll = lls[0] if len(lls) == 1 else torch.stack(lls)
         # -LL + kl_scale * KL in one launch (kl: the per-term vector of the grouped path, or a scalar)
         return E.ElboFn.apply(ll, kl, self.kl_scale).to(self.Xtilde.dtype)

@@ -364,6 +364,8 @@ def fit(model, data_dict, n_epochs, shard="rows", kl="owner", seed=0, **fit_kwar
         raise ValueError("parallel.fit: kl applies to row sharding (output-sharded ranks own their outputs' KL terms)")
     if "reducer" in fit_kwargs:
         raise ValueError("parallel.fit builds the reducer itself")
+    if fit_kwargs.get("batch_size") is not None:
+        raise ValueError("parallel.fit: batch_size (minibatch training) is not supported with data-parallel training")
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         return train.fit(model, data_dict, n_epochs, **fit_kwargs)
     if fit_kwargs.get("graphed"):

@@ -869,3 +869,57 @@ class ElboLossFn(torch.autograd.Function):
                                      float(aux["kl_scale"]), dF, dnoise, dkl, ws)
         shape, dt = ctx.noise_meta
         return (None, dnoise.reshape(shape).to(dt), dkl) + tuple(dF)
+
+
+class WeightedElboLossFn(torch.autograd.Function):
+    """ElboLossFn with per-view weights (minibatch training, minibatch.py):
+    loss = -(sum_i sum_v w_iv LL_iv) + kl_scale * sum(kl)  as one C call each way (gpsa_elbo_loss_weighted_fwd / _bwd).
+    inputs: noise_variance [n], kl (any shape) or None, F_0 .. F_{n_ll-1} (materialised draws [S, N_i, P_i]);
+    aux: Y tensors, noise indices, kl_scale, n_views (per term), view_off (every term's n_views + 1 row offsets,
+    concatenated), weights (per term a device fp64 tensor of n_views entries)"""
+
+    @staticmethod
+    def forward(ctx, aux, noise, kl, *Fs):
+        o = _ops_mod.get_ops()
+        n = len(Fs)
+        dev = Fs[0].device
+        f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+        Fc = [f32(f.detach()) for f in Fs]
+        Yc = [f32(y) for y in aux["Y"]]
+        nz = f32(noise.detach())
+        klc = None
+        if kl is not None:
+            klc = kl.detach().reshape(-1)
+            klc = klc if (klc.dtype == torch.float64 and klc.is_contiguous()) else klc.double().contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ll = torch.empty(n, dtype=torch.float64, device=dev)
+        ws = o._ws(8 * 4100 * n + 64, loss)
+        idx = [int(j) for j in aux["noise_idx"]]
+        torch.ops.gpsa.elbo_loss_weighted_fwd(Fc, Yc, nz, idx, list(aux["n_views"]), list(aux["view_off"]),
+                                              list(aux["weights"]), klc, float(aux["kl_scale"]), loss, ll, ws)
+        ctx.aux, ctx.args = aux, (Fc, Yc, nz, idx)
+        ctx.n_kl = 0 if klc is None else klc.numel()
+        ctx.kl_meta = None if kl is None else (kl.shape, kl.dtype)
+        ctx.noise_meta = (noise.shape, noise.dtype)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        o = _ops_mod.get_ops()
+        aux = ctx.aux
+        Fc, Yc, nz, idx = ctx.args
+        dev = Fc[0].device
+        g = gloss.detach().reshape(1)
+        g = g if g.dtype == torch.float32 else g.float()
+        dF = [torch.empty_like(f) for f in Fc]
+        dnoise = torch.empty(nz.numel(), dtype=torch.float32, device=dev)  # zero-filled by the first finishing launch
+        dkl = torch.empty(ctx.n_kl, dtype=torch.float64, device=dev) if ctx.n_kl else None
+        ws = o._ws(8 * 4100 * len(Fc) + 64, g)
+        torch.ops.gpsa.elbo_loss_weighted_bwd(Fc, Yc, nz, idx, list(aux["n_views"]), list(aux["view_off"]),
+                                              list(aux["weights"]), g, int(ctx.n_kl), float(aux["kl_scale"]), dF,
+                                              dnoise, dkl, ws)
+        if dkl is not None:
+            kshape, kdt = ctx.kl_meta
+            dkl = dkl.reshape(kshape).to(kdt)
+        shape, dt = ctx.noise_meta
+        return (None, dnoise.reshape(shape).to(dt), dkl) + tuple(dF)

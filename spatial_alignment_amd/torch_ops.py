@@ -20,6 +20,8 @@ each with
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
                                             gpsa::elbo_loss_fwd / _bwd, gpsa::adam_step  grid_example.py:59-78)
+   minibatch training (opt-in)              gpsa::row_sample_gather,                   (minibatch.py)
+                                            gpsa::elbo_loss_weighted_fwd / _bwd
 
 The step-engine ops are the ones ``VariationalGPSA.forward`` / ``loss_fn`` / ``FusedAdam`` go through
 (step_engine.py, optim.py): they mutate caller-allocated tensors (outputs, arenas, the flat gradient buffer) and
@@ -411,3 +413,72 @@ def _adam_step(params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps):
 
 _engine_op("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avg, Tensor(c!)[] exp_avg_sq, "
            "Tensor(d!) step, float lr, float beta1, float beta2, float eps) -> ()", _adam_step)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# minibatch (stochastic variational) training: the batch sampler-gather and the per-view weighted likelihood
+# (minibatch.py, csrc/minibatch.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _row_sample_gather(Xs, Ys, n_views, n_rows, batch, seed, counter, rows, Xb, Yb):
+    """gpsa_row_sample_gather: step counter[0]'s batch of every (modality, view) - row numbers, coordinates and
+    observations gathered into rows / Xb / Yb - and counter[0] += 1, all on the device"""
+    n = len(Xs)
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    ints = lambda vals: (C.c_int * len(vals))(*[int(x) for x in vals])
+    lls = lambda vals: (C.c_longlong * len(vals))(*[int(x) for x in vals])
+    _lib.check(_lib.load().gpsa_row_sample_gather(n, ints(n_views), lls(n_rows), lls(batch),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, counter.data_ptr(), arr(Xs),
+                                                  ints([x.shape[1] for x in Xs]), arr(Ys),
+                                                  ints([y.shape[1] for y in Ys]), arr(rows), arr(Xb), arr(Yb),
+                                                  _raw_stream(counter.device.index)), "gpsa_row_sample_gather")
+
+
+_engine_op("row_sample_gather(Tensor[] Xs, Tensor[] Ys, int[] n_views, int[] n_rows, int[] batch, int seed, "
+           "Tensor(a!) counter, Tensor(b!)[] rows, Tensor(c!)[] Xb, Tensor(d!)[] Yb) -> ()", _row_sample_gather)
+
+
+def _view_arrays(n_views, view_off):
+    """flattened per-term view offsets -> (n_views int array, host array of pointers to each term's offsets, keep)"""
+    n = len(n_views)
+    offs, at = [], 0
+    for nv in n_views:
+        offs.append((C.c_longlong * (int(nv) + 1))(*[int(x) for x in view_off[at:at + int(nv) + 1]]))
+        at += int(nv) + 1
+    return (C.c_int * n)(*[int(x) for x in n_views]), (C.c_void_p * n)(*[C.addressof(o) for o in offs]), offs
+
+
+def _elbo_loss_weighted_fwd(Fs, Ys, noise, noise_idx, n_views, view_off, weights, kl, kl_scale, loss, ll, ws):
+    """gpsa_elbo_loss_fwd with per-view fp64 weights: loss = -sum_m sum_v w_mv LL_mv + kl_scale * sum(kl)
+    (view_off: every term's n_views + 1 row offsets, concatenated)"""
+    n, Fp, Yp, Np, Sa, Na, Pa = _ll_arrays(Fs, Ys, noise, noise_idx)
+    nv, offp, _keep = _view_arrays(n_views, view_off)
+    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
+    _lib.check(_lib.load().gpsa_elbo_loss_weighted_fwd(n, Fp, Yp, Np, Sa, Na, Pa, nv, offp, Wp,
+                                                       0 if kl is None else kl.data_ptr(),
+                                                       0 if kl is None else kl.numel(), float(kl_scale),
+                                                       loss.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       _raw_stream(loss.device.index)), "gpsa_elbo_loss_weighted_fwd")
+
+
+_engine_op("elbo_loss_weighted_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] n_views, "
+           "int[] view_off, Tensor[] weights, Tensor? kl, float kl_scale, Tensor(a!) loss, Tensor(b!) ll, "
+           "Tensor(c!) ws) -> ()", _elbo_loss_weighted_fwd)
+
+
+def _elbo_loss_weighted_bwd(Fs, Ys, noise, noise_idx, n_views, view_off, weights, gloss, n_kl, kl_scale, dFs, dnoise,
+                            dkl, ws):
+    n, Fp, Yp, Np, Sa, Na, Pa = _ll_arrays(Fs, Ys, noise, noise_idx)
+    nv, offp, _keep = _view_arrays(n_views, view_off)
+    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
+    dFp = (C.c_void_p * n)(*[t.data_ptr() for t in dFs])
+    dNp = (C.c_void_p * n)(*[dnoise.data_ptr() + 4 * j for j in noise_idx])
+    _lib.check(_lib.load().gpsa_elbo_loss_weighted_bwd(n, Fp, Yp, Np, Sa, Na, Pa, nv, offp, Wp, gloss.data_ptr(),
+                                                       int(n_kl), float(kl_scale), dFp, dNp, dnoise.data_ptr(),
+                                                       dnoise.numel(), 0 if dkl is None else dkl.data_ptr(),
+                                                       ws.data_ptr(), ws.numel(), _raw_stream(gloss.device.index)),
+               "gpsa_elbo_loss_weighted_bwd")
+
+
+_engine_op("elbo_loss_weighted_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] n_views, "
+           "int[] view_off, Tensor[] weights, Tensor gloss, int n_kl, float kl_scale, Tensor(a!)[] dFs, "
+           "Tensor(b!) dnoise, Tensor(c!)? dkl, Tensor(d!) ws) -> ()", _elbo_loss_weighted_bwd)

@@ -19,12 +19,20 @@ def backward(loss):
     loss.backward(one)
 
 
-def train_step(model, optimizer, data_dict, view_idx, Ns, S=5, reducer=None, static_grads=False):
+def train_step(model, optimizer, data_dict, view_idx, Ns, S=5, reducer=None, static_grads=False, sampler=None,
+               noise=None):
     """forward(S) + loss_fn + backward + optimizer step; returns the loss tensor (no host sync).
     ``static_grads``: keep the .grad buffers (zeroed, accumulated into) instead of letting autograd hand
     over fresh ones: needed under graph capture, ~one extra launch per parameter otherwise.
     A ``reducer`` built ``with_loss=True`` (parallel.GradAllReducer) also sums the ranks' losses: the step engine's
-    backward writes this rank's into the gradient bucket (gpsa_step_io.loss_dst), and ``reducer.loss`` is the sum."""
+    backward writes this rank's into the gradient bucket (gpsa_step_io.loss_dst), and ``reducer.loss`` is the sum.
+    ``sampler`` (minibatch.RowSampler): the step draws its batch first and trains on it (``data_dict``, ``view_idx``
+    and ``Ns`` are then not used).  ``noise``: ``(eps_G, eps_F)`` for ``model.inject_noise`` before the forward."""
+    if sampler is not None:
+        batch = sampler.next()
+        data_dict, view_idx, Ns = batch.data_dict, batch.view_idx, batch.Ns
+    if noise is not None:
+        model.inject_noise(noise[0], noise[1], None)
     Xs = {m: d["spatial_coords"] for m, d in data_dict.items()}
     out = model.forward(Xs, view_idx=view_idx, Ns=Ns, S=S)
     loss = model.loss_fn(data_dict, out[3])
@@ -192,7 +200,7 @@ class Microbatches:
 
 
 def fit(model, data_dict, n_epochs, lr=1e-2, S=5, optimizer=None, checker=None, sync_every=10,
-        callback=None, graphed=False, reducer=None):
+        callback=None, graphed=False, reducer=None, batch_size=None, sample_seed=0):
     """The reference's training loop (examples/grid_example.py:59-78 and the convergence test of
     gpsa/util/util.py:257-278 used by the experiment scripts) as one call.
 
@@ -206,7 +214,15 @@ def fit(model, data_dict, n_epochs, lr=1e-2, S=5, optimizer=None, checker=None, 
     ``reducer`` (a ``parallel.GradAllReducer(..., with_loss=True)``; ``parallel.fit`` builds it): one rank of a
     data-parallel job.  Every step's gradients AND loss are summed over the ranks by the one all-reduce, and the
     trace holds the summed loss - the global negative ELBO, bit-identical on every rank - so ``checker`` and
-    ``callback`` decide alike everywhere and an early stop happens on the same step on every rank."""
+    ``callback`` decide alike everywhere and an early stop happens on the same step on every rank.
+
+    ``batch_size`` (an int per view, or ``{mod: [B_v]}``): minibatch (stochastic variational) training.  Each step
+    trains on a batch drawn on the device by a ``minibatch.RowSampler(model, data_dict, batch_size, sample_seed)``,
+    the batch rows' log-likelihood weighted by N_v / B_v, the KL terms whole; the trace holds these unbiased estimates
+    of the full negative ELBO.  With ``graphed=True`` the draw is part of the captured step.  Not combinable with a
+    ``reducer`` (data-parallel minibatches are out of scope)."""
+    if batch_size is not None and reducer is not None:
+        raise ValueError("fit: batch_size (minibatch training) with a reducer (data-parallel training) is not supported")
     if reducer is not None:
         if graphed:
             raise ValueError("fit: graphed=True with a reducer (a captured all-reduce) is not supported")
@@ -223,7 +239,12 @@ def fit(model, data_dict, n_epochs, lr=1e-2, S=5, optimizer=None, checker=None, 
             optimizer = FusedAdam(ps, lr=lr)
         else:  # CPU, model.double(), ...: what the reference's loop uses
             optimizer = torch.optim.Adam(ps, lr=lr, capturable=bool(graphed))
-    stepper = GraphedTrainStep(model, optimizer, data_dict, view_idx, Ns, S=S) if graphed else None
+    sampler = None
+    if batch_size is not None:
+        from .minibatch import RowSampler
+
+        sampler = RowSampler(model, data_dict, batch_size, seed=sample_seed)
+    stepper = GraphedTrainStep(model, optimizer, data_dict, view_idx, Ns, S=S, sampler=sampler) if graphed else None
     trace, pending = [], []
     # what exists by now (torch, the model, the plans) is long-lived: out of the cyclic collector's way for the loop.
     # A generation-2 collection over that heap costs 40-100 ms (round 6: the one slow block of every bench run, at the
@@ -238,7 +259,8 @@ def fit(model, data_dict, n_epochs, lr=1e-2, S=5, optimizer=None, checker=None, 
         pending.clear()
 
     for it in range(n_epochs):
-        loss = stepper.step() if graphed else train_step(model, optimizer, data_dict, view_idx, Ns, S, reducer=reducer)
+        loss = stepper.step() if graphed else train_step(model, optimizer, data_dict, view_idx, Ns, S, reducer=reducer,
+                                                         sampler=sampler)
         if reducer is not None:
             loss = reducer.loss.reshape(())  # (the summed loss: a tensor of its own, copied out of the bucket)
         pending.append(loss.detach().clone() if graphed else loss.detach())
@@ -265,10 +287,15 @@ class GraphedTrainStep:
       ``check()`` raises if any step since the last check tripped it (call it every N steps);
     * the optimizer must be capturable (``optim.FusedAdam`` or ``torch.optim.Adam(..., capturable=True)``);
     * ``reducer`` (parallel.GradAllReducer): the data-parallel all-reduce of the gradients is captured too -
-      RCCL collectives are capturable - so every rank of a sharded job replays ONE graph per step.
+      RCCL collectives are capturable - so every rank of a sharded job replays ONE graph per step;
+    * ``sampler`` (minibatch.RowSampler): the batch draw is captured too (it reads and advances the sampler's device
+      counter), so every replay trains on the next batch; the warm-up steps consume batches like any other step;
+    * ``noise`` (``(eps_G, eps_F)``, tests): injected before every warm-up step and the capture - the replays read
+      those tensors instead of drawing.
     """
 
-    def __init__(self, model, optimizer, data_dict, view_idx, Ns, S=5, warmup=3, reducer=None):
+    def __init__(self, model, optimizer, data_dict, view_idx, Ns, S=5, warmup=3, reducer=None, sampler=None,
+                 noise=None):
         if not torch.cuda.is_available():
             raise RuntimeError("GraphedTrainStep needs a HIP device")
         self.model, self.optimizer = model, optimizer
@@ -286,7 +313,8 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):  # warm-up off the default stream, as torch's capture rules ask
             for _ in range(warmup):
-                train_step(model, optimizer, data_dict, view_idx, Ns, S, reducer=reducer, static_grads=True)
+                train_step(model, optimizer, data_dict, view_idx, Ns, S, reducer=reducer, static_grads=True,
+                           sampler=sampler, noise=noise)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -294,7 +322,8 @@ class GraphedTrainStep:
         # legal during the capture: thread-local capture mode
         mode = {"capture_error_mode": "thread_local"} if reducer is not None else {}
         with torch.cuda.graph(self.graph, **mode):
-            self.loss = train_step(model, optimizer, data_dict, view_idx, Ns, S, reducer=reducer, static_grads=True)
+            self.loss = train_step(model, optimizer, data_dict, view_idx, Ns, S, reducer=reducer, static_grads=True,
+                                   sampler=sampler, noise=noise)
             flags = [f.reshape(-1).to(torch.int32) for f in model._cache.flags]
             # the step engine folds its Cholesky infos and variance flags into ONE device word (check_numerics is
             # off inside the capture, so nobody else reads it): a non-positive pivot is replaced by 1 and trains on
