@@ -792,6 +792,27 @@ int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* co
                                 double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all,
                                 int n_noise, double* dkl, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- prediction: closed-form moments of the data GP (csrc/predict.hip) ----------------------------------------------
+ * The counterpart of gpsa_data_sample_fwd: from a chunk of c rows evaluated at S warp samples - meanT, v [L, S*c] fp32
+ * (column s*c + r), q [S*c] fp64, var_u as there - it forms per sample the conditional of vgpsa.py:174-204,
+ *   mu_s[r,l] = meanT[l, s c + r],  sigma2_s[r,l] = (exp(var_u) - q[s c + r])_fp64 + v[l, s c + r] + 2e-5,
+ * mixes it with W [L,P] (LMC, vgpsa.py:428-432; W = NULL: P == L, no mix) per sample,
+ *   m_s = mu_s W,  u_s = sigma2_s (W o W),
+ * and reduces the S samples inside the kernel (law of total variance; fp64 arithmetic, centred sums):
+ *   F_mean[r,p] = mean_s m_s,  F_var[r,p] = mean_s u_s + mean_s (m_s - F_mean)^2  (+ tau^2 when include_noise),
+ *   tau = exp(noise_u[0]) + 1e-5 used as a standard deviation (vgpsa.py:217, 532-538).
+ * Y [c,P] (may be NULL, then lpd must be NULL too): lpd[r] = sum_p log( mean_s N(Y[r,p]; m_s, u_s + tau^2) ) in fp64,
+ * always with the noise, NaN entries of Y skipped, the mixture through a running maximum.
+ * Fl_mean / Fl_var [c,L] (both or neither): the same moments of the latent outputs (no mix, no noise).
+ * It stands for the draw-and-average idiom of the reference's prediction scripts
+ * (experiments/expression/slideseq/slideseq_prediction.py:360-368: forward(prediction_mode=True, S) + mean over draws).
+ * Nothing of size S*c*L or S*c*P is written; no workspace.  Any c, S, L, P >= 1; with W: L <= 64
+ * (GPSA_EUNSUPPORTED beyond), GPSA_EINVAL on W == NULL with P != L or a missing noise_u. */
+int gpsa_predict_moments_f32(const float* meanT, const float* v, const double* q, const float* var_u, long long c,
+                             int S, int L, int P, const float* W, const float* noise_u, int include_noise,
+                             const float* Y, float* F_mean, float* F_var, float* Fl_mean, float* Fl_var, double* lpd,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

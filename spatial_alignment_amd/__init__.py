@@ -5,6 +5,7 @@ Same public names as the reference package (gpsa/__init__.py:1-10) for the parts
 from .kernels import matern12_kernel, matern32_kernel, rbf_kernel
 from .models import GPSA, VariationalGPSA
 from .parallel import fit
+from .predict import predict
 from .util import (
     ConvergenceChecker,
     LossNotDecreasingChecker,
@@ -25,5 +26,6 @@ __all__ = [
     "LossNotDecreasingChecker",
     "ConvergenceChecker",
     "fit",
+    "predict",
 ]
 __version__ = "0.1.0"

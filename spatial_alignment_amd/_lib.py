@@ -209,6 +209,8 @@ SIGNATURES.update({
                                          C.POINTER(_i), _pp, _pp, _vp, _i, _d, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_elbo_loss_weighted_bwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i),
                                          C.POINTER(_i), _pp, _pp, _vp, _i, _d, _pp, _pp, _vp, _i, _vp, _vp, _ll, _vp]),
+    "gpsa_predict_moments_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
 })
 
 _lib = None

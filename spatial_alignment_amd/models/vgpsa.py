@@ -655,6 +655,14 @@ class VariationalGPSA(GPSA):
             )
         return G_means, G_samples, self.F_latent_samples, self.F_observed_samples
 
+    def predict(self, X_spatial=None, view_idx=None, Ns=None, **kwargs):
+        """Closed-form posterior moments and the held-out log predictive density (``predict.predict``): ``G_mean`` /
+        ``G_scale`` of the warp, ``F_mean`` / ``F_var`` of the outputs over S warp samples, ``lpd`` with observations -
+        in row chunks, without draws of the data GP and without touching the training state."""
+        from ..predict import predict as _predict
+
+        return _predict(self, X_spatial, view_idx, Ns, **kwargs)
+
     def _lazy_obs(self, plan, G_test, prediction_mode, grads):
         """per modality: True = an LMC modality whose F_obs = F_latent W is left to whoever asks for it (training;
         loss_fn runs gpsa_lmc_loglik_fused_f32 on (F_latent, W, Y) instead of forming it).  ``grads``: gradients are

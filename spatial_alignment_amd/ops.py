@@ -466,6 +466,46 @@ class HipOps:
         _lib.check(rc, "gpsa_data_sample_bwd")
         return g_ext, dmeanT, dvar
 
+    def predict_moments(self, meanT, v, q, var_u, S, W=None, noise_u=None, include_noise=False, Y=None,
+                        latent=False, out=None):
+        """gpsa_predict_moments_f32: the data GP's closing as moments instead of a draw.  meanT, v [L, S*c] fp32 (column
+        s*c + r), q [S*c] fp64, var_u / noise_u device scalars (unconstrained), W [L,P] or None (then P = L), Y [c,P] or
+        None.  -> (F_mean, F_var [c,P] fp32, Fl_mean, Fl_var [c,L] fp32 or None, lpd [c] fp64 or None); ``out``: the same
+        five, preallocated (contiguous row slices of the caller's result tensors; None where nothing is wanted)."""
+        meanT, v, q = self._c(meanT), self._c(v), self._c(q.double())
+        L, SC = meanT.shape
+        S = int(S)
+        if S < 1 or SC % S != 0 or tuple(v.shape) != (L, SC) or q.numel() != SC:
+            raise ValueError(f"predict_moments: meanT {tuple(meanT.shape)}, v {tuple(v.shape)}, q {tuple(q.shape)} do not "
+                             f"hold S = {S} samples of the same rows")
+        c = SC // S
+        var_u = self._f32(var_u).reshape(-1)
+        W = None if W is None else self._f32(W)
+        if W is not None and W.shape[0] != L:
+            raise ValueError(f"predict_moments: W has {W.shape[0]} rows, the data GP {L} latent outputs")
+        P = L if W is None else int(W.shape[1])
+        noise_u = None if noise_u is None else self._f32(noise_u).reshape(-1)
+        Y = None if Y is None else self._f32(Y)
+        if Y is not None and tuple(Y.shape) != (c, P):
+            raise ValueError(f"predict_moments: Y has shape {tuple(Y.shape)}, the chunk needs ({c}, {P})")
+        dev, f32 = meanT.device, torch.float32
+        if out is None:
+            new = lambda *sh, dt=f32: torch.empty(*sh, dtype=dt, device=dev)
+            out = (new(c, P), new(c, P), new(c, L) if latent else None, new(c, L) if latent else None,
+                   new(c, dt=torch.float64) if Y is not None else None)
+        Fm, Fv, Lm, Lv, lpd = out
+        for t, sh, dt in ((Fm, (c, P), f32), (Fv, (c, P), f32), (Lm, (c, L), f32), (Lv, (c, L), f32),
+                          (lpd, (c,), torch.float64)):
+            assert t is None or (tuple(t.shape) == sh and t.dtype == dt and t.is_contiguous()), (sh, dt)
+        rc = self.lib.gpsa_predict_moments_f32(_p(meanT), _p(v), _p(q), _p(var_u), c, S, L, P, _p(W), _p(noise_u),
+                                               int(bool(include_noise)), _p(Y), _p(Fm), _p(Fv), _p(Lm), _p(Lv), _p(lpd),
+                                               self._stream(meanT))
+        if rc == _lib.GPSA_EUNSUPPORTED:
+            raise _lib.GpsaHipError(f"gpsa_predict_moments_f32: an LMC mix of {L} latent outputs (more than 64, the "
+                                    "limit the LDS-resident W shares with the training kernels)")
+        _lib.check(rc, "gpsa_predict_moments_f32")
+        return Fm, Fv, Lm, Lv, lpd
+
     @staticmethod
     def _f32(t):
         t = t if t.dtype == torch.float32 else t.float()

@@ -16,6 +16,7 @@ each with
    (3) quadratic form (the star kernel)     gpsa::quadform, gpsa::quadform_bwd_alpha,  (vgpsa.py:192-196)
                                             gpsa::quadform_bwd_omega
    (4) reparameterised draws                gpsa::gauss_sample_F (+ _bwd)              (vgpsa.py:423-426)
+       ... closed as moments (prediction)   gpsa::predict_moments                      (predict.py)
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
@@ -28,6 +29,7 @@ The step-engine ops are the ones ``VariationalGPSA.forward`` / ``loss_fn`` / ``F
 take the non-tensor part of the call (plan handle, pointer structs) as an integer key into ``CALLS``.
 """
 import ctypes as C
+from typing import Optional
 
 import torch
 
@@ -212,6 +214,30 @@ def _gs_backward(ctx, dF, dSigma):
 
 
 gauss_sample_F.register_autograd(_gs_backward, setup_context=_gs_setup)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# (4b) the same layer closed as moments (prediction): mixture over S warp samples, reduced in the kernel
+# ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("gpsa::predict_moments", mutates_args=(), device_types="cuda")
+def predict_moments(meanT: torch.Tensor, v: torch.Tensor, q: torch.Tensor, var_u: torch.Tensor, S: int,
+                    W: Optional[torch.Tensor] = None, noise_u: Optional[torch.Tensor] = None,
+                    include_noise: bool = False, Y: Optional[torch.Tensor] = None,
+                    latent: bool = False) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """meanT, v [L, S*c]; q [S*c] -> (F_mean, F_var [c, P], Fl_mean, Fl_var [c, L], lpd [c] fp64); the latent pair and
+    lpd are empty tensors when not asked for (predict.py; slideseq_prediction.py:360-368 in closed form)"""
+    Fm, Fv, Lm, Lv, lpd = _o().predict_moments(meanT, v, q, var_u, S, W, noise_u, include_noise, Y, latent)
+    none = lambda t, dt: meanT.new_empty(0, dtype=dt) if t is None else t
+    return Fm, Fv, none(Lm, torch.float32), none(Lv, torch.float32), none(lpd, torch.float64)
+
+
+@predict_moments.register_fake
+def _(meanT, v, q, var_u, S, W=None, noise_u=None, include_noise=False, Y=None, latent=False):
+    L, c = meanT.shape[0], meanT.shape[1] // S
+    P = L if W is None else W.shape[1]
+    lat = (c, L) if latent else (0,)
+    return (meanT.new_empty(c, P), meanT.new_empty(c, P), meanT.new_empty(lat), meanT.new_empty(lat),
+            meanT.new_empty(c if Y is not None else 0, dtype=torch.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------
