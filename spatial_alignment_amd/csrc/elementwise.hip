@@ -848,16 +848,15 @@ namespace gpsa {
 // in a replayed graph with parallel branches that node was seen to land AFTER the kernel node behind it on the same
 // stream (the step's backward: the word the next kernel read still held the forward's scratch; found when that kernel
 // became the region's first reader - tests/test_hip_parity.py::test_eager_forward_between_graph_replays...).  A kernel
-// node is ordered like every other launch.  GPSA_ZERO_KERNEL=0: the runtime's memset.
+// node is ordered like every other launch.  (A pointer that is not 16-byte aligned takes the runtime's memset.)
 __global__ void __launch_bounds__(256) zero_fill_kernel(uint4* __restrict__ p, long long n16, int tail) {
   const long long i = blockIdx.x * 256LL + threadIdx.x;
   if (i < n16) p[i] = make_uint4(0, 0, 0, 0);
   if (blockIdx.x == 0 && (int)threadIdx.x < tail) reinterpret_cast<unsigned char*>(p + n16)[threadIdx.x] = 0;
 }
 int zero_fill_async(void* ptr, size_t bytes, hipStream_t st) {
-  static const bool off = [] { const char* e = getenv("GPSA_ZERO_KERNEL"); return e && e[0] == '0'; }();
   if (bytes == 0) return 0;
-  if (off || (reinterpret_cast<uintptr_t>(ptr) & 15)) return (int)hipMemsetAsync(ptr, 0, bytes, st);
+  if (reinterpret_cast<uintptr_t>(ptr) & 15) return (int)hipMemsetAsync(ptr, 0, bytes, st);
   const long long n16 = (long long)(bytes / 16);
   const long long blocks = n16 > 0 ? cdiv(n16, 256) : 1;
   zero_fill_kernel<<<(unsigned)blocks, 256, 0, st>>>(reinterpret_cast<uint4*>(ptr), n16, (int)(bytes % 16));
@@ -874,9 +873,8 @@ __global__ void __launch_bounds__(256) copy_kernel(uint4* __restrict__ d, const 
     reinterpret_cast<unsigned char*>(d + n16)[threadIdx.x] = reinterpret_cast<const unsigned char*>(s + n16)[threadIdx.x];
 }
 int copy_async(void* dst, const void* src, size_t bytes, hipStream_t st) {
-  static const bool off = [] { const char* e = getenv("GPSA_ZERO_KERNEL"); return e && e[0] == '0'; }();
   if (bytes == 0) return 0;
-  if (off || ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15))
+  if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15)
     return (int)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
   const long long n16 = (long long)(bytes / 16);
   const long long blocks = n16 > 0 ? cdiv(n16, 256) : 1;

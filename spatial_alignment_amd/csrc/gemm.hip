@@ -18,118 +18,10 @@ struct GemmSeg2 {
   TO* C;
 };
 
-template <typename T, bool TA, bool TB>
-__global__ void __launch_bounds__(256, 4)
-gemm_kernel(int m, int n, long long k, T alpha, const T* __restrict__ A, long long lda,
-            long long sA, const T* __restrict__ B, long long ldb, long long sB, T beta,
-            T* __restrict__ C, long long ldc, long long sC, int splitk, T* __restrict__ part) {
-  __shared__ T As[GB_K][GB_M + 4];
-  __shared__ T Bs[GB_K][GB_N + 4];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const int b = blockIdx.z / splitk, sp = blockIdx.z % splitk;
-  const int m0 = blockIdx.y * GB_M, n0 = blockIdx.x * GB_N;
-  long long kchunk = (k + splitk - 1) / splitk;
-  kchunk = (kchunk + GB_K - 1) / GB_K * GB_K;
-  const long long kbeg = (long long)sp * kchunk;
-  const long long kend = (kbeg + kchunk < k) ? kbeg + kchunk : k;
-  const T* Ab = A + (long long)b * sA;
-  const T* Bb = B + (long long)b * sB;
-  T acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = T(0);
-
-  // register-staged software pipeline: the global loads of K tile t+1 are in flight while tile t is
-  // multiplied out of LDS (the small M x M products of the step are latency-, not throughput-bound)
-  T ra[4], rb[4];
-  auto fetch = [&](long long k0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + i * 256;
-      int r, kk;
-      if (TA) { r = e % GB_M; kk = e / GB_M; } else { r = e / GB_K; kk = e % GB_K; }
-      const long long gr = m0 + r, gk = k0 + kk;
-      T v = T(0);
-      if (gr < m && gk < kend) v = TA ? Ab[gk * lda + gr] : Ab[gr * lda + gk];
-      ra[i] = v;
-      int c, kb;
-      if (TB) { kb = e % GB_K; c = e / GB_K; } else { c = e % GB_N; kb = e / GB_N; }
-      const long long gc = n0 + c, gk2 = k0 + kb;
-      T u = T(0);
-      if (gc < n && gk2 < kend) u = TB ? Bb[gc * ldb + gk2] : Bb[gk2 * ldb + gc];
-      rb[i] = u;
-    }
-  };
-  auto stash = [&]() {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + i * 256;
-      int r, kk;
-      if (TA) { r = e % GB_M; kk = e / GB_M; } else { r = e / GB_K; kk = e % GB_K; }
-      As[kk][r] = ra[i];
-      int c, kb;
-      if (TB) { kb = e % GB_K; c = e / GB_K; } else { c = e % GB_N; kb = e / GB_N; }
-      Bs[kb][c] = rb[i];
-    }
-  };
-  if (kbeg < kend) {
-    fetch(kbeg);
-    stash();
-  }
-  __syncthreads();
-  for (long long k0 = kbeg; k0 < kend; k0 += GB_K) {
-    const bool more = k0 + GB_K < kend;
-    if (more) fetch(k0 + GB_K);
-#pragma unroll 4
-    for (int kk = 0; kk < GB_K; ++kk) {
-      T a[4], bb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = As[kk][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bb[j] = Bs[kk][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] += a[i] * bb[j];
-    }
-    __syncthreads();
-    if (more) stash();
-    __syncthreads();
-  }
-  if (splitk == 1) {
-    T* Cb = C + (long long)b * sC;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = m0 + ty * 4 + i;
-      if (r >= m) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = n0 + tx * 4 + j;
-        if (c >= n) continue;
-        T* p = Cb + (long long)r * ldc + c;
-        *p = (beta == T(0)) ? alpha * acc[i][j] : alpha * acc[i][j] + beta * (*p);
-      }
-    }
-  } else {
-    T* P = part + ((long long)blockIdx.z) * m * n;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = m0 + ty * 4 + i;
-      if (r >= m) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = n0 + tx * 4 + j;
-        if (c < n) P[(long long)r * n + c] = acc[i][j];
-      }
-    }
-  }
-}
-
-// fp64 variant on the matrix cores (v_mfma_f64_16x16x4_f64): same 64 x 64 x 16 workgroup tile and the
-// same register-staged prefetch, but each wave owns a 32 x 32 quadrant as 2 x 2 MFMA tiles, so one K
-// step of 4 costs 4 LDS fragment reads per 4 MFMAs instead of 4 ds_read_b128 per 16 vector FMAs (the
-// vector kernel above is LDS-bandwidth-bound at twice its FMA time in fp64).
+// The product on the matrix cores (v_mfma_f64_16x16x4_f64): a 64 x 64 x 16 workgroup tile with a
+// register-staged prefetch; each wave owns a 32 x 32 quadrant as 2 x 2 MFMA tiles, so one K step of 4
+// costs 4 LDS fragment reads per 4 MFMAs (the vector-FMA kernel of the same tile that stood here until
+// every product moved to this one was LDS-bandwidth-bound at twice its FMA time in fp64).
 
 // TIA / TIB: storage types of the operands (fp32 parameters are read as stored and widened), TO: type of
 // C; SYMA: the left operand is A + A^T (square A); diag is added to C[i][i] (split-K == 1 only).  These
@@ -388,11 +280,6 @@ splitk_reduce_kernel(const T* __restrict__ part, int batch, int splitk, int m, i
   }
 }
 
-static inline bool gemm_force_vector() {
-  static const bool v = [] { const char* e = getenv("GPSA_GEMM_VECTOR"); return e && e[0] == '1'; }();
-  return v;
-}
-
 template <typename T>
 int gemm_launch_tri(int transA, int transB, int m, int n, long long k, double alpha, const T* A,
                     long long lda, long long sA, const T* B, long long ldb, long long sB, double beta,
@@ -441,32 +328,19 @@ int gemm_launch_scaled(int transA, int transB, int m, int n, long long k, double
     part = reinterpret_cast<T*>(ws);
   }
   dim3 grid((unsigned)cdiv(n, GB_N), (unsigned)cdiv(m, GB_M), (unsigned)(batch * splitk));
-#define GPSA_GEMM_CASE(TA, TB)                                                               \
-  gemm_kernel<T, TA, TB><<<grid, 256, 0, st>>>(m, n, k, (T)alpha, A, lda, sA, B, ldb, sB,     \
-                                               (T)beta, C, ldc, sC, splitk, part)
 #define GPSA_GEMMX_CASE(TA, TB)                                                                     \
   gemm_mfma_kernel<T, TA, TB><<<grid, 256, 0, st>>>(m, n, k, (T)alpha, A, lda, sA, B, ldb, sB, (T)beta, \
                                                     C, ldc, sC, splitk, part, T(0), tri, kscale, sKs, cscale, sCs)
-  // products with at least one MFMA tile in each direction run on the matrix cores (always with a triangle
-  // mode or a scale vector: only that kernel knows them)
+  // every product runs on the matrix cores
   // (round 4: also products with fewer than 16 rows or columns - the matrix-core kernel pads them inside a tile and
-  //  is 1.1 - 2.3 times faster than the vector kernel on every such product of a step: the ten-latent-GP mean term
-  //  96 -> 42 us, its adjoint 122 -> 61, the LMC products 209 -> 114 and 255 -> 126, the warp GPs' [M, 2] gradient
-  //  14.0 -> 12.6; GPSA_GEMM_MFMA_MIN=16 restores the old rule)
-  static const int mfma_min = [] { const char* e = getenv("GPSA_GEMM_MFMA_MIN"); return e ? atoi(e) : 1; }();
-  const bool mfma = (m >= mfma_min && n >= mfma_min && !gemm_force_vector()) || tri != GEMM_TRI_NONE ||
-                    kscale != nullptr || cscale != nullptr;
+  //  was 1.1 - 2.3 times faster than the LDS-tiled vector kernel it replaced on every such product of a step: the
+  //  ten-latent-GP mean term 96 -> 42 us, its adjoint 122 -> 61, the LMC products 209 -> 114 and 255 -> 126, the warp
+  //  GPs' [M, 2] gradient 14.0 -> 12.6)
   if (cscale != nullptr && splitk != 1) return GPSA_EINVAL;  // the split-K reduce does not know the scale
-  if (mfma) {
-    if (!transA && !transB) GPSA_GEMMX_CASE(false, false);
-    else if (transA && !transB) GPSA_GEMMX_CASE(true, false);
-    else if (!transA && transB) GPSA_GEMMX_CASE(false, true);
-    else GPSA_GEMMX_CASE(true, true);
-  } else if (!transA && !transB) GPSA_GEMM_CASE(false, false);
-  else if (transA && !transB) GPSA_GEMM_CASE(true, false);
-  else if (!transA && transB) GPSA_GEMM_CASE(false, true);
-  else GPSA_GEMM_CASE(true, true);
-#undef GPSA_GEMM_CASE
+  if (!transA && !transB) GPSA_GEMMX_CASE(false, false);
+  else if (transA && !transB) GPSA_GEMMX_CASE(true, false);
+  else if (!transA && transB) GPSA_GEMMX_CASE(false, true);
+  else GPSA_GEMMX_CASE(true, true);
 #undef GPSA_GEMMX_CASE
   GPSA_LAUNCH_CHECK();
   if (splitk > 1) {
@@ -679,8 +553,7 @@ __global__ void __launch_bounds__(256, 3) thin_update_kernel(const float* __rest
 }
 
 static inline bool thin_update_ok(int M, int L, long long C) {
-  static const bool off = [] { const char* e = getenv("GPSA_THIN_UPDATE"); return e && e[0] == '0'; }();
-  return !off && M >= 1 && M <= 256 && L >= 1 && L <= 64 && C >= 4096 && C % 4 == 0;
+  return M >= 1 && M <= 256 && L >= 1 && L <= 64 && C >= 4096 && C % 4 == 0;
 }
 
 }  // namespace gpsa

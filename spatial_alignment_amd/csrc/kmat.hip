@@ -91,11 +91,10 @@ constexpr int KB_D2_ROWS = 16;  // (24 rows per workgroup spill: 300 us)
 static inline int kmat_bwd_d2_rows() { return KB_D2_ROWS; }
 static inline bool kmat_bwd_d2(int M, long long Ctot, int D) {
   // (every size measured is faster this way: 117 -> 70 us at C = 100k, 41 -> 25 at 20k, 28 -> 19 at 12.5k,
-  //  15 -> 11 at 2.5k; M = 200.  GPSA_KMAT_BWD_D2=0: the older kernel)
-  static const bool off = [] { const char* e = getenv("GPSA_KMAT_BWD_D2"); return e && e[0] == '0'; }();
+  //  15 -> 11 at 2.5k; M = 200)
   (void)M;
   (void)Ctot;
-  return !off && D == 2;
+  return D == 2;
 }
 
 // grid (column blocks of 256, row chunks of KB_MCHUNK): one thread per column c, looping over the
@@ -444,7 +443,6 @@ int kmat_bwd_launch(int kind, const TI* Z, int M, const TX* X, long long C, int 
     // register-accumulating form (its own, finer row chunks: see kmat_bwd_d2_kernel)
     const int mr = kmat_bwd_d2_rows();
     const long long nby2 = cdiv(M, mr);
-    static const int per_env = [] { const char* e = getenv("GPSA_KMAT_BWD_PER"); return e ? atoi(e) : 0; }();
     // column blocks per workgroup: the fewest with which the whole grid is resident at once - two workgroups per CU
     // (launch bounds; ~200 registers).  Round 6, the exact data-GP backward at C = 100k (391 column blocks x 13 row
     // chunks): 8 blocks each = 637 workgroups ran as one full round and a quarter-full second one, 88 - 90 us; 10 (520
@@ -452,7 +450,6 @@ int kmat_bwd_launch(int kind, const TI* Z, int M, const TX* X, long long C, int 
     const long long slots = 2LL * num_cus();
     long long per = 1;
     while (per < ncb && cdiv(ncb, per) * nby2 * batch > slots) ++per;
-    if (per_env > 0) per = per_env;
     nbx = cdiv(ncb, per);
     const int rows = (int)cdiv(M, nby2);  // M spread evenly over the row chunks
     if ((nbx * nz + nby2 * nx + nbx * nby2 * 2) * (long long)sizeof(T) * batch > ws_bytes) return GPSA_EWORKSPACE;

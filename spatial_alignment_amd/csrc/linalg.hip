@@ -185,7 +185,7 @@ tri_inv_global_kernel(const double* __restrict__ L, double* __restrict__ Linv, i
 // Fused factorisation: Linv = chol(A)^-1, logdet, info in ONE pass with the matrix held in registers.
 // TS x TS threads own the lower triangle 2-D cyclically: thread (ty, tx) holds t[qa][qb] = element
 // (TS qa + ty, TS qb + tx), qb <= qa.  TS = 16 (one wave per SIMD, up to 136 elements per thread) runs
-// the per-column bookkeeping once per SIMD instead of four times and is the faster shape up to M = 208; TS = 32 above (GPSA_CHOL_TS forces one).  Step j of the right-looking factorisation publishes column j
+// the per-column bookkeeping once per SIMD instead of four times and is the faster shape up to M = 208; TS = 32 above.  Step j of the right-looking factorisation publishes column j
 // (rows >= j) and, for the forward substitution that runs in the same sweep, row j of the inverse
 // (columns < j) through a double-buffered LDS vector: ONE barrier per column, no LDS read-modify-
 // write.  The register position (i,k) holds A(i,k) while k > j and X(i,k) = L^-1(i,k) once k <= j
@@ -497,7 +497,7 @@ static inline long long chol_blk_lds_bytes(int NT) {
 template <int NT>
 __global__ void __launch_bounds__(256)
 chol_inv_blk_kernel(const double* __restrict__ A, int M, double* __restrict__ Linv,
-                    double* __restrict__ logdet, int* __restrict__ info, int skip, int n0, int gap) {
+                    double* __restrict__ logdet, int* __restrict__ info, int n0, int gap) {
   constexpr int MP = NT * 16;
   const int bx = (int)blockIdx.x < n0 ? (int)blockIdx.x : (int)blockIdx.x + gap;  // (chol_inv_reg_kernel: n0 / gap)
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -536,20 +536,18 @@ chol_inv_blk_kernel(const double* __restrict__ A, int M, double* __restrict__ Li
     for (int qb = 0; qb < q0; ++qb) Tb[ty * MP + 16 * qb + tx] = t[q0][qb];
     __syncthreads();
     // (2) diagonal block, every wave for itself
-    if (!(skip & 1))
-      bad = chol16_wave_ldl((const lds_f64*)Lp, (lds_f64*)(Ldw + w * 256), (lds_f64*)(dinvw + w * 16),
-                            (lds_f64*)(colw + w * 256), i0);
+    bad = chol16_wave_ldl((const lds_f64*)Lp, (lds_f64*)(Ldw + w * 256), (lds_f64*)(dinvw + w * 16),
+                          (lds_f64*)(colw + w * 256), i0);
     if (tid < 16) sdiag[i0 + tid] = dinvw[tid];  // wave 0's copy (written by its lane 0 above; same wave)
     if (bad) break;  // uniform: every wave factorised the same block
     // (3) panel rows and X columns, one thread each
-    if (!(skip & 2))
-      panel_solves_col((lds_f64*)Lp, R, (const lds_f64*)(Ldw + w * 256), (const lds_f64*)(dinvw + w * 16),
-                       (const lds_f64*)Tb, MP, (lds_f64*)XpT, i0);
+    panel_solves_col((lds_f64*)Lp, R, (const lds_f64*)(Ldw + w * 256), (const lds_f64*)(dinvw + w * 16),
+                     (const lds_f64*)Tb, MP, (lds_f64*)XpT, i0);
     __syncthreads();
     // (4) the row block of t is final; rank-16 update of the rows below
 #pragma unroll
     for (int qb = 0; qb <= q0; ++qb) t[q0][qb] = XpT[(16 * qb + tx) * CB_LS + ty];
-    if (q0 + 1 < NT && !(skip & 4)) {
+    if (q0 + 1 < NT) {
 #pragma unroll
       for (int qa = q0 + 1; qa < NT; ++qa) t[qa][q0] = 0.0;  // L(i,J) left for LDS, X(i,J) accumulates from zero
 #pragma unroll 1
@@ -601,14 +599,12 @@ static int chol_inv_blk_launch_nt(const double* A, int M, double* Linv, double* 
       return GPSA_EUNSUPPORTED;
     attr_set = true;
   }
-  // timing-only experiments (results are then wrong): bit 0 skips the block factorisation, 1 the solves, 2 the update
-  static const int skip = [] { const char* e = getenv("GPSA_CHOL_SKIP"); return e ? atoi(e) : 0; }();
-  chol_inv_blk_kernel<NT><<<batch, 256, (size_t)lds, st>>>(A, M, Linv, logdet, info, skip, n0, gap);
+  chol_inv_blk_kernel<NT><<<batch, 256, (size_t)lds, st>>>(A, M, Linv, logdet, info, n0, gap);
   GPSA_LAUNCH_CHECK();
   return 0;
 }
 
-// contiguous batch, M <= 208: the blocked kernel (GPSA_CHOL_BLOCKED=0 falls back to one barrier per column)
+// contiguous batch, M <= 208: the blocked kernel
 static int chol_inv_blk_launch(const double* A, int M, double* Linv, double* logdet, int* info, int batch,
                                hipStream_t st, int n0 = 0x7fffffff, int gap = 0) {
   const int nt = (M + 15) / 16;
@@ -660,8 +656,7 @@ static int chol_inv_reg_launch(const double* A, int M, double* Linv, double* log
                                                             col0, accumulate, n0, gap)
   // 16 x 16 threads (one wave per SIMD) while a thread's share fits comfortably in registers: 166 vs
   // 185 us at M = 200; 32 x 32 above (252 vs 287 us at M = 256)
-  static const int forced = [] { const char* e = getenv("GPSA_CHOL_TS"); return e ? atoi(e) : 0; }();
-  const int ts = forced ? forced : (M <= 208 ? 16 : 32);
+  const int ts = M <= 208 ? 16 : 32;
   if (ts == 32) {
     const int nt = (M + 31) / 32;
     if (nt <= 1) GPSA_CI_CASE(1, 32);
@@ -797,8 +792,7 @@ int gpsa_chol_inv_f64(const void* A, void* Linv, int M, int batch, void* logdet,
                       void* stream) {
   using namespace gpsa;
   if (M < 1 || batch < 1) return GPSA_EINVAL;
-  static const bool blocked = [] { const char* e = getenv("GPSA_CHOL_BLOCKED"); return !(e && e[0] == '0'); }();
-  if (blocked && M <= 208) {
+  if (M <= 208) {
     int rc = chol_inv_blk_launch((const double*)A, M, (double*)Linv, (double*)logdet, info, batch, as_stream(stream));
     if (rc != GPSA_EUNSUPPORTED) return rc;
   }
@@ -816,8 +810,7 @@ int gpsa_chol_inv_sel_f64(const void* A, void* Linv, int M, int batch, int n_alw
   if (keep_hi < keep_lo) keep_hi = keep_lo;
   const int n = n_always + (keep_hi - keep_lo), gap = keep_lo - n_always;
   if (n == 0) return 0;
-  static const bool blocked = [] { const char* e = getenv("GPSA_CHOL_BLOCKED"); return !(e && e[0] == '0'); }();
-  if (blocked && M <= 208) {
+  if (M <= 208) {
     int rc = chol_inv_blk_launch((const double*)A, M, (double*)Linv, (double*)logdet, info, n, as_stream(stream),
                                  n_always, gap);
     if (rc != GPSA_EUNSUPPORTED) return rc;

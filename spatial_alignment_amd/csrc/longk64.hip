@@ -360,8 +360,7 @@ extern "C" {
 long long gpsa_longk_f64_workspace(int M, long long K, int nprob) {
   using namespace gpsa;
   const int MB = longk_mb_for(M);
-  static const bool off = [] { const char* e = getenv("GPSA_LONGK"); return e && e[0] == '0'; }();
-  if (off || MB == 0 || nprob < 1 || nprob > LK_MAXP || K < 512 || (K & 1)) return 0;
+  if (MB == 0 || nprob < 1 || nprob > LK_MAXP || K < 512 || (K & 1)) return 0;
   const int ns = longk_nsplit(K, nprob);
   if ((long long)ns * nprob < 48) return 0;  // too few workgroups to be worth a 512-thread launch
   return (long long)nprob * ns * MB * 16 * MB * 16 * 8;

@@ -36,8 +36,6 @@ struct ProjArgs {
   long long C, sX;
   long long U;        // units = batch * T * MB
   int M, T;           // T = column tiles of 64 per problem
-  int dbg;            // timing experiments (GPSA_PROJ64_SKIP; results are then wrong): 1 no stores, 2 one slab load per
-                      // workgroup, 4 no LDS-DMA after the first stage, 8 no barrier / vmcnt wait
   // GEN (round 6): the right-hand side is not read but FORMED - K_uf[m, c] = k(Z_m, x_c) as the wave loads its 16
   // columns: the covariance launch in front (kmat_fwd: C M doubles written, then read back here) disappears
   const float* gZ;    // [M][gD] inducing points (fp32 parameters)
@@ -144,16 +142,16 @@ __global__ void __launch_bounds__(256, OCC) proj64_kernel(ProjArgs a) {
   float* o32b = nullptr;
   int slot = 0;
   for (long long u = u0; u < u1; ++u) {
-    if (!(a.dbg & 8)) __syncthreads();  // stage u has landed (everyone waited for its own pieces); stage u - 1 has been read by all
+    __syncthreads();  // stage u has landed (everyone waited for its own pieces); stage u - 1 has been read by all
     {
       int nrt = rt + 1, nb = b;
       if (nrt == MB) {
         nrt = 0;
         if (t + 1 == a.T) nb = b + 1;
       }
-      if (u + 1 < u1 && !(a.dbg & 4)) GPSA_PJ_STAGE(nrt, nb, slot ^ 1)
+      if (u + 1 < u1) GPSA_PJ_STAGE(nrt, nb, slot ^ 1)
     }
-    if (u == u0 || (rt == 0 && !(a.dbg & 2))) {  // a new column tile: its columns of the right-hand side
+    if (u == u0 || rt == 0) {  // a new column tile: its columns of the right-hand side
       c = (long long)t * 64 + w * 16 + j;
       okc = c < C;
       Xb = reinterpret_cast<const TI*>(a.X) + (long long)b * a.sX;
@@ -242,9 +240,9 @@ __global__ void __launch_bounds__(256, OCC) proj64_kernel(ProjArgs a) {
     // everything older than this point has been in flight for a whole stage: the next stage's pieces have landed
     // (the barrier at the top publishes them), the previous stage's stores are out
     __builtin_amdgcn_sched_barrier(0);
-    if (!(a.dbg & 8)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if (!(a.dbg & 1)) {
+    {
       const int row0 = 16 * rt + kq;
       const long long o = (long long)row0 * C + c;
 #pragma unroll
@@ -280,26 +278,14 @@ __global__ void __launch_bounds__(256, OCC) proj64_kernel(ProjArgs a) {
 #undef GPSA_PJ_STAGE
 }
 
-static inline long long proj64_min_units() {
-  static const long long v = [] {
-    const char* e = getenv("GPSA_PROJ64_MIN_TILES");
-    return e ? atoll(e) : -1LL;
-  }();
-  return v;
-}
-
 // shapes the persistent kernel takes (everything else stays on whiten_mfma_kernel)
 bool proj64_ok(int MB, long long C, int batch) {
-  static const bool off = [] {
-    const char* e = getenv("GPSA_PROJ64");
-    return e && e[0] == '0';
-  }();
-  if (off || (MB != 13 && MB != 7)) return false;
+  if (MB != 13 && MB != 7) return false;
   // long panels only: at least two column tiles per workgroup of the full grid.  Below that a workgroup is one tile's
   // 13 dependent stages behind one memory latency and whiten_mfma_kernel's wider spread wins (C = 20 000: 64 vs 72 us,
   // C = 12 500: 41 vs 50; at C = 100 000 / 200 000: 231 -> 218 / 423 -> 410 isolated, 202 -> 192 and 179 -> 164 in the step)
   const long long tiles = (long long)batch * cdiv(C, 64);
-  const long long floor_t = proj64_min_units() >= 0 ? proj64_min_units() : 2LL * 3 * num_cus();
+  const long long floor_t = 2LL * 3 * num_cus();
   return tiles >= floor_t && C * 8 < (1LL << 40);
 }
 
@@ -317,17 +303,11 @@ int proj64_launch(int MB, const double* Apk, const TI* X, int M, long long C, do
   a.M = M;
   a.T = (int)cdiv(C, 64);
   a.U = (long long)batch * a.T * MB;
-  static const int dbg = [] { const char* e = getenv("GPSA_PROJ64_SKIP"); return e ? atoi(e) : 0; }();
-  a.dbg = dbg;
   a.gZ = nullptr; a.gX = nullptr; a.g_ls = a.g_var = nullptr; a.gD = 0;
   // at least MB units per workgroup: a column tile (MB consecutive units) then meets at most two workgroups
   // workgroups per CU: three for the fp32 right-hand side (168 registers), two for the fp64 one (its three-per-CU
-  // instantiation spills five registers; measured equal: LAB_NOTES); GPSA_PROJ64_OCC = 1 / 2 / 3 forces one
-  static const int occ_env = [] {
-    const char* e = getenv("GPSA_PROJ64_OCC");
-    return e && (e[0] == '1' || e[0] == '2' || e[0] == '3') ? e[0] - '0' : 0;
-  }();
-  const int occ = occ_env ? occ_env : (sizeof(TI) == 8 ? 2 : 3);
+  // instantiation spills five registers; measured equal: LAB_NOTES)
+  constexpr int occ = sizeof(TI) == 8 ? 2 : 3;
   long long grid = (long long)occ * num_cus();
   if (grid > (long long)batch * a.T) grid = (long long)batch * a.T;
   if (q != nullptr && !q_zeroed) {
@@ -335,15 +315,8 @@ int proj64_launch(int MB, const double* Apk, const TI* X, int M, long long C, do
     if (e != 0) return e;
   }
   switch (MB) {
-    case 13:
-      if (occ == 1) proj64_kernel<13, TI, 1><<<(unsigned)grid, 256, 0, st>>>(a);
-      else if (occ == 2) proj64_kernel<13, TI, 2><<<(unsigned)grid, 256, 0, st>>>(a);
-      else proj64_kernel<13, TI, 3><<<(unsigned)grid, 256, 0, st>>>(a);
-      break;
-    case 7:
-      if (occ == 2) proj64_kernel<7, TI, 2><<<(unsigned)grid, 256, 0, st>>>(a);
-      else proj64_kernel<7, TI, 3><<<(unsigned)grid, 256, 0, st>>>(a);
-      break;
+    case 13: proj64_kernel<13, TI, occ><<<(unsigned)grid, 256, 0, st>>>(a); break;
+    case 7: proj64_kernel<7, TI, occ><<<(unsigned)grid, 256, 0, st>>>(a); break;
     default: return GPSA_EUNSUPPORTED;
   }
   GPSA_LAUNCH_CHECK();
@@ -366,7 +339,6 @@ int proj64_gen_launch(int MB, const double* Apk, int kind, const float* Z, const
   a.M = M;
   a.T = (int)cdiv(C, 64);
   a.U = (long long)a.T * MB;
-  a.dbg = 0;
   a.gZ = Z;
   a.gX = X64;
   a.g_ls = ls_u;

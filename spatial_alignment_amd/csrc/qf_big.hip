@@ -8,14 +8,12 @@ namespace gpsa {
 // KiB of piece P_ (0 .. 15) inside a ring slot of the 128 x 128 kernels: wave-major, see gram_big_kernel's stage
 #define GPSA_BIG_POS(P_) ((((P_) & 3) << 2) + ((P_) >> 2))
 
-// PAIR (round 6, the lever the round-5 counters pointed at): ONE wait + barrier per TWO 16-column chunks.  Four
-// one-chunk slots (64 KB a workgroup: two workgroups still share a CU); iteration k multiplies the chunks 2k, 2k + 1 out
-// of the slots (2k, 2k + 1) mod 4 while the stages of the chunks 2k + 2, 2k + 3 - requested at the top of the iteration
-// into the slots the barrier that ended iteration k - 1 released - are in flight; the iteration ends on vmcnt(0) + barrier.
-// GPSA_BIG_PAIR=1 selects it (A/B: profiles/r06_big_pair_ab.txt).
-template <bool PAIR>
+// (A variant with ONE wait + barrier per TWO 16-column chunks - four one-chunk slots, 64 KB a workgroup - was built in
+// round 6 behind a switch since removed and refuted: profiles/r06_big_pair_ab.txt.)
+// NSLOT: ring slots of one 16-column chunk each (3: two stages in flight)
+template <int NSLOT>
 __global__ void __launch_bounds__(256, 2) gram_big_kernel_t(GramBigArgs a) {
-  constexpr int NSLOT = PAIR ? 4 : 3;
+  static_assert(NSLOT == 3, "the ring walk below counts modulo 3");
   __shared__ __attribute__((aligned(16))) float lds[NSLOT][16 * 256];
   __shared__ __attribute__((aligned(16))) float sg[NSLOT][16];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -50,7 +48,6 @@ __global__ void __launch_bounds__(256, 2) gram_big_kernel_t(GramBigArgs a) {
   const long long nch = (C + 15) / 16;
   const long long ch0 = (long long)sp * nch / a.nsplit, ch1 = (long long)(sp + 1) * nch / a.nsplit;
   const float* gl = a.g + (long long)l * a.Cpad;
-  big_phase_prologue(a.phase);
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -111,40 +108,20 @@ __global__ void __launch_bounds__(256, 2) gram_big_kernel_t(GramBigArgs a) {
     GPSA_GB_MMA(z)                                                                            \
     GPSA_GB_MMA(w)                                                                            \
   }
-  if (PAIR) {
-    if (ch0 < ch1) {
-      GPSA_GB_STAGE(ch0, 0)
-      GPSA_GB_STAGE(ch0 + 1 < ch1 ? ch0 + 1 : ch0, 1)
-    }
-    GPSA_DMA_WAIT(0);
-    __syncthreads();
-    int buf = 0;  // 0 or 2: the pair's first slot
-    for (long long ch = ch0; ch < ch1; ch += 2) {
-      const int nb = buf ^ 2;
-      GPSA_GB_STAGE(ch + 2 < ch1 ? ch + 2 : ch1 - 1, nb)
-      GPSA_GB_STAGE(ch + 3 < ch1 ? ch + 3 : ch1 - 1, nb + 1)
-      GPSA_GB_CHUNK(buf)
-      if (ch + 1 < ch1) GPSA_GB_CHUNK(buf + 1)
-      GPSA_DMA_WAIT(0);
-      __syncthreads();
-      buf = nb;
-    }
-  } else {
-    if (ch0 < ch1) {
-      GPSA_GB_STAGE(ch0, 0)
-      GPSA_GB_STAGE(ch0 + 1 < ch1 ? ch0 + 1 : ch0, 1)
-    }
+  if (ch0 < ch1) {
+    GPSA_GB_STAGE(ch0, 0)
+    GPSA_GB_STAGE(ch0 + 1 < ch1 ? ch0 + 1 : ch0, 1)
+  }
+  GPSA_DMA_WAIT(5);
+  __syncthreads();
+  int buf = 0;
+  for (long long ch = ch0; ch < ch1; ++ch) {
+    // slot (buf + 2) % 3 held chunk ch - 1: everyone left it before the barrier that ended that iteration
+    GPSA_GB_STAGE(ch + 2 < ch1 ? ch + 2 : ch1 - 1, buf == 0 ? 2 : buf - 1)
+    GPSA_GB_CHUNK(buf)
     GPSA_DMA_WAIT(5);
     __syncthreads();
-    int buf = 0;
-    for (long long ch = ch0; ch < ch1; ++ch) {
-      // slot (buf + 2) % 3 held chunk ch - 1: everyone left it before the barrier that ended that iteration
-      GPSA_GB_STAGE(ch + 2 < ch1 ? ch + 2 : ch1 - 1, buf == 0 ? 2 : buf - 1)
-      GPSA_GB_CHUNK(buf)
-      GPSA_DMA_WAIT(5);
-      __syncthreads();
-      buf = (buf == 2) ? 0 : buf + 1;
-    }
+    buf = (buf == 2) ? 0 : buf + 1;
   }
 #undef GPSA_GB_CHUNK
 #undef GPSA_GB_MMA
@@ -161,12 +138,9 @@ __global__ void __launch_bounds__(256, 2) gram_big_kernel_t(GramBigArgs a) {
         if (row < M && col < M) P[(long long)row * M + col] = acc[i][k][r];
       }
 }
-template __global__ void gram_big_kernel_t<false>(GramBigArgs);
-template __global__ void gram_big_kernel_t<true>(GramBigArgs);
+template __global__ void gram_big_kernel_t<3>(GramBigArgs);
 void gram_big_launch(dim3 grid, hipStream_t st, const GramBigArgs& a) {
-  static const bool pair = [] { const char* e = getenv("GPSA_BIG_PAIR"); return e && e[0] == '1'; }();
-  if (pair) gram_big_kernel_t<true><<<grid, 256, 0, st>>>(a);
-  else gram_big_kernel_t<false><<<grid, 256, 0, st>>>(a);
+  gram_big_kernel_t<3><<<grid, 256, 0, st>>>(a);
 }
 
 // The large-M full product W[l] = P[l] X  ([M,M] x [M,C], fp32 matrix cores) with both operands staged by LDS-DMA
@@ -337,7 +311,6 @@ __global__ void __launch_bounds__(256, 2) big_quad_kernel(BigQuadArgs a) {
   const long long c0 = ctile * 128;
   const float* Pl = a.P + (long long)l * M * Mp;
   const int nch = Mp / 16, nrb = (M + 127) / 128;
-  big_phase_prologue(a.phase);
   f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -505,7 +478,6 @@ __global__ void __launch_bounds__(256, 2) big_accum_kernel(BigAccumArgs a) {
   const long long c0 = ct * 128;
   const int l0 = (int)((long long)sp * a.L / a.nsplit), l1 = (int)((long long)(sp + 1) * a.L / a.nsplit);
   const int nch = Mp / 16;
-  big_phase_prologue(a.phase);
   f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -750,8 +722,7 @@ __global__ void __launch_bounds__(256, 4) omega_fwd_dma_kernel(OmegaDmaArgs a) {
 
 int omega_fwd_dma_launch(const float* A0, int n0, double* O0, const float* A1, int n1, double* O1, int M, double jitter,
                          hipStream_t st) {
-  static const bool off = [] { const char* e = getenv("GPSA_OMEGA_DMA"); return e && e[0] == '0'; }();
-  if (off || (M & 3) != 0 || M < 16 || (reinterpret_cast<uintptr_t>(A0) & 15) != 0 ||
+  if ((M & 3) != 0 || M < 16 || (reinterpret_cast<uintptr_t>(A0) & 15) != 0 ||
       (n1 > 0 && (reinterpret_cast<uintptr_t>(A1) & 15) != 0) || n0 + n1 > 65535)
     return GPSA_EUNSUPPORTED;
   const int nb = (int)cdiv(M, 64);
@@ -874,9 +845,8 @@ __global__ void __launch_bounds__(256, 4) omega_bwd_dma_kernel(OmegaBwdArgs a) {
 
 int omega_bwd_dma_launch(const double* G0, const float* A0, float* D0, int n0, const double* G1, const float* A1,
                          float* D1, int n1, int M, hipStream_t st) {
-  static const bool off = [] { const char* e = getenv("GPSA_OMEGA_DMA"); return e && e[0] == '0'; }();
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (off || (M & 3) != 0 || M < 16 || !al(G0) || !al(A0) || !al(D0) || (n1 > 0 && (!al(G1) || !al(A1) || !al(D1))) ||
+  if ((M & 3) != 0 || M < 16 || !al(G0) || !al(A0) || !al(D0) || (n1 > 0 && (!al(G1) || !al(A1) || !al(D1))) ||
       n0 + n1 > 65535)
     return GPSA_EUNSUPPORTED;
   const unsigned nb = (unsigned)cdiv(M, 64);

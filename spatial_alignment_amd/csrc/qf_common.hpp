@@ -202,11 +202,10 @@ struct GramBigArgs {
   long long C, Cpad;
   int lb;  // > 0: 1-D grid, workgroups that share an XCD (ids equal mod 8) come in runs of ``lb`` outputs of ONE
            // (block pair, column split): they read the same rows of alpha at about the same time, from that XCD's L2
-  int phase = 0;  // experiment knob (big_phase()): see big_phase_prologue
 };
 __global__ void pad_rows_kernel(const float* __restrict__ g, int L, long long C, long long Cpad,
                                 float* __restrict__ gpad);
-void gram_big_launch(dim3 grid, hipStream_t st, const GramBigArgs& a);  // qf_big.hip (GPSA_BIG_PAIR: the A/B)
+void gram_big_launch(dim3 grid, hipStream_t st, const GramBigArgs& a);  // qf_big.hip
 // W[l] = P[l] X for large M (see prod_big_kernel)
 struct ProdBigArgs {
   const float* P;  // [L][M][Mp], zero for k >= M (Mp = a multiple of 16)
@@ -218,40 +217,11 @@ struct ProdBigArgs {
 __global__ void __launch_bounds__(256, 2) prod_big_kernel(ProdBigArgs a);
 template <typename TO>
 __global__ void __launch_bounds__(256) gram_big_reduce_kernel(const float* __restrict__ part, int M, int nsplit, TO* __restrict__ out);
-// outputs per run of same-XCD workgroups in the large-M kernels (GPSA_BIG_LB; 0 = the plain 3-D / 2-D grids)
-// The in-phase experiment on the two-workgroups-per-CU kernels (round-4 verdict item 7 (i)): the wave that sits in
-// an ODD wave slot of its SIMD (HW_ID.wave_id: the second of the two co-resident workgroups) can be started late
-// (GPSA_BIG_PHASE = n: n x 256 cycles of s_sleep, half a 64-MFMA chunk = 4) and / or raised to s_setprio 1 for its
-// whole life (GPSA_BIG_PRIO = 1; MI355X_MICROARCH.md "Two waves per SIMD" item 4).  Default 0 / 0: measured, no gain
-// (docs/LAB_NOTES.md, round 5).
-static inline int big_phase() {
-  static const int v = [] {
-    const char* e = getenv("GPSA_BIG_PHASE");
-    const char* q = getenv("GPSA_BIG_PRIO");
-    int r = e ? atoi(e) & 0xff : 0;
-    if (q && q[0] == '1') r |= 0x100;
-    return r;
-  }();
-  return v;
-}
-#if defined(__HIPCC__)
-__device__ __forceinline__ void big_phase_prologue(int phase) {
-  if (phase == 0) return;
-  const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | 4);  // HW_REG_HW_ID bits [3:0]: the SIMD's wave slot
-  if (slot & 1) {
-    if (phase & 0x100) __builtin_amdgcn_s_setprio(1);
-    for (int i = 0; i < (phase & 0xff); ++i) __builtin_amdgcn_s_sleep(4);
-  }
-}
-#endif
-static inline int big_remap_lb() {
-  static const int v = [] { const char* e = getenv("GPSA_BIG_LB"); return e ? atoi(e) : 16; }();
-  return v;
-}
-static inline bool gram_big_off() {
-  static const bool v = [] { const char* e = getenv("GPSA_GRAM_BIG"); return e && e[0] == '0'; }();
-  return v;
-}
+// outputs per run of same-XCD workgroups in the large-M kernels
+// (An in-phase experiment on the two-workgroups-per-CU kernels - round-4 verdict item 7 (i): start the wave in an odd
+// wave slot of its SIMD late and / or at raised priority - was measured in round 5 behind switches since removed: no
+// gain, docs/LAB_NOTES.md.)
+static inline int big_remap_lb() { return 16; }
 
 struct BigQuadArgs {
   const float* P;  // [L][M][Mp]  (TRI: U_l, else Omega_l), zero for k >= M
@@ -262,7 +232,6 @@ struct BigQuadArgs {
   long long C;
   int lb;  // > 0: 1-D grid; same-XCD workgroups come in runs of ``lb`` outputs of ONE column tile (they share its
            // alpha tile in that XCD's L2; each U_l / Omega_l is then shared by the few column tiles the XCD works on)
-  int phase = 0;
 };
 
 struct BigAccumArgs {
@@ -273,21 +242,17 @@ struct BigAccumArgs {
   int M, Mp, L, nrb, nsplit;
   long long C, ctiles;
   float scale;
-  int phase = 0;
 };
 
 __global__ void __launch_bounds__(256) big_accum_reduce_kernel(const float* __restrict__ part, int nsplit, long long n4, float* __restrict__ out);
 // shapes the two kernels cover (everything else stays on the generic tiled product)
 static inline bool big_panel_ok(int M, long long C, int L, const void* alpha) {
-  static const bool off = [] { const char* e = getenv("GPSA_BIG_PANEL"); return e && e[0] == '0'; }();
-  return !off && M > 128 && (C & 3) == 0 && C >= 128 && cdiv(C, 128) * cdiv(M, 128) * 32 < 0x7fffffffLL && L <= 65535 &&
+  return M > 128 && (C & 3) == 0 && C >= 128 && cdiv(C, 128) * cdiv(M, 128) * 32 < 0x7fffffffLL && L <= 65535 &&
          (reinterpret_cast<uintptr_t>(alpha) & 15) == 0;
 }
 // splits of the outputs for big_accum_kernel: the fewest (<= 4) that fill the rounds of workgroups (2 per CU) to
 // >= 90 %, else the fullest
 static inline int big_accum_nsplit(int M, long long C, int L) {
-  static const int forced = [] { const char* e = getenv("GPSA_BA_NSPLIT"); return e ? atoi(e) : 0; }();
-  if (forced > 0) return (forced <= L) ? forced : 1;
   const long long wgs = cdiv(M, 128) * cdiv(C, 128), slots = 2LL * num_cus();
   int best = 1;
   double beff = 0.0;

@@ -332,8 +332,7 @@ int generic_quadform_bwd_alpha(const T* alpha, const T* Omega, const T* g, int M
 static inline int gram_splitk(long long C, int M) {
   // enough K-splits that a single M x M product still fills the chip (tiles of 64 x 64)
   const long long tiles = cdiv(M, 64) * cdiv(M, 64);
-  static const long long target = [] { const char* e = getenv("GPSA_GRAM_SK_TARGET"); return e ? atoll(e) : 512LL; }();
-  long long s = cdiv(target, tiles);
+  long long s = cdiv(512LL, tiles);
   const long long cap = C / 256 > 1 ? C / 256 : 1;
   if (s > cap) s = cap;
   if (s > 256) s = 256;
@@ -358,15 +357,15 @@ int generic_quadform_bwd_omega(const T* alpha, const T* g, int M, long long C, i
     if (ns < 1) ns = 1;
     const long long Cpad = nch * 16, part_b = (long long)L * ns * M * M * 4;
     const long long need = part_b + (long long)L * Cpad * 4;
-    if (!gram_big_off() && (C & 3) == 0 && C >= 16 && (reinterpret_cast<uintptr_t>(alpha) & 15) == 0 && need <= ws_bytes &&
+    if ((C & 3) == 0 && C >= 16 && (reinterpret_cast<uintptr_t>(alpha) & 15) == 0 && need <= ws_bytes &&
         L <= 65535) {
       float* gpad = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + part_b);
       pad_rows_kernel<<<(unsigned)cdiv((long long)L * Cpad, 256), 256, 0, st>>>(g, L, C, Cpad, gpad);
       GPSA_LAUNCH_CHECK();
-      GramBigArgs a{alpha, gpad, reinterpret_cast<float*>(ws), M, L, (int)ns, nblk, C, Cpad, 0, big_phase()};
+      GramBigArgs a{alpha, gpad, reinterpret_cast<float*>(ws), M, L, (int)ns, nblk, C, Cpad, 0};
       const int lb = big_remap_lb();
-      const long long combos = (long long)pairs * ns * cdiv(L, lb > 0 ? lb : 1);
-      if (lb > 0 && 8 * lb * cdiv(combos, 8) < 0x7fffffffLL) {
+      const long long combos = (long long)pairs * ns * cdiv(L, lb);
+      if (8 * lb * cdiv(combos, 8) < 0x7fffffffLL) {
         a.lb = lb;
         gram_big_launch(dim3((unsigned)(8 * lb * cdiv(combos, 8))), st, a);
       } else {
@@ -700,8 +699,6 @@ static inline int gram_nsplit(long long C, int L) {
   // fewer prologues, and a third of the partial sums for gram_reduce_kernel to add
   const long long nch = cdiv(C, GR_KC);
   const int cus = num_cus();
-  static const int forced = [] { const char* e = getenv("GPSA_GRAM_NSPLIT"); return e ? atoi(e) : 0; }();
-  if (forced > 0) return (int)(forced < nch ? forced : nch);
   // W workgroups per output group fill the chip once; each takes c = ceil(nch / W) chunks.  (Few outputs -
   // the warp GPs' L = 2 - used to be held to >= 4 chunks per workgroup, i.e. 39 workgroups on 256 CUs at
   // C = 10k: 75 us; one chunk each, 157 workgroups: 44 us including the larger reduce.)
@@ -729,9 +726,7 @@ static inline long long gram_gpad_floats(long long C, int L) { return (long long
 // the column range is long enough for the saved staging to outweigh the doubled number of partial slabs
 // the reduce kernel adds (2.05 vs 2.28 ms at C = 100k, 0.28 vs 0.30 ms at C = 12.5k; L = 50)
 static inline int gram_nl(int MB, int L, long long C) {
-  static const int forced = [] { const char* e = getenv("GPSA_GRAM_NL"); return e ? atoi(e) : 0; }();
   const bool can = L >= 2 && MB <= 13;
-  if (forced == 1 || forced == 2) return (forced == 2 && can) ? 2 : 1;
   return (can && C >= 8192) ? 2 : 1;
 }
 
@@ -881,8 +876,7 @@ __global__ void __launch_bounds__(256) unpad_cols_kernel(const float* __restrict
   dst[i] = src[r * Cp + c];
 }
 static inline bool big_wants_pad(int M, long long C) {
-  static const bool off = [] { const char* e = getenv("GPSA_BIG_PANEL"); return e && e[0] == '0'; }();
-  return !off && M > 256 && C >= 128 && (C & 3) != 0;
+  return M > 256 && C >= 128 && (C & 3) != 0;
 }
 static inline long long pad4(long long C) { return (C + 3) & ~3LL; }
 // carve ``floats`` (rounded to 64) off the END of a workspace; nullptr when it does not fit
@@ -910,7 +904,7 @@ static int big_accum_launch(int omega_dtype, const float* alpha, const void* Ome
     pad_k_kernel<float><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((const float*)Omega, M, Mp, L, Pp);
   GPSA_LAUNCH_CHECK();
   const long long ctiles = cdiv(C, 128), ct8 = cdiv(ctiles, 8);
-  BigAccumArgs aa{Pp, alpha, g, part, M, Mp, L, nrb, ns, C, ctiles, 2.f, big_phase()};
+  BigAccumArgs aa{Pp, alpha, g, part, M, Mp, L, nrb, ns, C, ctiles, 2.f};
   // (measured, no faster: 3 workgroups per CU; a 4-slot ring with three stages in flight)
   big_accum_kernel<3><<<(unsigned)(8 * nrb * ct8 * ns), 256, 0, st>>>(aa);
   GPSA_LAUNCH_CHECK();
@@ -963,16 +957,11 @@ int gpsa_quadform_fwd(int dtype, int omega_dtype, const void* alpha, const void*
     if (MB && MB <= MB_MAX_QUAD && !force_generic()) {
       if (workspace_bytes < (long long)L * MB * 16 * MB * 16 * 4) return GPSA_EWORKSPACE;
       float* Ppk = (float*)workspace;
-      static const bool full_env = [] { const char* e = getenv("GPSA_QUAD_FULL"); return e && e[0] == '1'; }();
-      const bool full = full_env && MB <= 16;  // (the full-product kernel holds M <= 256)
       // (the last chunk goes in K-step order exactly when quad_sym_launch picks the step-skipping kernel)
       const int sym = PACK_SYM_UPPER | ((M - 16 * (MB - 1) <= 8) ? PACK_KSTEP_LAST : 0);
-      const int klast = (M - 16 * (MB - 1) <= 8) ? PACK_KSTEP_LAST : 0;  // matches panel_mfma_launch's RL choice
-      int rc = pack_any(omega_dtype, Omega, M, MB, L, 0, Ppk, st, full ? klast : sym);
+      int rc = pack_any(omega_dtype, Omega, M, MB, L, 0, Ppk, st, sym);
       if (rc) return rc;
-      if (!full) return quad_sym_launch(MB, Ppk, (const float*)alpha, M, C, L, (float*)v, st);
-      return panel_mfma_launch<MODE_QUAD>(MB, Ppk, (const float*)alpha, nullptr, M, C, L, (float*)v,
-                                          nullptr, 1.f, nullptr, st);
+      return quad_sym_launch(MB, Ppk, (const float*)alpha, M, C, L, (float*)v, st);
     }
     if (big_wants_pad(M, C)) {  // unaligned column count: the same kernels on zero-padded copies
       const long long Cp = pad4(C);
@@ -1000,10 +989,10 @@ int gpsa_quadform_fwd(int dtype, int omega_dtype, const void* alpha, const void*
         else
           pad_k_tri_kernel<float><<<(unsigned)cdiv(n, 256), 256, 0, st>>>((const float*)Omega, M, Mp, L, Pp);
         GPSA_LAUNCH_CHECK();
-        BigQuadArgs qa{Pp, (const float*)alpha, (float*)v, nullptr, M, Mp, L, C, 0, big_phase()};
+        BigQuadArgs qa{Pp, (const float*)alpha, (float*)v, nullptr, M, Mp, L, C, 0};
         const int lb = big_remap_lb();
-        const long long combos = cdiv(C, 128) * cdiv(L, lb > 0 ? lb : 1);
-        if (lb > 0 && 8 * lb * cdiv(combos, 8) < 0x7fffffffLL) {
+        const long long combos = cdiv(C, 128) * cdiv(L, lb);
+        if (8 * lb * cdiv(combos, 8) < 0x7fffffffLL) {
           qa.lb = lb;
           big_quad_kernel<true, false, 3><<<(unsigned)(8 * lb * cdiv(combos, 8)), 256, 0, st>>>(qa);
         } else {
@@ -1080,11 +1069,10 @@ int gpsa_quadform_fwd_keep_f32(int omega_dtype, const float* alpha, const void* 
   if (C > 0x7fffffffLL) return GPSA_EINVAL;
   {
     // the LDS-DMA product (16-byte aligned rows of alpha; zero-padded fp32 copy of Omega in the workspace)
-    static const bool off = [] { const char* e = getenv("GPSA_PROD_BIG"); return e && e[0] == '0'; }();
     const int Mp = (M + 15) / 16 * 16;
     const long long need = (long long)L * M * Mp * 4;
     const long long ctiles = cdiv(C, 128);
-    if (!off && (C & 3) == 0 && C >= 16 && (reinterpret_cast<uintptr_t>(alpha) & 15) == 0 &&
+    if ((C & 3) == 0 && C >= 16 && (reinterpret_cast<uintptr_t>(alpha) & 15) == 0 &&
         (reinterpret_cast<uintptr_t>(W) & 15) == 0 && need <= workspace_bytes && L <= 65535 && ctiles <= 65535) {
       float* Pp = (float*)workspace;
       const long long n = (long long)L * M * Mp;
@@ -1095,12 +1083,11 @@ int gpsa_quadform_fwd_keep_f32(int omega_dtype, const float* alpha, const void* 
       else
         return GPSA_EINVAL;
       GPSA_LAUNCH_CHECK();
-      static const bool old_pb = [] { const char* e = getenv("GPSA_PROD_BIG"); return e && e[0] == '1'; }();
-      if (!old_pb && big_panel_ok(M, C, L, alpha)) {  // product, kept copy and the closing column sums in one kernel
-        BigQuadArgs qa{Pp, alpha, v, W, M, Mp, L, C, 0, big_phase()};
+      if (big_panel_ok(M, C, L, alpha)) {  // product, kept copy and the closing column sums in one kernel
+        BigQuadArgs qa{Pp, alpha, v, W, M, Mp, L, C, 0};
         const int lb = big_remap_lb();
-        const long long combos = ctiles * cdiv(L, lb > 0 ? lb : 1);
-        if (lb > 0 && 8 * lb * cdiv(combos, 8) < 0x7fffffffLL) {
+        const long long combos = ctiles * cdiv(L, lb);
+        if (8 * lb * cdiv(combos, 8) < 0x7fffffffLL) {
           qa.lb = lb;
           big_quad_kernel<false, true, 3><<<(unsigned)(8 * lb * cdiv(combos, 8)), 256, 0, st>>>(qa);
         } else {
@@ -1161,8 +1148,7 @@ long long gpsa_quadform_elbo_f32_workspace(int M, long long C, int L) {
 // the mean can ride in the product's first padding row (gpsa_quadform_elbo_delta_f32) when row M lies in the LAST row tile
 static inline bool elbo_delta_ok(int M) {
   const int MB = gpsa::mfma_mb_for(M);
-  static const bool off = [] { const char* e = getenv("GPSA_ELBO_DELTA"); return e && e[0] == '0'; }();
-  return !off && elbo_path(M) && M > 16 * (MB - 1) && M < 16 * MB;
+  return elbo_path(M) && M > 16 * (MB - 1) && M < 16 * MB;
 }
 
 int gpsa_quadform_elbo_takes_delta(int M) { return M >= 1 && elbo_delta_ok(M) ? 1 : 0; }
@@ -1390,14 +1376,7 @@ int gpsa_quadform_bwd_alpha(int dtype, int omega_dtype, const void* alpha, const
         return 0;
       }
     }
-    // 256 < M <= 512: the register-resident kernel stays ahead of the LDS-DMA one (BASELINE config 4: 319 vs 342 ms);
-    // GPSA_ACCUM_PANEL=0 takes the LDS-DMA kernel there too (tests, A/B)
-    static const bool panel_off = [] { const char* e = getenv("GPSA_ACCUM_PANEL"); return e && e[0] == '0'; }();
-    if (MB > 16 && panel_off && !force_generic()) {
-      const int rc = big_accum_launch(omega_dtype, (const float*)alpha, Omega, (const float*)g, M, C, L, (float*)dalpha,
-                                      workspace, workspace_bytes, st);
-      if (rc != GPSA_EUNSUPPORTED) return rc;
-    }
+    // 256 < M <= 512: the register-resident kernel stays ahead of the LDS-DMA one (BASELINE config 4: 319 vs 342 ms)
     if (MB && MB <= MB_MAX_ACCUM && !force_generic()) {
       const long long pk = (long long)L * MB * 16 * MB * 16;
       if (workspace_bytes < (pk + accum_slab_floats(MB)) * 4) return GPSA_EWORKSPACE;
@@ -1497,9 +1476,8 @@ int gpsa_quadform_bwd_omega(int dtype, int out_dtype, const void* alpha, const v
 
 // the d-delta option of the Gram kernel: M in the last row tile with a padding row behind it, the MFMA path, 4-column alignment
 static inline bool gram_delta_ok(int M, long long C) {
-  static const bool off = [] { const char* e = getenv("GPSA_GRAM_DELTA"); return e && e[0] == '0'; }();
   const int MB = gpsa::gram_mb_for(M);
-  return !off && MB != 0 && !gpsa::force_generic() && M > 16 * (MB - 1) && M < 16 * MB && (C % 4 == 0) && C >= 8;
+  return MB != 0 && !gpsa::force_generic() && M > 16 * (MB - 1) && M < 16 * MB && (C % 4 == 0) && C >= 8;
 }
 
 int gpsa_quadform_bwd_omega_takes_delta(int M, long long C) { return M >= 1 && C >= 1 && gram_delta_ok(M, C) ? 1 : 0; }

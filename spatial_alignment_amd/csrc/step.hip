@@ -598,10 +598,6 @@ struct Plan {
   char* dev = nullptr;
   ViewTab tab;
   int* d_free = nullptr;
-  // side stream for the work only the KL terms need (factorising / inverting the variational covariances,
-  // the KL kernels and their backward): forked from and joined to the caller's stream inside every call
-  hipStream_t side = nullptr;
-  hipEvent_t sev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // optional HIP-event timing of the three contraction launches of the first data-GP pass (bench.py's
   // roofline figures): slot = step index modulo the ring, 2 events per kernel
   std::vector<hipEvent_t> tev;
@@ -671,8 +667,6 @@ static void free_plan(Plan* p) {
   if (p == nullptr) return;
   if (p->dev != nullptr) (void)hipFree(p->dev);
   for (hipEvent_t e : p->tev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : p->sev)
-    if (e != nullptr) (void)hipEventDestroy(e);
   if (!p->graphs.empty() || !p->retired.empty()) (void)hipDeviceSynchronize();  // nothing of theirs is in flight any more
   for (auto& ge : p->graphs)
     if (ge.exec != nullptr) (void)hipGraphExecDestroy(ge.exec);
@@ -681,7 +675,6 @@ static void free_plan(Plan* p) {
     (void)hipEventDestroy(r.ev);
   }
   if (p->gstream != nullptr) (void)hipStreamDestroy(p->gstream);
-  if (p->side != nullptr) (void)hipStreamDestroy(p->side);
   delete p;
 }
 
@@ -903,17 +896,6 @@ static Plan* make_plan(const gpsa_step_desc* dsc, bool host_only = false) {
   }
   if (!host_only && hipMemcpy(p->dev, host.data(), (size_t)bytes, hipMemcpyHostToDevice) != hipSuccess) { free_plan(p); return nullptr; }
   p->tab.V = V; p->tab.D = D; p->tab.S = S; p->tab.nm = nm; p->tab.nf = p->nf; p->tab.Cs = p->Cs;
-  {
-    // off by default: measured on MI355X (profiles/r02_*), the fork buys nothing - the side stream's kernels
-    // cannot co-reside with the persistent full-chip contraction kernels (one wave per SIMD holding the whole
-    // register file), and next to the latency-bound small kernels they only trade places
-    const char* e = getenv("GPSA_STEP_SIDE");
-    if (!host_only && (e && e[0] == '1') && dsc->want_kl) {
-      bool ok = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) == hipSuccess;
-      for (int i = 0; i < 5 && ok; ++i) ok = hipEventCreateWithFlags(&p->sev[i], hipEventDisableTiming) == hipSuccess;
-      if (!ok) { free_plan(p); return nullptr; }
-    }
-  }
   return p;
 }
 
@@ -939,8 +921,7 @@ static inline int splitk_small(long long k, int m, int n, int batch) {  // ops.H
 // the same rule for the handful of priors' products of the KL backward (0.5 K^-1 S K^-1: two dependent M x M x M
 // products, batch = the number of priors): 48 workgroups with a 13-step K loop each were 21.5 us apiece at M = 200
 static inline int splitk_few(long long k, int m, int n, int batch) {
-  static const bool on = [] { const char* e = getenv("GPSA_SPLITK_FEW"); return !(e && e[0] == '0'); }();
-  if (on && batch <= 4 && k >= 128 && k <= 1024 && cdiv(m, 64) * cdiv(n, 64) * batch <= 64) {
+  if (batch <= 4 && k >= 128 && k <= 1024 && cdiv(m, 64) * cdiv(n, 64) * batch <= 64) {
     int s = (int)(k / 48);
     return s > 4 ? 4 : (s < 1 ? 1 : s);
   }
@@ -1107,42 +1088,19 @@ static int mm_stage_fwd(Ctx& c) {
   for (int m = m_first; m < P.nm; ++m)
     GPSA_RUN(gpsa_omega_fwd(c.prm.Omega_sqt_F[m], Mg, P.d.n_latent[m], 1e-5, c.mats(GD, P.pos_OmF(m, 0)), c.stv()));
   // factorise: the priors always; the variational covariances only when the KL terms are wanted (the
-  // layers use Omega itself, never its factor) - and then on the side stream, next to the priors: neither
-  // the layers nor the warp GPs wait for them
-  const bool fork = kl && P.side != nullptr && !dry;
-  hipStream_t sst = fork ? P.side : c.st;
-  if (fork) {
-    GPSA_CK((int)hipEventRecord(P.sev[0], c.st));
-    GPSA_CK((int)hipStreamWaitEvent(P.side, P.sev[0], 0));
-  }
-  // buffers the side stream owns for the whole call (never handed back to the bump allocator before the join)
-  double* LinvO[2] = {nullptr, nullptr};
-  void* wsO[2] = {nullptr, nullptr};
-  long long wsOb[2] = {0, 0};
-  if (kl && P.side != nullptr)
-    for (int g = 0; g < P.ng; ++g) {
-      Group& G = P.grp[g];
-      if (G.n_omega == 0) continue;
-      LinvO[g] = c.sc.get<double>((long long)G.n_omega * G.M * G.M);
-      if (G.M > 256) {
-        wsOb[g] = gpsa_chol_inv_blocked_workspace(G.M, G.n_omega);
-        wsO[g] = c.sc.get<char>(wsOb[g]);
-      }
-      wsOb[g] += 0;
-    }
+  // layers use Omega itself, never its factor)
   for (int g = 0; g < P.ng; ++g) {
     Group& G = P.grp[g];
     const long long mm = (long long)G.M * G.M;
     double* logdet = c.sv<double>(G.o_logdet);
     int* info = c.sv<int>(G.o_info);
-    const bool split = kl && P.side != nullptr;  // priors on the caller's stream, the rest on the side stream
     const int np = G.n_prior, n_own = G.own_hi - G.own_lo;
     // owner computes: only the priors and this plan's own variational covariances (batch positions np + own_lo ..
     // np + own_hi) are factorised and inverted - in ONE launch all the same (a second one would cost a second matrix's
     // latency); the entries of the others in Linv / inv / logdet stay unwritten and nobody reads them (their terms are
     // listed as absent), their infos were zeroed by step_prep_kernel
-    const bool sel = kl && !split && !G.own_all();
-    const int nb_main = split ? np : (kl ? G.nb() : np);
+    const bool sel = kl && !G.own_all();
+    const int nb_main = kl ? G.nb() : np;
     // K^-1 = L^-T L^-1 for ``cnt`` matrices in one product
     // (the triangle mode contracts k >= max(i, j) only and mirrors; it needs split-K 1: a large batch)
     auto inverse_product = [&](const double* Lin, double* out, int cnt) -> int {
@@ -1186,20 +1144,6 @@ static int mm_stage_fwd(Ctx& c) {
       }
       c.sc.release(mk);
     }
-    if (split && n_own > 0) {
-      const int o0 = np + G.own_lo;
-      if (G.M > 256)
-        GPSA_RUN(gpsa_chol_inv_blocked_f64(c.mats(G, o0), LinvO[g], G.M, n_own, logdet + o0, info + o0, wsO[g],
-                                           wsOb[g], (void*)sst));
-      else
-        GPSA_RUN(gpsa_chol_inv_f64(c.mats(G, o0), LinvO[g], G.M, n_own, logdet + o0, info + o0, (void*)sst));
-      GPSA_RUN((gemm_launch_tri<double>(1, 0, G.M, G.M, G.M, 1.0, LinvO[g], G.M, mm, LinvO[g], G.M, mm, 0.0,
-                                        c.inv(G, o0), G.M, mm, n_own, 1, nullptr, 0, sst, GEMM_TRI_LTL)));
-    }
-  }
-  if (fork) {  // the KL kernels read the priors' inverses too
-    GPSA_CK((int)hipEventRecord(P.sev[1], c.st));
-    GPSA_CK((int)hipStreamWaitEvent(P.side, P.sev[1], 0));
   }
   if (kl)
     for (int g = 0; g < P.ng; ++g) {
@@ -1209,9 +1153,8 @@ static int mm_stage_fwd(Ctx& c) {
         GPSA_RUN(mvn_kl_grouped_fwd_copy(c.mats(G, 0), c.inv(G, 0), c.sv<double>(G.o_logdet), G.om_idx, G.pr_idx,
                                          c.sv<double>(G.o_D), G.M, G.n_omega, c.io.kl + G.kl_off,
                                          c.sv<double>(G.o_KD), c.sv<double>(P.o_klcache) + G.kl_off, klpart[g], klcnt[g],
-                                         sst));
+                                         c.st));
     }
-  if (fork) GPSA_CK((int)hipEventRecord(P.sev[2], P.side));
   return 0;
 }
 
@@ -1313,8 +1256,6 @@ static int warp_stage_fwd(Ctx& c) {
     boff += nb;
   }
   c.sc.release(mk);
-  // join the side stream (KL terms, factorisation infos of the variational covariances)
-  if (P.d.want_kl && P.side != nullptr && !dry) GPSA_CK((int)hipStreamWaitEvent(c.st, P.sev[2], 0));
   // one word for the host: Cholesky infos and variance flags
   if (c.io.flag != nullptr && !dry) {
     Group& G0 = P.grp[0];
@@ -1540,8 +1481,7 @@ static int data_pass_bwd(Ctx& c, const Pass& ps, int pass_idx, const float* dFl_
     void* ws = c.sc.get<char>(wsb);
     const bool timed = !dry && !c.quiet && &ps == &P.passes[0];
     if (timed) P.tick(1, 0, false, c.st);  // (slot 1: what is left of the alpha-gradient - the mean term's share)
-    static const int fold = [] { const char* e = getenv("GPSA_FOLD_FINISH"); return e ? atoi(e) : 3; }();
-    if (pass_idx < BWD_TICKS - 32 && (fold & 2))  // (a ticket per pass: the post kernel's last block closes dvar itself)
+    if (pass_idx < BWD_TICKS - 32)  // (a ticket per pass: the post kernel's last block closes dvar itself)
       GPSA_RUN(elbo_fused_post_ticket(g_ext, dmeanT, abar, Mg, C, L, gloss, c.prm.data_var, B.dvar_ds + pass_idx,
                                       (double*)ws, B.tick + 32 + pass_idx, c.st));
     else
@@ -1632,9 +1572,7 @@ static int data_pass_bwd(Ctx& c, const Pass& ps, int pass_idx, const float* dFl_
   // exact training pass: the covariance backward HERE, straight behind the C-long product that has just read the same
   // two fp64 panels (gamma, alpha: 320 MB at the headline size - what of them the memory-side cache still holds is
   // not fetched again; behind the Gram kernel, where it stood until round 6, nothing of them was left).
-  // GPSA_COV_BWD_EARLY=0: the old place
-  static const bool cov_early_on = [] { const char* e = getenv("GPSA_COV_BWD_EARLY"); return !(e && e[0] == '0'); }();
-  const bool cov_early = exact && !ps.test && cov_early_on;
+  const bool cov_early = exact && !ps.test;
   if (cov_early) {
     const long long mk2 = c.sc.mark();
     const long long wsb = gpsa_kmat_bwd_workspace(GPSA_F64, Mg, C, D);
@@ -1647,25 +1585,19 @@ static int data_pass_bwd(Ctx& c, const Pass& ps, int pass_idx, const float* dFl_
     c.sc.release(mk2);
   }
   // gamma = K^-1 abar (fp64 product on the fp32 panel).  With many columns dK_uu comes from the identity below
-  // and only dK_uf = gamma + 2 qbar a is needed: the column-scaled update rides in the solve's store
+  // and only dK_uf = gamma + 2 qbar a is needed: the column-scaled update rides in the covariance backward
   float* gamma = exact ? nullptr : c.sc.get<float>((long long)Mg * C);
   const bool identity = !exact && C >= 4LL * L * Mg;
-  bool fused_axpy = false, axpy_in_cov = false;
+  bool axpy_in_cov = false;
   if (!exact) {
     const long long wsb = gpsa_whiten_workspace(Mg);
     if (wsb > 0) {
       const long long mk2 = c.sc.mark();
       void* ws = c.sv<char>(P.o_apk_d);  // packed by the forward
-      // measured (bench.py A/B in one run, twice): the fused store makes the step 37 us SLOWER (8.939 vs 8.901
-      // ms): its row-strided reads of alpha in the projection kernel's epilogue cost more than the separate
-      // streaming pass saves.  Kept behind GPSA_FUSED_AXPY=1.
-      static const bool fuse = [] { const char* e = getenv("GPSA_FUSED_AXPY"); return e && e[0] == '1'; }();
-      if (identity && fuse) {
-        GPSA_RUN(gpsa_whiten_axpy_f32(nullptr, abar, Mg, C, alpha, qbar, 2.0, gamma, ws, wsb, c.stv()));
-        fused_axpy = true;
-      } else {
-        GPSA_RUN(gpsa_whiten_f64(nullptr, GPSA_F32, abar, Mg, C, GPSA_F32, gamma, nullptr, ws, wsb, c.stv()));
-      }
+      // (the column-scaled update is NOT fused into this solve's store - gpsa_whiten_axpy_f32: measured with bench.py,
+      // A/B in one run, twice, the fused store made the step 37 us SLOWER (8.939 vs 8.901 ms): its row-strided reads
+      // of alpha in the projection kernel's epilogue cost more than the separate streaming pass saves)
+      GPSA_RUN(gpsa_whiten_f64(nullptr, GPSA_F32, abar, Mg, C, GPSA_F32, gamma, nullptr, ws, wsb, c.stv()));
       c.sc.release(mk2);
     } else {
       GPSA_CK((gemmx<double, float, float>(c, 0, 0, Mg, (int)C, Mg, 1.0, Kinv, Mg, 0, abar, C, 0, 0.0, gamma, C, 0, 1, 1)));
@@ -1747,9 +1679,9 @@ static int data_pass_bwd(Ctx& c, const Pass& ps, int pass_idx, const float* dFl_
       }
       // dK_uf = gamma + 2 qbar a: formed inside the covariance backward as it reads the panel (no pass that
       // writes it out) - except for test passes, whose covariance backward is the plain entry point
-      if (!fused_axpy && ps.test)
+      if (ps.test)
         GPSA_RUN(gpsa_col_axpy(GPSA_F32, gamma, alpha, qbar, 2.0, Mg, C, gamma, c.stv()));
-      else if (!fused_axpy)
+      else
         axpy_in_cov = true;
     } else if (!exact) {
       // few columns: W = gamma + qbar a;  dK_uu = -W a^T ADDED in fp64;  dK_uf = W + qbar a
@@ -1810,8 +1742,7 @@ static int warp_stage_bwd(Ctx& c, const gpsa_step_out_grads& og, BwdBufs& B, boo
     const double* dG64[MAXMODS];
     for (int m = 0; m < MAXMODS; ++m) dG64[m] = (m < P.nm && B.have_dG[m]) ? B.dG64[m] : nullptr;
     dim3 grid((unsigned)nblk, (unsigned)nf);
-    static const int fold = [] { const char* e = getenv("GPSA_FOLD_FINISH"); return e ? atoi(e) : 3; }();
-    const bool closes = nf <= 32 && (fold & 1);  // (a ticket per free view)
+    const bool closes = nf <= 32;  // (a ticket per free view)
     warp_sample_views_bwd_kernel<<<grid, 256, 0, c.st>>>(P.tab, P.d_free, mod_ptrs(c, &og, dG64), c.io.eps_G, dmeanT,
                                                          g, qbar, part, closes ? B.tick : nullptr, c.prm.warp_var,
                                                          B.dvar_ws);
@@ -1928,23 +1859,9 @@ static int step_backward(Plan& P, const gpsa_step_params& prm, const gpsa_step_i
   BwdBufs B;
   memset(&B, 0, sizeof(B));
   const bool kl = P.d.want_kl != 0 && og.dkl != nullptr;
-  // a slice of a microbatched step that does not close (bwd_acc_mode 1 / 2) leaves before the KL terms are joined:
-  // it must not start them either (its KL share is zero, and an unjoined fork would still be writing into the
-  // scratch arena when the next slice reuses it - and stays unjoined under stream capture)
-  const bool closes = io.bwd_acc == nullptr || io.bwd_acc_mode == 0 || io.bwd_acc_mode == 3;
-  const bool fork = kl && P.side != nullptr && !dry && closes;
-  // the KL terms' backward runs on the side stream into buffers of its own (dKL: same layout as dstack)
-  double* dKL[2] = {nullptr, nullptr};
-  double* Skl[2] = {nullptr, nullptr};
-  double* Tkl[2] = {nullptr, nullptr};
   for (int g = 0; g < P.ng; ++g) {
     Group& G = P.grp[g];
     B.dD[g] = sc.get<double>((long long)G.n_omega * G.M);
-    if (kl && P.side != nullptr) {
-      dKL[g] = sc.get<double>((long long)G.nb() * G.M * G.M);
-      Skl[g] = sc.get<double>((long long)G.n_prior * G.M * G.M);
-      Tkl[g] = sc.get<double>((long long)G.n_prior * G.M * G.M);
-    }
   }
   // everything that must start at zero sits in ONE contiguous region: one fill
   const long long z0 = (sc.off + 255) & ~255LL;
@@ -1979,25 +1896,6 @@ static int step_backward(Plan& P, const gpsa_step_params& prm, const gpsa_step_i
     B.ddc_F[m] = sc.get<float>((long long)Mg * P.d.n_latent[m]);
     B.dG64[m] = sc.get<double>((long long)P.S * P.d.n_rows[m] * D);
   }
-  // ---- KL terms: dOmega, dK_p = 0.5 K_p^-1 S_p K_p^-1, dD   (side stream when there is one)
-  if (fork) {
-    GPSA_CK((int)hipEventRecord(P.sev[3], st));
-    GPSA_CK((int)hipStreamWaitEvent(P.side, P.sev[3], 0));
-  }
-  for (int g = 0; g < P.ng && kl && P.side != nullptr && closes; ++g) {
-    Group& G = P.grp[g];
-    if (G.n_omega == 0 || G.n_prior == 0) continue;
-    const long long mm = (long long)G.M * G.M;
-    hipStream_t sst = dry ? st : P.side;
-    GPSA_RUN(gpsa_mvn_kl_grouped_bwd_acc(c.mats(G, 0), c.inv(G, 0), G.om_idx, G.pr_list, G.grp_off, G.order,
-                                         c.sv<double>(G.o_D), c.sv<double>(G.o_KD), og.dkl + G.kl_off, G.M, G.n_omega,
-                                         G.n_prior, dKL[g] + (long long)G.n_prior * mm, B.dD[g], Skl[g], 0, (void*)sst));
-    GPSA_RUN((gemm_launch<double>(0, 0, G.M, G.M, G.M, 1.0, c.inv(G, 0), G.M, mm, Skl[g], G.M, mm, 0.0, Tkl[g], G.M, mm,
-                                  G.n_prior, 1, nullptr, 0, sst)));
-    GPSA_RUN((gemm_launch<double>(0, 0, G.M, G.M, G.M, 0.5, Tkl[g], G.M, mm, c.inv(G, 0), G.M, mm, 0.0, dKL[g], G.M, mm,
-                                  G.n_prior, 1, nullptr, 0, sst)));
-  }
-  if (fork) GPSA_CK((int)hipEventRecord(P.sev[4], P.side));
   // ---- data GP passes
   bool seen[MAXMODS] = {false, false, false, false};
   for (int pi = 0; pi < npass; ++pi) {
@@ -2016,7 +1914,7 @@ static int step_backward(Plan& P, const gpsa_step_params& prm, const gpsa_step_i
   //      dOmega -> dA and the finalisation of the data GP's parameters, the event, and only then the warp GPs' backward
   //      (its products ADDED to the KL shares already in the batch), the priors' backward and everything else.
   const bool early = io.f_event != nullptr && !dry && (io.bwd_acc == nullptr || io.bwd_acc_mode == 0) &&
-                     P.side == nullptr && warp_runs_longk(P);
+                     warp_runs_longk(P);
   if (!early) GPSA_CK(warp_stage_bwd(c, og, B, false));
   // ---- one optimiser step as several passes over row slices (train.Microbatches): everything N-scaled of this
   //      slice is in the region [z0, z1) (fp64 pieces, then the samplers' fp32 scalars) and in ddc_F.  A slice that is not
@@ -2072,18 +1970,8 @@ static int step_backward(Plan& P, const gpsa_step_params& prm, const gpsa_step_i
     if (io.bwd_acc_mode != 3) return 0;
   }
   auto kl_backward = [&]() -> int {
-  // ---- KL terms
-    if (kl && P.side != nullptr) {  // join: add the side stream's share (same layout as dstack) in one pass
-      if (fork) GPSA_CK((int)hipStreamWaitEvent(st, P.sev[4], 0));
-      for (int g = 0; g < P.ng; ++g) {
-        Group& G = P.grp[g];
-        if (G.n_omega == 0 || G.n_prior == 0 || dry) continue;
-        const long long n = (long long)G.nb() * G.M * G.M;
-        add_inplace_kernel<<<(unsigned)cdiv(n, 256), 256, 0, st>>>(B.dstack[g], dKL[g], n);
-        GPSA_LAUNCH_CHECK();
-      }
-    }
-    for (int g = 0; g < P.ng && kl && P.side == nullptr; ++g) {  // single stream: accumulate in place
+  // ---- KL terms: dOmega, dK_p = 0.5 K_p^-1 S_p K_p^-1, dD, accumulated in place
+    for (int g = 0; g < P.ng && kl; ++g) {
       Group& G = P.grp[g];
       if (G.n_omega == 0 || G.n_prior == 0) continue;
       const long long mm = (long long)G.M * G.M;
@@ -2214,7 +2102,7 @@ static int step_backward(Plan& P, const gpsa_step_params& prm, const gpsa_step_i
  * runs on a stream of the plan's own (the caller's is usually PyTorch's null stream, which cannot be captured); the
  * graph is launched into the caller's stream.  A first sighting runs eagerly; <= 32 graphs per plan
  * (GPSA_STEP_GRAPH_MAX), least recently used out - retired behind an event, never destroyed under a queued launch; after 8 captures in a row that were never replayed the plan stops capturing.  Never used inside somebody
- * else's capture (train.GraphedTrainStep), with the side stream or the kernel timing on.
+ * else's capture (train.GraphedTrainStep) or with the kernel timing on.
  * Measured (tools/graph_probe.py, BASELINE config 1's size, the reference's loop, runs alternating in one process):
  *   * a fresh process replays 3879 of 3903 calls from 6 graphs (three call kinds x the allocator's two alternating block
  *     sets); a model built after others have come and gone in the same process meets a longer-period allocation
@@ -2246,7 +2134,7 @@ static bool graph_usable(Plan& P, hipStream_t st) {
     const char* e = getenv("GPSA_STEP_GRAPH");
     P.g_enabled = (e && e[0] == '1') ? 1 : 0;
   }
-  if (!P.g_enabled || P.side != nullptr || P.tslots != 0 || P.g_idle_captures > 8) return false;
+  if (!P.g_enabled || P.tslots != 0 || P.g_idle_captures > 8) return false;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;
   return true;
@@ -2343,15 +2231,14 @@ static int graph_call(Plan& P, const Plan::GraphKey& key, hipStream_t st, F&& en
     // now pulls the kernel arguments from under that launch (round 5's unexplained numerics errors "with the cache
     // on, in models built after others" - the models whose allocation pattern has more than 16 distinct argument sets
     // and therefore evicts).  It retires behind an event on the stream it was launched into instead.
-    static const bool unsafe = [] { const char* e = getenv("GPSA_STEP_GRAPH_UNSAFE_DESTROY"); return e && e[0] == '1'; }();
     hipEvent_t ev = nullptr;
     // (the victim may have been launched into ANOTHER stream than this call's - the key includes the stream)
     hipStream_t vst = P.graphs[lru].last;
-    if (!unsafe && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, vst) == hipSuccess) {
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, vst) == hipSuccess) {
       P.retired.push_back(Plan::Retired{P.graphs[lru].exec, ev});
     } else {
       if (ev != nullptr) (void)hipEventDestroy(ev);
-      if (!unsafe) (void)hipStreamSynchronize(vst);
+      (void)hipStreamSynchronize(vst);
       (void)hipGraphExecDestroy(P.graphs[lru].exec);
     }
     P.graphs.erase(P.graphs.begin() + (long)lru);

@@ -283,10 +283,9 @@ static int whiten_launch(int MB, const double* Apk, const TI* X, int M, long lon
   const dim3 grid((unsigned)cdiv(C, 64), (unsigned)batch);
   bool stream = q == nullptr || (long long)grid.x * batch > num_cus();
   // at most one workgroup per CU and no second pass needed for q: split the rows over wave pairs (RS)
-  static const bool rs_off = [] { const char* e = getenv("GPSA_WHITEN_RS"); return e && e[0] == '0'; }();
   // (only while the doubled grid still leaves every workgroup a CU of its own: measured at a 1/8 shard, 80
   //  workgroups 28 -> 19 us, but 391 instead of 196 workgroups 34 -> 44 us)
-  const bool rs = !rs_off && cdiv(C, 32) * batch <= num_cus() && (MB == 13 || MB == 7 || MB == 16 || MB == 4) &&
+  const bool rs = cdiv(C, 32) * batch <= num_cus() && (MB == 13 || MB == 7 || MB == 16 || MB == 4) &&
                   ax.X2 == nullptr;
   if (rs) {
     const dim3 grid2((unsigned)cdiv(C, 32), (unsigned)batch);
@@ -301,7 +300,6 @@ static int whiten_launch(int MB, const double* Apk, const TI* X, int M, long lon
     }
 #undef GPSA_WRS
   }
-  if (const char* e = getenv("GPSA_WHITEN_STREAM")) stream = atoi(e) != 0;
   if (MB > 16) stream = true;
 #define GPSA_WCASE(V)                                                                     \
   case V:                                                                                 \
@@ -402,15 +400,14 @@ int gpsa_whiten_f64_dual(const double* Kinv, const double* Kuf, int M, long long
  *   gpsa_kmat(GPSA_F64, GPSA_F32_X64, ...) evaluates, the same device function in the same precision)
  * so the covariance launch in front and its C*M doubles written and read back disappear (vgpsa.py:171-189: Kuf and
  * the product with Kuu^-1 in one pass).  GPSA_EUNSUPPORTED when the persistent kernel does not take the shape (short
- * panels, M beyond 208, D > 4) or GPSA_PROJ64_GEN=0: the caller then runs gpsa_kmat + gpsa_whiten_f64_dual. */
+ * panels, M beyond 208, D > 4): the caller then runs gpsa_kmat + gpsa_whiten_f64_dual. */
 int gpsa_whiten_gen_f64_dual(const double* Kinv, int kind, const float* Z, const double* X64, int D, const float* ls_u,
                              const float* var_u, int M, long long C, double* alpha64, float* alpha32, double* q,
                              void* workspace, long long workspace_bytes, void* stream) {
   using namespace gpsa;
   if (M < 1 || C < 1 || !Z || !X64 || !ls_u || !var_u || alpha64 == nullptr || alpha32 == nullptr) return GPSA_EINVAL;
-  static const bool off = [] { const char* e = getenv("GPSA_PROJ64_GEN"); return e && e[0] == '0'; }();
   const int MB = whiten_mb_for(M);
-  if (off || MB == 0 || D < 1 || D > MAXD || !proj64_ok(MB, C, 1)) return GPSA_EUNSUPPORTED;
+  if (MB == 0 || D < 1 || D > MAXD || !proj64_ok(MB, C, 1)) return GPSA_EUNSUPPORTED;
   if (kind != GPSA_K_RBF && kind != GPSA_K_MATERN12 && kind != GPSA_K_MATERN32) return GPSA_EINVAL;
   if (workspace_bytes < gpsa_whiten_workspace(M)) return GPSA_EWORKSPACE;
   hipStream_t st = as_stream(stream);

@@ -387,3 +387,24 @@ def test_bench_full_asks_its_config_children_for_their_full_lines(monkeypatch):
     for which in ("1", "3"):
         assert "error" not in bench.extra_workload(which, args)
     assert len(seen) == 3 and all("--full" in cmd for cmd in seen)  # (config 1 twice: with the step-graph cache on)
+
+
+def test_csrc_reads_only_the_listed_environment_variables():
+    """the library's behaviour depends on the process environment through these variables and no others: a new
+    getenv("GPSA_...") in csrc/ has to be added to this list on purpose (A/B switches whose decision is made do not
+    stay in the library: docs/LAB_NOTES.md, "Retired switches")"""
+    import glob
+    import os
+    import re
+
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "spatial_alignment_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*")))
+    assert files
+    found = set()
+    for path in files:
+        with open(path, errors="replace") as f:
+            found.update(re.findall(r'getenv\("(GPSA_[A-Z0-9_]+)"\)', f.read()))
+    assert found == {
+        "GPSA_FORCE_GENERIC", "GPSA_KEEP_GB", "GPSA_LMC_MFMA", "GPSA_ELBO_PAIR", "GPSA_ELBO_NCT", "GPSA_STEP_GRAPH",
+        "GPSA_STEP_GRAPH_MAX", "GPSA_STEP_GRAPH_DEBUG", "GPSA_TIMING_FENCE",
+    }, found

@@ -1,7 +1,7 @@
 """Stress of the step engine's hipGraph cache (GPU): BASELINE config 1's size, several models one after another in one
 process, each trained twice from the same seed - cache off, cache on - and the two loss trajectories compared bit for
 bit.  With GPSA_STEP_GRAPH_MAX small the cache evicts on almost every call.
-usage: [GPSA_STEP_GRAPH_MAX=n] [GPSA_STEP_GRAPH_UNSAFE_DESTROY=1] python tools/graph_stress.py [models] [steps]"""
+usage: [GPSA_STEP_GRAPH_MAX=n] python tools/graph_stress.py [models] [steps]"""
 import ctypes as C
 import os
 import sys
@@ -61,6 +61,5 @@ for k in range(n_models):
           f"trajectories {'IDENTICAL' if same else 'DIFFER (first at sample %s)' % first}  final {ref[-1] if ref else None} / "
           f"{got[-1] if got else None}", flush=True)
     bad += 0 if same else 1
-print("GPSA_STEP_GRAPH_MAX =", os.environ.get("GPSA_STEP_GRAPH_MAX"), " UNSAFE_DESTROY =",
-      os.environ.get("GPSA_STEP_GRAPH_UNSAFE_DESTROY"), " models with a difference:", bad, flush=True)
+print("GPSA_STEP_GRAPH_MAX =", os.environ.get("GPSA_STEP_GRAPH_MAX"), " models with a difference:", bad, flush=True)
 sys.exit(1 if bad else 0)

@@ -1,6 +1,5 @@
-"""Time the data GP's covariance backward (gpsa_kmat_bwd_x64_axpy) alone at the headline size and compare the
-register-accumulating kernel with the older one (env GPSA_KMAT_BWD_D2 / _ROWS / _PER are read once per process:
-run this script once per setting).  usage: python tools/microbench/kmat_bwd_time.py [M C]"""
+"""Time the data GP's covariance backward (gpsa_kmat_bwd_x64_axpy) alone at the headline size.
+usage: python tools/microbench/kmat_bwd_time.py [M C]"""
 import ctypes, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -42,5 +41,4 @@ for _ in range(50):
     run()
 e1.record()
 torch.cuda.synchronize()
-tag = {k: os.environ[k] for k in os.environ if k.startswith("GPSA_KMAT")}
-print(tag, "us per call", round(e0.elapsed_time(e1) * 20, 1), "dZ", dZ.sum().item(), "dX", dX.abs().sum().item(), "dp", dp.tolist())
+print("us per call", round(e0.elapsed_time(e1) * 20, 1), "dZ", dZ.sum().item(), "dX", dX.abs().sum().item(), "dp", dp.tolist())

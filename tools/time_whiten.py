@@ -1,5 +1,5 @@
 """Time the fp64 projection kernels (csrc/whiten.hip, csrc/proj64.hip) at the shapes of the step.
-usage: [GPSA_PROJ64=0|1] [GPSA_PROJ64_MIN_TILES=n] python tools/time_whiten.py [reps]
+usage: python tools/time_whiten.py [reps]
 The packed inverse is built once; the timed calls pass Kinv = NULL (as the engine's later passes do)."""
 import os
 import sys
@@ -77,8 +77,6 @@ def case(name, M, C, kind, B=1):
           f"= {fl / med / 1e6 / 78.6:.2f} of the fp64-MFMA peak   rel.err {err:.1e}", flush=True)
 
 
-print("GPSA_PROJ64 =", os.environ.get("GPSA_PROJ64"), " GPSA_PROJ64_MIN_TILES =", os.environ.get("GPSA_PROJ64_MIN_TILES"),
-      " GPSA_PROJ64_SKIP =", os.environ.get("GPSA_PROJ64_SKIP"))
 case("data GP forward (dual, q)", 200, 100000, "dual")
 case("data GP backward (fp32 in)", 200, 100000, "bwd")
 if os.environ.get("GPSA_TW_SHORT") == "1":
