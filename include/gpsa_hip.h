@@ -725,7 +725,9 @@ int gpsa_elbo_loss_bwd(int n_ll, const float* const* F, const float* const* Y, c
                        double* dkl, void* workspace, long long workspace_bytes, void* stream);
 
 /* gpsa_elbo_loss_fwd / _bwd with some likelihood terms fused into the step (gpsa_step_io.fuse_elbo): zpart[i] non-null =
- * term i's partial sums of z^2 (nparts doubles: gpsa_step_io.ll_part[m]); F[i] / dF[i] are then ignored */
+ * term i's partial sums of z^2 (nparts doubles: gpsa_step_io.ll_part[m]); F[i] / dF[i] are then ignored.  One
+ * implementation serves both pairs: the plain pair above is this one without a zpart table (every term from its draws),
+ * and a table of NULLs here issues exactly the plain pair's launches. */
 int gpsa_elbo_loss_fused_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
                              const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
                              const double* kl, int n_kl, double kl_scale, float* loss, double* ll_out, void* workspace,

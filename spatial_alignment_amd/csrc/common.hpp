@@ -1,4 +1,5 @@
-// Shared device helpers for libgpsa_hip (gfx950 only; wave = 64 lanes).
+// Shared device helpers for libgpsa_hip (gfx950 only; wave = 64 lanes), and the workspace slot and host-side argument
+// check that the ELBO loss entries of elementwise.hip and minibatch.hip have in common.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +30,20 @@ namespace gpsa {
 
 constexpr int WAVE = 64;
 constexpr int MAXD = 4;  // spatial dims supported by the fused covariance kernels
+
+// The ELBO loss entries (gpsa_elbo_loss_fwd / _bwd, _fused_*, _weighted_*): every likelihood term owns a slot of this
+// many doubles in the workspace for its block partials (at most 4096 of them per term)
+constexpr long long LL_SLOT_DOUBLES = 4100;
+// ... and the argument check they share, made before any launch: 0, GPSA_EINVAL or GPSA_EWORKSPACE
+static inline int elbo_loss_args_check(int n_ll, const float* const* F, const float* const* Y,
+                                       const float* const* noise_u, const int* S, const long long* N, const int* P,
+                                       long long workspace_bytes) {
+  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !F || !Y || !noise_u || !S || !N || !P) return GPSA_EINVAL;
+  if (workspace_bytes < 8 * LL_SLOT_DOUBLES * n_ll) return GPSA_EWORKSPACE;
+  for (int i = 0; i < n_ll; ++i)
+    if (S[i] < 1 || N[i] < 1 || P[i] < 1) return GPSA_EINVAL;
+  return 0;
+}
 
 // Cross-lane moves on the DPP path (no LDS crossbar round trip as with ds_bpermute / __shfl_xor).
 template <int CTRL>

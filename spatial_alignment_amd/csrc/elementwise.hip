@@ -642,6 +642,74 @@ static inline int lmc_blocks(long long C, int nparts) {
   if (g > nparts) g = nparts;
   return (int)(g < 1 ? 1 : g);
 }
+// gpsa_elbo_loss_fwd / _bwd and their _fused variants, host side.  zpart (nullable): zpart[i] non-null = term i arrives as
+// nparts partial sums of z^2 and launches no likelihood kernel of its own; every other term's block partials go to its
+// slot of the workspace.
+static int elbo_loss_fwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                              const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                              const double* kl, int n_kl, double kl_scale, float* loss, double* ll_out, void* workspace,
+                              long long workspace_bytes, void* stream) {
+  if (!loss || !ll_out) return GPSA_EINVAL;
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  for (int i = 0; i < n_ll; ++i)
+    if (zpart && zpart[i] && nparts < 1) return GPSA_EINVAL;
+  hipStream_t st = as_stream(stream);
+  ElboFinishArgs a;
+  a.n_ll = n_ll;
+  a.n_kl = kl ? n_kl : 0;
+  a.kl = kl;
+  a.kl_scale = kl_scale;
+  a.ll = ll_out;
+  a.loss = loss;
+  for (int i = 0; i < n_ll; ++i) {
+    const long long NP = N[i] * P[i], tot = NP * S[i];
+    a.S[i] = S[i];
+    a.tot[i] = (double)tot;
+    if (zpart && zpart[i]) {
+      a.part[i] = zpart[i];
+      a.nb[i] = nparts;
+      a.z2_noise[i] = noise_u[i];
+      continue;
+    }
+    const int nb = loglik_blocks(tot);
+    double* part = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
+    loglik_fwd_kernel<<<nb, 256, 0, st>>>(F[i], Y[i], noise_u[i], tot, NP, part);
+    a.part[i] = part;
+    a.nb[i] = nb;
+    a.z2_noise[i] = nullptr;
+  }
+  elbo_loss_finish_kernel<<<1, 256, 0, st>>>(a);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+static int elbo_loss_bwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                              const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                              const float* gloss, int n_kl, double kl_scale, float* const* dF, float* const* dnoise,
+                              float* dnoise_all, int n_noise, double* dkl, void* workspace, long long workspace_bytes,
+                              void* stream) {
+  if (!gloss || !dF || !dnoise) return GPSA_EINVAL;
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  hipStream_t st = as_stream(stream);
+  for (int i = 0; i < n_ll; ++i) {
+    const long long NP = N[i] * P[i], tot = NP * S[i];
+    // the first term's finishing launch also zero-fills the noise gradient and writes dkl
+    double* dkl_i = i == 0 ? dkl : nullptr;
+    float* zero_i = i == 0 ? dnoise_all : nullptr;
+    if (zpart && zpart[i]) {  // (its partials sum z^2, not z^2 - 1: the count goes in)
+      loglik_bwd_finish_kernel<<<1, 256, 0, st>>>(zpart[i], nparts, noise_u[i], nullptr, S[i], dnoise[i], gloss, dkl_i,
+                                                  n_kl, kl_scale, zero_i, n_noise, (double)tot);
+      continue;
+    }
+    const int nb = loglik_blocks(tot);
+    double* part = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
+    loglik_bwd_kernel<<<nb, 256, 0, st>>>(F[i], Y[i], noise_u[i], nullptr, S[i], tot, NP, dF[i], part, gloss);
+    loglik_bwd_finish_kernel<<<1, 256, 0, st>>>(part, nb, noise_u[i], nullptr, S[i], dnoise[i], gloss, dkl_i, n_kl,
+                                                kl_scale, zero_i, n_noise);
+  }
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
 }  // namespace gpsa
 
 extern "C" {
@@ -765,58 +833,42 @@ int gpsa_elbo_bwd(const float* gloss, int n_ll, int n_kl, double kl_scale, doubl
   return 0;
 }
 
-/* ---- likelihood + ELBO fused: one host call each way, one finishing launch for all of it ------------------ */
+/* ---- likelihood + ELBO fused: one host call each way, one finishing launch for all of it ------------------
+ * (the plain pair is the fused pair without a zpart table) */
 int gpsa_elbo_loss_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
                        const int* S, const long long* N, const int* P, const double* kl, int n_kl, double kl_scale,
                        float* loss, double* ll_out, void* workspace, long long workspace_bytes, void* stream) {
-  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !F || !Y || !noise_u || !S || !N || !P || !loss || !ll_out) return GPSA_EINVAL;
-  if (workspace_bytes < 8LL * 4100 * n_ll) return GPSA_EWORKSPACE;
-  hipStream_t st = as_stream(stream);
-  gpsa::ElboFinishArgs a;
-  a.n_ll = n_ll;
-  a.n_kl = kl ? n_kl : 0;
-  a.kl = kl;
-  a.kl_scale = kl_scale;
-  a.ll = ll_out;
-  a.loss = loss;
-  for (int i = 0; i < n_ll; ++i) {
-    if (S[i] < 1 || N[i] < 1 || P[i] < 1) return GPSA_EINVAL;
-    const long long NP = N[i] * P[i], tot = NP * S[i];
-    const int nb = gpsa::loglik_blocks(tot);
-    double* part = reinterpret_cast<double*>(workspace) + 4100LL * i;
-    gpsa::loglik_fwd_kernel<<<nb, 256, 0, st>>>(F[i], Y[i], noise_u[i], tot, NP, part);
-    a.part[i] = part;
-    a.nb[i] = nb;
-    a.S[i] = S[i];
-    a.z2_noise[i] = nullptr;
-    a.tot[i] = (double)tot;
-  }
-  gpsa::elbo_loss_finish_kernel<<<1, 256, 0, st>>>(a);
-  GPSA_LAUNCH_CHECK();
-  return 0;
+  return gpsa::elbo_loss_fwd_impl(n_ll, F, Y, noise_u, S, N, P, nullptr, 0, kl, n_kl, kl_scale, loss, ll_out, workspace,
+                                  workspace_bytes, stream);
 }
 
 int gpsa_elbo_loss_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
                        const int* S, const long long* N, const int* P, const float* gloss, int n_kl, double kl_scale,
                        float* const* dF, float* const* dnoise, float* dnoise_all, int n_noise, double* dkl,
                        void* workspace, long long workspace_bytes, void* stream) {
-  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !F || !Y || !noise_u || !S || !N || !P || !gloss || !dF || !dnoise)
-    return GPSA_EINVAL;
-  if (workspace_bytes < 8LL * 4100 * n_ll) return GPSA_EWORKSPACE;
-  hipStream_t st = as_stream(stream);
-  for (int i = 0; i < n_ll; ++i) {
-    if (S[i] < 1 || N[i] < 1 || P[i] < 1) return GPSA_EINVAL;
-    const long long NP = N[i] * P[i], tot = NP * S[i];
-    const int nb = gpsa::loglik_blocks(tot);
-    double* part = reinterpret_cast<double*>(workspace) + 4100LL * i;
-    gpsa::loglik_bwd_kernel<<<nb, 256, 0, st>>>(F[i], Y[i], noise_u[i], nullptr, S[i], tot, NP, dF[i], part, gloss);
-    // the first term's finishing launch also writes dkl
-    gpsa::loglik_bwd_finish_kernel<<<1, 256, 0, st>>>(part, nb, noise_u[i], nullptr, S[i], dnoise[i], gloss,
-                                                      i == 0 ? dkl : nullptr, n_kl, kl_scale,
-                                                      i == 0 ? dnoise_all : nullptr, n_noise);
-  }
-  GPSA_LAUNCH_CHECK();
-  return 0;
+  return gpsa::elbo_loss_bwd_impl(n_ll, F, Y, noise_u, S, N, P, nullptr, 0, gloss, n_kl, kl_scale, dF, dnoise, dnoise_all,
+                                  n_noise, dkl, workspace, workspace_bytes, stream);
+}
+
+/* ... with some likelihood terms FUSED into the step (gpsa_step_io.fuse_elbo): zpart[i] non-null = term i's partial sums
+ * of z^2 (nparts doubles, gpsa_step_io.ll_part); F[i] / dF[i] are then ignored. */
+int gpsa_elbo_loss_fused_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                             const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                             const double* kl, int n_kl, double kl_scale, float* loss, double* ll_out, void* workspace,
+                             long long workspace_bytes, void* stream) {
+  if (!zpart) return GPSA_EINVAL;
+  return gpsa::elbo_loss_fwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, kl, n_kl, kl_scale, loss, ll_out,
+                                  workspace, workspace_bytes, stream);
+}
+
+int gpsa_elbo_loss_fused_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                             const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                             const float* gloss, int n_kl, double kl_scale, float* const* dF, float* const* dnoise,
+                             float* dnoise_all, int n_noise, double* dkl, void* workspace, long long workspace_bytes,
+                             void* stream) {
+  if (!zpart) return GPSA_EINVAL;
+  return gpsa::elbo_loss_bwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, gloss, n_kl, kl_scale, dF, dnoise,
+                                  dnoise_all, n_noise, dkl, workspace, workspace_bytes, stream);
 }
 
 /* the fused forward's outputs (formed at upstream gradient 1) as the backward wants them: g, dmeanT, abar scaled by the
@@ -896,76 +948,6 @@ int elbo_fused_post_ticket(float* g_ext, float* dmeanT, float* abar, int M, long
 }  // namespace gpsa
 
 extern "C" {
-
-/* gpsa_elbo_loss_fwd / _bwd with some likelihood terms FUSED into the step (gpsa_step_io.fuse_elbo): zpart[i] non-null
- * = term i's partial sums of z^2 (nparts doubles, gpsa_step_io.ll_part); F[i] / dF[i] are then ignored. */
-int gpsa_elbo_loss_fused_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
-                             const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
-                             const double* kl, int n_kl, double kl_scale, float* loss, double* ll_out, void* workspace,
-                             long long workspace_bytes, void* stream) {
-  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !F || !Y || !noise_u || !S || !N || !P || !loss || !ll_out || !zpart)
-    return GPSA_EINVAL;
-  if (workspace_bytes < 8LL * 4100 * n_ll) return GPSA_EWORKSPACE;
-  hipStream_t st = as_stream(stream);
-  gpsa::ElboFinishArgs a;
-  a.n_ll = n_ll;
-  a.n_kl = kl ? n_kl : 0;
-  a.kl = kl;
-  a.kl_scale = kl_scale;
-  a.ll = ll_out;
-  a.loss = loss;
-  for (int i = 0; i < n_ll; ++i) {
-    if (S[i] < 1 || N[i] < 1 || P[i] < 1) return GPSA_EINVAL;
-    const long long NP = N[i] * P[i], tot = NP * S[i];
-    a.S[i] = S[i];
-    a.z2_noise[i] = nullptr;
-    a.tot[i] = (double)tot;
-    if (zpart[i] != nullptr) {
-      if (nparts < 1) return GPSA_EINVAL;
-      a.part[i] = zpart[i];
-      a.nb[i] = nparts;
-      a.z2_noise[i] = noise_u[i];
-      continue;
-    }
-    const int nb = gpsa::loglik_blocks(tot);
-    double* part = reinterpret_cast<double*>(workspace) + 4100LL * i;
-    gpsa::loglik_fwd_kernel<<<nb, 256, 0, st>>>(F[i], Y[i], noise_u[i], tot, NP, part);
-    a.part[i] = part;
-    a.nb[i] = nb;
-  }
-  gpsa::elbo_loss_finish_kernel<<<1, 256, 0, st>>>(a);
-  GPSA_LAUNCH_CHECK();
-  return 0;
-}
-
-int gpsa_elbo_loss_fused_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
-                             const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
-                             const float* gloss, int n_kl, double kl_scale, float* const* dF, float* const* dnoise,
-                             float* dnoise_all, int n_noise, double* dkl, void* workspace, long long workspace_bytes,
-                             void* stream) {
-  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !F || !Y || !noise_u || !S || !N || !P || !gloss || !dF || !dnoise || !zpart)
-    return GPSA_EINVAL;
-  if (workspace_bytes < 8LL * 4100 * n_ll) return GPSA_EWORKSPACE;
-  hipStream_t st = as_stream(stream);
-  for (int i = 0; i < n_ll; ++i) {
-    if (S[i] < 1 || N[i] < 1 || P[i] < 1) return GPSA_EINVAL;
-    const long long NP = N[i] * P[i], tot = NP * S[i];
-    if (zpart[i] != nullptr) {
-      gpsa::loglik_bwd_finish_kernel<<<1, 256, 0, st>>>(zpart[i], nparts, noise_u[i], nullptr, S[i], dnoise[i], gloss,
-                                                        i == 0 ? dkl : nullptr, n_kl, kl_scale,
-                                                        i == 0 ? dnoise_all : nullptr, n_noise, (double)tot);
-      continue;
-    }
-    const int nb = gpsa::loglik_blocks(tot);
-    double* part = reinterpret_cast<double*>(workspace) + 4100LL * i;
-    gpsa::loglik_bwd_kernel<<<nb, 256, 0, st>>>(F[i], Y[i], noise_u[i], nullptr, S[i], tot, NP, dF[i], part, gloss);
-    gpsa::loglik_bwd_finish_kernel<<<1, 256, 0, st>>>(part, nb, noise_u[i], nullptr, S[i], dnoise[i], gloss,
-                                                      i == 0 ? dkl : nullptr, n_kl, kl_scale,
-                                                      i == 0 ? dnoise_all : nullptr, n_noise);
-  }
-  GPSA_LAUNCH_CHECK();
-  return 0;
-}
 
 long long gpsa_lmc_loglik_workspace(long long C, int L, int P, int nparts) {
   if (C < 1 || L < 1 || P < 1 || nparts < 1) return 0;

@@ -283,10 +283,8 @@ int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* co
                                 double kl_scale, float* loss, double* ll_out, void* workspace,
                                 long long workspace_bytes, void* stream) {
   using namespace gpsa;
-  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !F || !Y || !noise_u || !S || !N || !P || !n_views || !view_off || !w ||
-      !loss || !ll_out)
-    return GPSA_EINVAL;
-  if (workspace_bytes < 8LL * 4100 * n_ll) return GPSA_EWORKSPACE;
+  if (!n_views || !view_off || !w || !loss || !ll_out) return GPSA_EINVAL;
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
   hipStream_t st = as_stream(stream);
   WeightedFinishArgs a = {};
   a.n_ll = n_ll;
@@ -296,11 +294,11 @@ int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* co
   a.ll = ll_out;
   a.loss = loss;
   for (int i = 0; i < n_ll; ++i) {
-    if (S[i] < 1 || N[i] < 1 || P[i] < 1 || !w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
+    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
     ViewRows vr;
     for (int v = 0; v <= n_views[i]; ++v) vr.off[v] = view_off[i][v];
     const int nb = loglik_w_blocks(S[i], view_off[i], n_views[i], P[i]);
-    double* part = reinterpret_cast<double*>(workspace) + 4100LL * i;
+    double* part = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
     loglik_w_kernel<false><<<dim3(nb, n_views[i]), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], vr,
                                                                  w[i], nullptr, nullptr, part);
     a.part[i] = part;
@@ -320,17 +318,15 @@ int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* co
                                 double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all,
                                 int n_noise, double* dkl, void* workspace, long long workspace_bytes, void* stream) {
   using namespace gpsa;
-  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !F || !Y || !noise_u || !S || !N || !P || !n_views || !view_off || !w ||
-      !gloss || !dF || !dnoise)
-    return GPSA_EINVAL;
-  if (workspace_bytes < 8LL * 4100 * n_ll) return GPSA_EWORKSPACE;
+  if (!n_views || !view_off || !w || !gloss || !dF || !dnoise) return GPSA_EINVAL;
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
   hipStream_t st = as_stream(stream);
   for (int i = 0; i < n_ll; ++i) {
-    if (S[i] < 1 || N[i] < 1 || P[i] < 1 || !w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
+    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
     ViewRows vr;
     for (int v = 0; v <= n_views[i]; ++v) vr.off[v] = view_off[i][v];
     const int nb = loglik_w_blocks(S[i], view_off[i], n_views[i], P[i]);
-    double* part = reinterpret_cast<double*>(workspace) + 4100LL * i;
+    double* part = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
     loglik_w_kernel<true><<<dim3(nb, n_views[i]), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], vr,
                                                                 w[i], gloss, dF[i], part);
     // the first term's finishing launch also zero-fills the noise gradient and writes dkl

@@ -943,6 +943,12 @@ class VariationalGPSA(GPSA):
             weights.append(w)
         return dict(n_views=n_views, view_off=view_off, weights=weights)
 
+    def _loss_aux(self, data_dict):
+        """the loss nodes' ``aux``: observations, the modalities' entries of ``noise_variance`` (quirk 5), the KL scale"""
+        nn_ = self.noise_variance.numel()
+        return dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
+                    noise_idx=[nn_ - self.n_modalities + i for i in range(self.n_modalities)], kl_scale=self.kl_scale)
+
     # ------------------------------------------------------------------------------------------
     def loss_fn(self, data_dict, F_samples):
         """Negative (approximate) ELBO (vgpsa.py:491-540).  Valid only after ``forward`` on the same
@@ -956,10 +962,7 @@ class VariationalGPSA(GPSA):
             kl = cache.kl if self.kl_scale != 0 else None  # (a slice without a KL share: no KL backward either)
             if kl is not None and self.kl_weight_G != 1.0:  # output-sharded rank: its share of the warp GPs' terms
                 kl = torch.cat([kl[: V * D] * self.kl_weight_G, kl[V * D:]])
-            nn_ = self.noise_variance.numel()
-            aux = dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
-                       noise_idx=[nn_ - self.n_modalities + i for i in range(self.n_modalities)],  # quirk 5
-                       kl_scale=self.kl_scale)
+            aux = self._loss_aux(data_dict)
             if weighted is not None:
                 # weighted terms take the separate kernels: lazy draws / LMC products materialise (the fused closings
                 # have no per-view weights)
@@ -1057,10 +1060,7 @@ class VariationalGPSA(GPSA):
             Y = data_dict[m]["outputs"]
             lls.append(E.LogLikFn.apply(F_samples[m], Y, noise_u))
         if weighted is not None:
-            nn_ = self.noise_variance.numel()
-            aux = dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
-                       noise_idx=[nn_ - self.n_modalities + i for i in range(self.n_modalities)],  # quirk 5
-                       kl_scale=self.kl_scale, **weighted)
+            aux = dict(self._loss_aux(data_dict), **weighted)
             Fs = [F_samples[m] for m in self.modality_names]
             return SE.WeightedElboLossFn.apply(aux, self.noise_variance, kl, *Fs).to(self.Xtilde.dtype)
         ll = lls[0] if len(lls) == 1 else torch.stack(lls)

@@ -3,7 +3,9 @@
 ``forward`` of the model becomes ONE autograd node whose forward and backward are one C call each
 (``gpsa_step_forward`` / ``gpsa_step_backward``): the launch sequence of the whole step is enqueued from
 C++, the warp GPs of all free views share their launches, and every parameter gradient is accumulated in
-fp64 and rounded once.  ``loss_fn`` is a second node (``gpsa_elbo_loss_fwd`` / ``_bwd``).
+fp64 and rounded once.  ``loss_fn`` is a second node, ``ElboLossFn``: ``gpsa_elbo_loss_fused_fwd`` / ``_bwd`` when some
+likelihood terms arrive from the step as partial sums, ``gpsa_elbo_loss_fwd`` / ``_bwd`` (the same host code without
+such terms) otherwise; ``WeightedElboLossFn`` (``gpsa_elbo_loss_weighted_fwd`` / ``_bwd``) under minibatch weights.
 
 PyTorch remains plumbing: it owns the tensors (parameters, outputs, the two arenas), the stream and the
 autograd bookkeeping between the two nodes and the optimiser.
@@ -27,7 +29,6 @@ LAST_LOSS = {}  # the loss tensor the closing kernel copied into LAST_FLAT's las
 
 MAXM = _lib.MAX_MODS
 KINDS = _ops_mod.KINDS
-_raw_stream = torch._C._cuda_getCurrentRawStream
 
 
 def _p(t):
@@ -736,64 +737,68 @@ class StepFn(torch.autograd.Function):
             fuse["live"] = None
 
 
+def _f32c(t):
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _loss_inputs(Fs, Ys, noise, kl, fused=None, flat_kl=False):
+    """the loss nodes' inputs as the kernels read them -> (Fc, Yc, nz, klc): detached contiguous fp32 draws (a fused
+    term's partial sums stay as they are), observations and noise; kl detached contiguous fp64 (or None)"""
+    Fc = [f.detach() if (fused is not None and fused[i]) else _f32c(f.detach()) for i, f in enumerate(Fs)]
+    klc = None
+    if kl is not None:
+        klc = kl.detach().reshape(-1) if flat_kl else kl.detach()
+        klc = klc if (klc.dtype == torch.float64 and klc.is_contiguous()) else klc.double().contiguous()
+    return Fc, [_f32c(y) for y in Ys], _f32c(noise.detach()), klc
+
+
+def _loss_ws(n, like):
+    return _ops_mod.get_ops()._ws(TO.loss_workspace_bytes(n), like)
+
+
+def _loss_outputs(n, dev):
+    """-> (loss [1] fp32, ll [n] fp64, workspace) for a loss forward over n likelihood terms"""
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    return loss, torch.empty(n, dtype=torch.float64, device=dev), _loss_ws(n, loss)
+
+
+def _loss_grad_buffers(gloss, Fc, nz, n_kl, fused=None):
+    """-> (g, dF, dnoise, dkl, workspace) for a loss backward: the upstream gradient as [1] fp32 and the outputs (a
+    fused term's dF is a placeholder: its real gradient travels through the ``fuse`` record)"""
+    dev = Fc[0].device
+    g = gloss.detach().reshape(1)
+    g = g if g.dtype == torch.float32 else g.float()
+    dF = [placeholder_grad(dev, f.numel()) if (fused is not None and fused[i]) else torch.empty_like(f)
+          for i, f in enumerate(Fc)]
+    dnoise = torch.empty(nz.numel(), dtype=torch.float32, device=dev)  # zero-filled by the first finishing launch
+    dkl = torch.empty(n_kl, dtype=torch.float64, device=dev) if n_kl else None
+    return g, dF, dnoise, dkl, _loss_ws(len(Fc), g)
+
+
+def _loss_grads(ctx, dnoise, dkl, dF, dWs=()):
+    shape, dt = ctx.noise_meta
+    return (None, dnoise.reshape(shape).to(dt), dkl) + tuple(dF) + tuple(dWs)
+
+
 class ElboLossFn(torch.autograd.Function):
     """loss = -(sum_i LL_i) + kl_scale * sum(kl_w * kl)   (vgpsa.py:532-540) as one C call each way.
-    inputs: noise_variance [n], kl [T] or None, F_0 .. F_{n_ll-1};  aux: Y tensors, noise indices, kl_scale"""
+    inputs: noise_variance [n], kl [T] or None, F_0 .. F_{n_ll-1} (then the W of the LMC terms);
+    aux: Y tensors, noise indices, kl_scale.  With aux["fuse_mods"] the terms it marks arrive as partial sums of z^2
+    instead of draws: from the step (StepFn with aux["fuse"]: the likelihood rode in the data GP's pass), or - an LMC
+    modality, aux["lmc"] = {term: index of its W among the trailing inputs} - formed here from (F_latent, W, Y) without
+    F_obs (gpsa_lmc_loglik_fused_f32); aux["term_shapes"] holds such a term's [S, N, P].  A call with at least one such
+    term takes gpsa_elbo_loss_fused_fwd / _bwd, one with none gpsa_elbo_loss_fwd / _bwd."""
 
     @staticmethod
-    def forward(ctx, aux, noise, kl, *Fs):
-        if aux.get("fuse_mods") is not None:
-            return ElboLossFn._forward_fused(ctx, aux, noise, kl, *Fs)
-        lib = _lib.load()
-        o = _ops_mod.get_ops()
-        n = len(Fs)
-        dev = Fs[0].device
-        Fc = [f.detach() if (f.dtype == torch.float32 and f.is_contiguous()) else f.detach().float().contiguous()
-              for f in Fs]
-        Yc = [y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous() for y in aux["Y"]]
-        nz = noise.detach()
-        nz = nz if (nz.dtype == torch.float32 and nz.is_contiguous()) else nz.float().contiguous()
-        arr = lambda vals: (C.c_void_p * n)(*vals)
-        Fp, Yp = arr([f.data_ptr() for f in Fc]), arr([y.data_ptr() for y in Yc])
-        Np = arr([nz.data_ptr() + 4 * j for j in aux["noise_idx"]])
-        Sa = (C.c_int * n)(*[int(f.shape[0]) for f in Fc])
-        Na = (C.c_longlong * n)(*[int(f.shape[1]) for f in Fc])
-        Pa = (C.c_int * n)(*[int(f.shape[2]) for f in Fc])
-        klc = None
-        if kl is not None:
-            klc = kl.detach()
-            klc = klc if (klc.dtype == torch.float64 and klc.is_contiguous()) else klc.double().contiguous()
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ll = torch.empty(n, dtype=torch.float64, device=dev)
-        ws = o._ws(8 * 4100 * n + 64, loss)
-        stream = _raw_stream(dev.index)
-        torch.ops.gpsa.elbo_loss_fwd(Fc, Yc, nz, [int(j) for j in aux["noise_idx"]], klc, float(aux["kl_scale"]), loss,
-                                     ll, ws)
-        ctx.aux, ctx.args = aux, (Fc, Yc, nz, Fp, Yp, Np, Sa, Na, Pa)
-        ctx.n_kl = 0 if klc is None else klc.numel()
-        ctx.noise_meta = (noise.shape, noise.dtype)
-        return loss.reshape(())
-
-    @staticmethod
-    def _forward_fused(ctx, aux, noise, kl, *ins):
-        """some terms arrive as partial sums of z^2 instead of draws: from the step (StepFn with aux["fuse"]: the
-        likelihood rode in the data GP's pass), or - an LMC modality, aux["lmc"] = {term: index of its W among the
-        trailing inputs} - formed here from (F_latent, W, Y) without F_obs (gpsa_lmc_loglik_fused_f32)"""
-        o = _ops_mod.get_ops()
-        fuse = aux.get("fuse")
-        lmc = aux.get("lmc") or {}
-        fused = [bool(z) for z in aux["fuse_mods"]]  # the terms that come as partial sums in THIS call
+    def forward(ctx, aux, noise, kl, *ins):
         n = len(aux["Y"])
         Fs, Ws = ins[:n], ins[n:]
+        partial = aux.get("fuse_mods") is not None
+        fused = [bool(z) for z in aux["fuse_mods"]] if partial else [False] * n  # partial sums in THIS call
+        lmc = (aux.get("lmc") or {}) if partial else {}
         dev = Fs[0].device
-        Fc = [f.detach() if (z or (f.dtype == torch.float32 and f.is_contiguous())) else f.detach().float().contiguous()
-              for f, z in zip(Fs, fused)]
-        Yc = [y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous() for y in aux["Y"]]
-        nz = noise.detach()
-        nz = nz if (nz.dtype == torch.float32 and nz.is_contiguous()) else nz.float().contiguous()
-        shapes = []
-        for i in range(n):
-            shapes += list(aux["term_shapes"][i]) if fused[i] else [int(d) for d in Fc[i].shape]
+        Fc, Yc, nz, klc = _loss_inputs(Fs, aux["Y"], noise, kl, fused)
+        idx = [int(j) for j in aux["noise_idx"]]
         lmc_saved = {}
         for i, wpos in lmc.items():
             Fl, W = Fc[i], Ws[wpos].detach()
@@ -801,20 +806,21 @@ class ElboLossFn(torch.autograd.Function):
             nparts = int(_lib.load().gpsa_quadform_elbo_parts())
             zpart = torch.empty(nparts, dtype=torch.float64, device=dev)
             dFl, dW = torch.empty_like(Fl), torch.empty_like(W)
-            wsl = o._ws(int(_lib.load().gpsa_lmc_loglik_workspace(S_ * N_, L_, int(W.shape[1]), nparts)), Fl)
-            torch.ops.gpsa.lmc_loglik_fused(Fl, W, Yc[i], nz, int(aux["noise_idx"][i]), zpart, dFl, dW, wsl)
+            wsl = _ops_mod.get_ops()._ws(int(_lib.load().gpsa_lmc_loglik_workspace(S_ * N_, L_, int(W.shape[1]), nparts)),
+                                         Fl)
+            torch.ops.gpsa.lmc_loglik_fused(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
             lmc_saved[i] = (dFl, dW, wpos)
             Fc[i] = zpart
-        klc = None
-        if kl is not None:
-            klc = kl.detach()
-            klc = klc if (klc.dtype == torch.float64 and klc.is_contiguous()) else klc.double().contiguous()
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ll = torch.empty(n, dtype=torch.float64, device=dev)
-        ws = o._ws(8 * 4100 * n + 64, loss)
-        idx = [int(j) for j in aux["noise_idx"]]
-        torch.ops.gpsa.elbo_loss_fused_fwd(Fc, Yc, nz, idx, shapes, [int(z) for z in fused], klc, float(aux["kl_scale"]),
-                                           loss, ll, ws)
+        loss, ll, ws = _loss_outputs(n, dev)  # (after the LMC terms: they grow the same per-stream scratch)
+        shapes = None
+        if any(fused):
+            shapes = []
+            for i in range(n):
+                shapes += list(aux["term_shapes"][i]) if fused[i] else [int(d) for d in Fc[i].shape]
+            torch.ops.gpsa.elbo_loss_fused_fwd(Fc, Yc, nz, idx, shapes, [int(z) for z in fused], klc,
+                                               float(aux["kl_scale"]), loss, ll, ws)
+        else:
+            torch.ops.gpsa.elbo_loss_fwd(Fc, Yc, nz, idx, klc, float(aux["kl_scale"]), loss, ll, ws)
         ctx.aux, ctx.args = aux, (Fc, Yc, nz, idx, shapes, fused)
         ctx.lmc, ctx.n_w = lmc_saved, len(Ws)
         ctx.n_kl = 0 if klc is None else klc.numel()
@@ -822,53 +828,25 @@ class ElboLossFn(torch.autograd.Function):
         return loss.reshape(())
 
     @staticmethod
-    def _backward_fused(ctx, gloss):
-        o = _ops_mod.get_ops()
+    def backward(ctx, gloss):
         aux = ctx.aux
         fuse = aux.get("fuse")
         Fc, Yc, nz, idx, shapes, fused = ctx.args
-        dev = Fc[0].device
-        g = gloss.detach().reshape(1)
-        g = g if g.dtype == torch.float32 else g.float()
+        g, dF, dnoise, dkl, ws = _loss_grad_buffers(gloss, Fc, nz, ctx.n_kl, fused)
         if fuse is not None and any(z and i not in ctx.lmc for i, z in enumerate(fused)):
             # StepFn.backward hands it to the engine (gpsa_step_out_grads.gloss); loss_fn called twice on one forward: summed
             fuse["gloss"] = g if fuse.get("gloss") is None else fuse["gloss"] + g
-        dF = [placeholder_grad(dev, f.numel()) if z else torch.empty_like(f) for f, z in zip(Fc, fused)]
         dWs = [None] * ctx.n_w
         for i, (dFl, dW, wpos) in ctx.lmc.items():  # formed at upstream gradient 1 by the forward: scaled here
             dF[i] = dFl * g
             dWs[wpos] = dW * g
-        dnoise = torch.empty(nz.numel(), dtype=torch.float32, device=dev)
-        dkl = torch.empty(ctx.n_kl, dtype=torch.float64, device=dev) if ctx.n_kl else None
-        ws = o._ws(8 * 4100 * len(Fc) + 64, g)
-        real = [d if not z else g for d, z in zip(dF, fused)]  # (mutable-argument list: no expanded tensors in it)
-        torch.ops.gpsa.elbo_loss_fused_bwd(Fc, Yc, nz, idx, shapes, [int(z) for z in fused], g, int(ctx.n_kl),
-                                           float(aux["kl_scale"]), real, dnoise, dkl, ws)
-        shape, dt = ctx.noise_meta
-        return (None, dnoise.reshape(shape).to(dt), dkl) + tuple(dF) + tuple(dWs)
-
-    @staticmethod
-    def backward(ctx, gloss):
-        if ctx.aux.get("fuse_mods") is not None:
-            return ElboLossFn._backward_fused(ctx, gloss)
-        lib = _lib.load()
-        o = _ops_mod.get_ops()
-        aux = ctx.aux
-        Fc, Yc, nz, Fp, Yp, Np, Sa, Na, Pa = ctx.args
-        n = len(Fc)
-        dev = Fc[0].device
-        g = gloss.detach().reshape(1)
-        g = g if g.dtype == torch.float32 else g.float()
-        dF = [torch.empty_like(f) for f in Fc]
-        dnoise = torch.empty(nz.numel(), dtype=torch.float32, device=dev)  # zero-filled by the first finishing launch
-        dkl = torch.empty(ctx.n_kl, dtype=torch.float64, device=dev) if ctx.n_kl else None
-        dFp = (C.c_void_p * n)(*[t.data_ptr() for t in dF])
-        dNp = (C.c_void_p * n)(*[dnoise.data_ptr() + 4 * j for j in aux["noise_idx"]])
-        ws = o._ws(8 * 4100 * n + 64, g)
-        torch.ops.gpsa.elbo_loss_bwd(Fc, Yc, nz, [int(j) for j in aux["noise_idx"]], g, int(ctx.n_kl),
-                                     float(aux["kl_scale"]), dF, dnoise, dkl, ws)
-        shape, dt = ctx.noise_meta
-        return (None, dnoise.reshape(shape).to(dt), dkl) + tuple(dF)
+        if any(fused):
+            real = [d if not z else g for d, z in zip(dF, fused)]  # (mutable-argument list: no expanded tensors in it)
+            torch.ops.gpsa.elbo_loss_fused_bwd(Fc, Yc, nz, idx, shapes, [int(z) for z in fused], g, int(ctx.n_kl),
+                                               float(aux["kl_scale"]), real, dnoise, dkl, ws)
+        else:
+            torch.ops.gpsa.elbo_loss_bwd(Fc, Yc, nz, idx, g, int(ctx.n_kl), float(aux["kl_scale"]), dF, dnoise, dkl, ws)
+        return _loss_grads(ctx, dnoise, dkl, dF, dWs)
 
 
 class WeightedElboLossFn(torch.autograd.Function):
@@ -880,20 +858,8 @@ class WeightedElboLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, aux, noise, kl, *Fs):
-        o = _ops_mod.get_ops()
-        n = len(Fs)
-        dev = Fs[0].device
-        f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-        Fc = [f32(f.detach()) for f in Fs]
-        Yc = [f32(y) for y in aux["Y"]]
-        nz = f32(noise.detach())
-        klc = None
-        if kl is not None:
-            klc = kl.detach().reshape(-1)
-            klc = klc if (klc.dtype == torch.float64 and klc.is_contiguous()) else klc.double().contiguous()
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ll = torch.empty(n, dtype=torch.float64, device=dev)
-        ws = o._ws(8 * 4100 * n + 64, loss)
+        Fc, Yc, nz, klc = _loss_inputs(Fs, aux["Y"], noise, kl, flat_kl=True)
+        loss, ll, ws = _loss_outputs(len(Fs), Fs[0].device)
         idx = [int(j) for j in aux["noise_idx"]]
         torch.ops.gpsa.elbo_loss_weighted_fwd(Fc, Yc, nz, idx, list(aux["n_views"]), list(aux["view_off"]),
                                               list(aux["weights"]), klc, float(aux["kl_scale"]), loss, ll, ws)
@@ -905,21 +871,13 @@ class WeightedElboLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss):
-        o = _ops_mod.get_ops()
         aux = ctx.aux
         Fc, Yc, nz, idx = ctx.args
-        dev = Fc[0].device
-        g = gloss.detach().reshape(1)
-        g = g if g.dtype == torch.float32 else g.float()
-        dF = [torch.empty_like(f) for f in Fc]
-        dnoise = torch.empty(nz.numel(), dtype=torch.float32, device=dev)  # zero-filled by the first finishing launch
-        dkl = torch.empty(ctx.n_kl, dtype=torch.float64, device=dev) if ctx.n_kl else None
-        ws = o._ws(8 * 4100 * len(Fc) + 64, g)
+        g, dF, dnoise, dkl, ws = _loss_grad_buffers(gloss, Fc, nz, ctx.n_kl)
         torch.ops.gpsa.elbo_loss_weighted_bwd(Fc, Yc, nz, idx, list(aux["n_views"]), list(aux["view_off"]),
                                               list(aux["weights"]), g, int(ctx.n_kl), float(aux["kl_scale"]), dF,
                                               dnoise, dkl, ws)
         if dkl is not None:
             kshape, kdt = ctx.kl_meta
             dkl = dkl.reshape(kshape).to(kdt)
-        shape, dt = ctx.noise_meta
-        return (None, dnoise.reshape(shape).to(dt), dkl) + tuple(dF)
+        return _loss_grads(ctx, dnoise, dkl, dF)

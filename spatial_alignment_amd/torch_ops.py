@@ -335,20 +335,42 @@ _engine_op("step_backward(Tensor[] params, Tensor[] grads_out, Tensor saved, Ten
            "int call) -> ()", _step_backward)
 
 
-def _ll_arrays(Fs, Ys, noise, noise_idx):
+def loss_workspace_bytes(n):  # n likelihood terms, LL_SLOT_DOUBLES (csrc/common.hpp) doubles each; tests/test_cabi.py
+    return 8 * 4100 * n + 64
+
+
+def _ll_arrays(Fs, Ys, noise, noise_idx, shapes=None, fused=None):
+    """-> (n, (F, Y, noise_u, S, N, P), zpart, nparts) as the gpsa_elbo_loss_* entries take them.  shapes: [S, N, P] per
+    term, flattened (default: those of Fs); fused: per term, whether its "F" is its partial-sum vector (ll_part)"""
     n = len(Fs)
     arr = lambda vals: (C.c_void_p * n)(*vals)
-    return (n, arr([f.data_ptr() for f in Fs]), arr([y.data_ptr() for y in Ys]),
-            arr([noise.data_ptr() + 4 * j for j in noise_idx]), (C.c_int * n)(*[int(f.shape[0]) for f in Fs]),
-            (C.c_longlong * n)(*[int(f.shape[1]) for f in Fs]), (C.c_int * n)(*[int(f.shape[2]) for f in Fs]))
+    sh = [int(f.shape[k]) for f in Fs for k in range(3)] if shapes is None else shapes[:3 * n]
+    if fused is None:
+        Fp, Zp, nparts = arr([f.data_ptr() for f in Fs]), None, 0
+    else:
+        Fp = arr([0 if z else f.data_ptr() for f, z in zip(Fs, fused)])
+        Zp = arr([f.data_ptr() if z else 0 for f, z in zip(Fs, fused)])
+        nparts = max([int(f.numel()) for f, z in zip(Fs, fused) if z] or [0])
+    terms = (Fp, arr([y.data_ptr() for y in Ys]), arr([noise.data_ptr() + 4 * j for j in noise_idx]),
+             (C.c_int * n)(*sh[0::3]), (C.c_longlong * n)(*sh[1::3]), (C.c_int * n)(*sh[2::3]))
+    return n, terms, Zp, nparts
+
+
+def _grad_arrays(dFs, dnoise, noise_idx, fused=None):
+    n = len(dFs)  # -> dF pointers (NULL for a fused term), pointers to the terms' noise gradients, dnoise_all, n_noise
+    return ((C.c_void_p * n)(*[0 if (fused and fused[i]) else t.data_ptr() for i, t in enumerate(dFs)]),
+            (C.c_void_p * n)(*[dnoise.data_ptr() + 4 * j for j in noise_idx]), dnoise.data_ptr(), dnoise.numel())
+
+
+def _kl_args(kl):
+    return (0, 0) if kl is None else (kl.data_ptr(), kl.numel())
 
 
 def _elbo_loss_fwd(Fs, Ys, noise, noise_idx, kl, kl_scale, loss, ll, ws):
     """loss = -(sum_i LL_i) + kl_scale * sum(kl): log-likelihood partials, finish and the ELBO glue
     (gpsa_elbo_loss_fwd; contiguous fp32 F / Y / noise, fp64 kl)"""
-    n, Fp, Yp, Np, Sa, Na, Pa = _ll_arrays(Fs, Ys, noise, noise_idx)
-    _lib.check(_lib.load().gpsa_elbo_loss_fwd(n, Fp, Yp, Np, Sa, Na, Pa, 0 if kl is None else kl.data_ptr(),
-                                              0 if kl is None else kl.numel(), float(kl_scale), loss.data_ptr(),
+    n, terms, _, _ = _ll_arrays(Fs, Ys, noise, noise_idx)
+    _lib.check(_lib.load().gpsa_elbo_loss_fwd(n, *terms, *_kl_args(kl), float(kl_scale), loss.data_ptr(),
                                               ll.data_ptr(), ws.data_ptr(), ws.numel(),
                                               _raw_stream(loss.device.index)), "gpsa_elbo_loss_fwd")
 
@@ -358,11 +380,9 @@ _engine_op("elbo_loss_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_id
 
 
 def _elbo_loss_bwd(Fs, Ys, noise, noise_idx, gloss, n_kl, kl_scale, dFs, dnoise, dkl, ws):
-    n, Fp, Yp, Np, Sa, Na, Pa = _ll_arrays(Fs, Ys, noise, noise_idx)
-    dFp = (C.c_void_p * n)(*[t.data_ptr() for t in dFs])
-    dNp = (C.c_void_p * n)(*[dnoise.data_ptr() + 4 * j for j in noise_idx])
-    _lib.check(_lib.load().gpsa_elbo_loss_bwd(n, Fp, Yp, Np, Sa, Na, Pa, gloss.data_ptr(), int(n_kl), float(kl_scale),
-                                              dFp, dNp, dnoise.data_ptr(), dnoise.numel(),
+    n, terms, _, _ = _ll_arrays(Fs, Ys, noise, noise_idx)
+    grads = _grad_arrays(dFs, dnoise, noise_idx)
+    _lib.check(_lib.load().gpsa_elbo_loss_bwd(n, *terms, gloss.data_ptr(), int(n_kl), float(kl_scale), *grads,
                                               0 if dkl is None else dkl.data_ptr(), ws.data_ptr(), ws.numel(),
                                               _raw_stream(gloss.device.index)), "gpsa_elbo_loss_bwd")
 
@@ -371,26 +391,12 @@ _engine_op("elbo_loss_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_id
            "float kl_scale, Tensor(a!)[] dFs, Tensor(b!) dnoise, Tensor(c!)? dkl, Tensor(d!) ws) -> ()", _elbo_loss_bwd)
 
 
-def _ll_arrays_fused(Fs, Ys, noise, noise_idx, shapes, fused):
-    """as _ll_arrays with explicit [S, N, P] per term; a fused term's "F" is its partial-sum vector (gpsa_step_io.ll_part)"""
-    n = len(Fs)
-    arr = lambda vals: (C.c_void_p * n)(*vals)
-    nparts = max([int(f.numel()) for f, z in zip(Fs, fused) if z] or [0])
-    return (n, arr([0 if z else f.data_ptr() for f, z in zip(Fs, fused)]), arr([y.data_ptr() for y in Ys]),
-            arr([noise.data_ptr() + 4 * j for j in noise_idx]), (C.c_int * n)(*[int(shapes[3 * i]) for i in range(n)]),
-            (C.c_longlong * n)(*[int(shapes[3 * i + 1]) for i in range(n)]),
-            (C.c_int * n)(*[int(shapes[3 * i + 2]) for i in range(n)]),
-            arr([f.data_ptr() if z else 0 for f, z in zip(Fs, fused)]), nparts)
-
-
 def _elbo_loss_fused_fwd(Fs, Ys, noise, noise_idx, shapes, fused, kl, kl_scale, loss, ll, ws):
     """gpsa_elbo_loss_fused_fwd: the loss with some likelihood terms already reduced to partial sums by the step"""
-    n, Fp, Yp, Np, Sa, Na, Pa, Zp, nparts = _ll_arrays_fused(Fs, Ys, noise, noise_idx, shapes, fused)
-    _lib.check(_lib.load().gpsa_elbo_loss_fused_fwd(n, Fp, Yp, Np, Sa, Na, Pa, Zp, nparts,
-                                                    0 if kl is None else kl.data_ptr(), 0 if kl is None else kl.numel(),
-                                                    float(kl_scale), loss.data_ptr(), ll.data_ptr(), ws.data_ptr(),
-                                                    ws.numel(), _raw_stream(loss.device.index)),
-               "gpsa_elbo_loss_fused_fwd")
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes, fused)
+    _lib.check(_lib.load().gpsa_elbo_loss_fused_fwd(n, *terms, Zp, nparts, *_kl_args(kl), float(kl_scale),
+                                                    loss.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    _raw_stream(loss.device.index)), "gpsa_elbo_loss_fused_fwd")
 
 
 _engine_op("elbo_loss_fused_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
@@ -398,13 +404,12 @@ _engine_op("elbo_loss_fused_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] no
 
 
 def _elbo_loss_fused_bwd(Fs, Ys, noise, noise_idx, shapes, fused, gloss, n_kl, kl_scale, dFs, dnoise, dkl, ws):
-    n, Fp, Yp, Np, Sa, Na, Pa, Zp, nparts = _ll_arrays_fused(Fs, Ys, noise, noise_idx, shapes, fused)
-    dFp = (C.c_void_p * n)(*[0 if z else t.data_ptr() for t, z in zip(dFs, fused)])
-    dNp = (C.c_void_p * n)(*[dnoise.data_ptr() + 4 * j for j in noise_idx])
-    _lib.check(_lib.load().gpsa_elbo_loss_fused_bwd(n, Fp, Yp, Np, Sa, Na, Pa, Zp, nparts, gloss.data_ptr(), int(n_kl),
-                                                    float(kl_scale), dFp, dNp, dnoise.data_ptr(), dnoise.numel(),
-                                                    0 if dkl is None else dkl.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    _raw_stream(gloss.device.index)), "gpsa_elbo_loss_fused_bwd")
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes, fused)
+    grads = _grad_arrays(dFs, dnoise, noise_idx, fused)
+    _lib.check(_lib.load().gpsa_elbo_loss_fused_bwd(n, *terms, Zp, nparts, gloss.data_ptr(), int(n_kl), float(kl_scale),
+                                                    *grads, 0 if dkl is None else dkl.data_ptr(), ws.data_ptr(),
+                                                    ws.numel(), _raw_stream(gloss.device.index)),
+               "gpsa_elbo_loss_fused_bwd")
 
 
 _engine_op("elbo_loss_fused_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
@@ -476,12 +481,10 @@ def _view_arrays(n_views, view_off):
 def _elbo_loss_weighted_fwd(Fs, Ys, noise, noise_idx, n_views, view_off, weights, kl, kl_scale, loss, ll, ws):
     """gpsa_elbo_loss_fwd with per-view fp64 weights: loss = -sum_m sum_v w_mv LL_mv + kl_scale * sum(kl)
     (view_off: every term's n_views + 1 row offsets, concatenated)"""
-    n, Fp, Yp, Np, Sa, Na, Pa = _ll_arrays(Fs, Ys, noise, noise_idx)
+    n, terms, _, _ = _ll_arrays(Fs, Ys, noise, noise_idx)
     nv, offp, _keep = _view_arrays(n_views, view_off)
     Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
-    _lib.check(_lib.load().gpsa_elbo_loss_weighted_fwd(n, Fp, Yp, Np, Sa, Na, Pa, nv, offp, Wp,
-                                                       0 if kl is None else kl.data_ptr(),
-                                                       0 if kl is None else kl.numel(), float(kl_scale),
+    _lib.check(_lib.load().gpsa_elbo_loss_weighted_fwd(n, *terms, nv, offp, Wp, *_kl_args(kl), float(kl_scale),
                                                        loss.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(),
                                                        _raw_stream(loss.device.index)), "gpsa_elbo_loss_weighted_fwd")
 
@@ -493,14 +496,12 @@ _engine_op("elbo_loss_weighted_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[]
 
 def _elbo_loss_weighted_bwd(Fs, Ys, noise, noise_idx, n_views, view_off, weights, gloss, n_kl, kl_scale, dFs, dnoise,
                             dkl, ws):
-    n, Fp, Yp, Np, Sa, Na, Pa = _ll_arrays(Fs, Ys, noise, noise_idx)
+    n, terms, _, _ = _ll_arrays(Fs, Ys, noise, noise_idx)
     nv, offp, _keep = _view_arrays(n_views, view_off)
     Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
-    dFp = (C.c_void_p * n)(*[t.data_ptr() for t in dFs])
-    dNp = (C.c_void_p * n)(*[dnoise.data_ptr() + 4 * j for j in noise_idx])
-    _lib.check(_lib.load().gpsa_elbo_loss_weighted_bwd(n, Fp, Yp, Np, Sa, Na, Pa, nv, offp, Wp, gloss.data_ptr(),
-                                                       int(n_kl), float(kl_scale), dFp, dNp, dnoise.data_ptr(),
-                                                       dnoise.numel(), 0 if dkl is None else dkl.data_ptr(),
+    grads = _grad_arrays(dFs, dnoise, noise_idx)
+    _lib.check(_lib.load().gpsa_elbo_loss_weighted_bwd(n, *terms, nv, offp, Wp, gloss.data_ptr(), int(n_kl),
+                                                       float(kl_scale), *grads, 0 if dkl is None else dkl.data_ptr(),
                                                        ws.data_ptr(), ws.numel(), _raw_stream(gloss.device.index)),
                "gpsa_elbo_loss_weighted_bwd")
 

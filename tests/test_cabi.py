@@ -41,6 +41,27 @@ def test_workspace_queries_are_pure():
     assert lib.gpsa_quadform_workspace(0, 200, 1000, 50) >= 50 * 208 * 208 * 4
 
 
+def test_loss_workspace_size_is_what_the_c_entries_ask_for():
+    """torch_ops.loss_workspace_bytes restates csrc's per-term slot: the entries take that size (less its 64 spare bytes)
+    and refuse 8 bytes less.  No launch: with S[0] = 0 an entry that accepts the workspace returns GPSA_EINVAL."""
+    import ctypes as C
+
+    from spatial_alignment_amd import torch_ops
+
+    lib = _lib.load()
+    for n in (1, 3):
+        buf = (C.c_double * 4)()
+        ptrs = (C.c_void_p * n)(*[C.addressof(buf)] * n)
+        S, N, P = (C.c_int * n)(*[0] * n), (C.c_longlong * n)(*[1] * n), (C.c_int * n)(*[1] * n)
+        need = torch_ops.loss_workspace_bytes(n) - 64
+        for nbytes, want in ((need, _lib.GPSA_EINVAL), (need - 8, _lib.GPSA_EWORKSPACE)):
+            a = (n, ptrs, ptrs, ptrs, S, N, P)
+            out = (C.addressof(buf), C.addressof(buf), C.addressof(buf), nbytes, None)
+            assert lib.gpsa_elbo_loss_fwd(*a, None, 0, 1.0, *out) == want
+            assert lib.gpsa_elbo_loss_fused_fwd(*a, ptrs, 1, None, 0, 1.0, *out) == want
+            assert lib.gpsa_elbo_loss_weighted_fwd(*a, S, ptrs, ptrs, None, 0, 1.0, *out) == want
+
+
 def test_library_is_stamped_with_its_sources():
     """the library carries the sha256 of the sources it was built from; load() refuses another one"""
     lib = _lib.load()
