@@ -285,6 +285,8 @@ int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* co
   using namespace gpsa;
   if (!n_views || !view_off || !w || !loss || !ll_out) return GPSA_EINVAL;
   if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  for (int i = 0; i < n_ll; ++i)
+    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
   hipStream_t st = as_stream(stream);
   WeightedFinishArgs a = {};
   a.n_ll = n_ll;
@@ -294,7 +296,6 @@ int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* co
   a.ll = ll_out;
   a.loss = loss;
   for (int i = 0; i < n_ll; ++i) {
-    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
     ViewRows vr;
     for (int v = 0; v <= n_views[i]; ++v) vr.off[v] = view_off[i][v];
     const int nb = loglik_w_blocks(S[i], view_off[i], n_views[i], P[i]);
@@ -320,9 +321,10 @@ int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* co
   using namespace gpsa;
   if (!n_views || !view_off || !w || !gloss || !dF || !dnoise) return GPSA_EINVAL;
   if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  for (int i = 0; i < n_ll; ++i)
+    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
   hipStream_t st = as_stream(stream);
   for (int i = 0; i < n_ll; ++i) {
-    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
     ViewRows vr;
     for (int v = 0; v <= n_views[i]; ++v) vr.off[v] = view_off[i][v];
     const int nb = loglik_w_blocks(S[i], view_off[i], n_views[i], P[i]);

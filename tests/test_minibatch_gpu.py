@@ -50,9 +50,11 @@ def _host(MB, n_views, Ns, Bs, seed, t):
     return out
 
 
-CASES = [  # (views per modality, N per (m, v), B per (m, v)): B does not divide N, B = N, N = 1, two modalities
-    ([5], [1, 7, 600, 1000, 37], [1, 3, 200, 1000, 5]),
-    ([2, 3], [64, 129, 10, 11, 4099], [16, 128, 10, 2, 700]),
+CASES = [  # (views per modality, N per (m, v), B per (m, v), P per modality, D): B does not divide N, B = N, N = 1, two
+    # modalities; rows wider than a wave (the lanes' p += 64 / d += 64 loops take a second and a third trip)
+    ([5], [1, 7, 600, 1000, 37], [1, 3, 200, 1000, 5], (5,), 2),
+    ([2, 3], [64, 129, 10, 11, 4099], [16, 128, 10, 2, 700], (5, 3), 2),
+    ([2, 3], [64, 129, 10, 11, 300], [16, 128, 10, 2, 70], (130, 65), 3),
 ]
 
 
@@ -60,9 +62,8 @@ CASES = [  # (views per modality, N per (m, v), B per (m, v)): B does not divide
 @pytest.mark.parametrize("seed", [0, 2**62 + 7])
 def test_sampler_matches_host_mirror(case, seed):
     MB = _lib()
-    n_views, Ns, Bs = CASES[case]
-    P = (5, 3)[: len(n_views)]
-    Xs, Ys, rows, Xb, Yb, counter = _gather_case(n_views, Ns, Bs, P=P)
+    n_views, Ns, Bs, P, D = CASES[case]
+    Xs, Ys, rows, Xb, Yb, counter = _gather_case(n_views, Ns, Bs, P=P, D=D)
     starts = list(range(16)) + [10**9 + 5]  # several epochs of every view, and a far step
     for t in starts:
         counter.fill_(t)
@@ -78,9 +79,9 @@ def test_sampler_matches_host_mirror(case, seed):
 
 def test_sampler_under_graph_capture():
     MB = _lib()
-    n_views, Ns, Bs = CASES[1]
+    n_views, Ns, Bs, P, D = CASES[1]
     seed, t0, R = 99, 5, 7
-    Xs, Ys, rows, Xb, Yb, counter = _gather_case(n_views, Ns, Bs, P=(5, 3))
+    Xs, Ys, rows, Xb, Yb, counter = _gather_case(n_views, Ns, Bs, P=P, D=D)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -99,6 +100,48 @@ def test_sampler_under_graph_capture():
             assert np.array_equal(rows[m].cpu().numpy(), want[m]), (r, m)
             assert torch.equal(Yb[m], Ys[m][rows[m]])
     assert int(counter.item()) == t0 + R
+
+
+def _segment_case(n_views):
+    """small views, N = 1 and N = 2 among them, 1 <= B <= N"""
+    n = sum(n_views)
+    Ns = [1, 2] + [3 + (5 * i) % 11 for i in range(n - 2)]
+    Bs = [1, 1] + [1 + (3 * i) % N for i, N in enumerate(Ns[2:])]
+    assert all(1 <= b <= N for b, N in zip(Bs, Ns)) and any(b == N for b, N in zip(Bs[2:], Ns[2:]))
+    return Ns, Bs
+
+
+def test_sampler_with_a_full_segment_table():
+    """64 (modality, view) segments, all the table holds"""
+    MB = _lib()
+    n_views, seed = [33, 31], 12345
+    Ns, Bs = _segment_case(n_views)
+    Xs, Ys, rows, Xb, Yb, counter = _gather_case(n_views, Ns, Bs, P=(5, 3))
+    for t in (0, 1, 17):
+        counter.fill_(t)
+        torch.ops.gpsa.row_sample_gather(Xs, Ys, n_views, Ns, Bs, seed, counter, rows, Xb, Yb)
+        want = _host(MB, n_views, Ns, Bs, seed, t)
+        assert int(counter.item()) == t + 1
+        for m in range(2):
+            assert np.array_equal(rows[m].cpu().numpy(), want[m]), (t, m)
+            assert torch.equal(Xb[m], Xs[m][rows[m]]) and torch.equal(Yb[m], Ys[m][rows[m]])
+
+
+def test_sampler_refuses_a_65th_segment():
+    """... and one more is refused before anything is launched: rows / Xb / Yb keep their fill, the counter its step"""
+    _lib()
+    from spatial_alignment_amd._lib import GpsaHipError
+
+    n_views = [33, 32]
+    Ns, Bs = _segment_case(n_views)
+    Xs, Ys, rows, Xb, Yb, counter = _gather_case(n_views, Ns, Bs, P=(5, 3))
+    counter.fill_(17)
+    with pytest.raises(GpsaHipError, match="unsupported size"):
+        torch.ops.gpsa.row_sample_gather(Xs, Ys, n_views, Ns, Bs, 12345, counter, rows, Xb, Yb)
+    torch.cuda.synchronize()
+    assert int(counter.item()) == 17
+    for m in range(2):
+        assert bool((rows[m] == -1).all()) and bool(torch.isnan(Xb[m]).all()) and bool(torch.isnan(Yb[m]).all())
 
 
 def _weighted_inputs():
@@ -168,27 +211,46 @@ def test_weighted_likelihood_kernels():
     assert _rel(dkl, rdkl) <= 1e-12
 
 
+# one term each: views of very unequal length (9 blocks per view, all but one of them past the end of the two short
+# views); 64 views, two of them empty, one that takes a second grid-stride sweep behind the 4096 / 64 block cap
+UNEQUAL_VIEWS = (2, 3, [1, 1500, 20])  # S, P, rows per view
+MANY_VIEWS = (3, 33, [0] + [i * 7 % 5 + 1 for i in range(30)] + [0] + [700] + [i * 3 % 5 + 1 for i in range(31)])
+
+
+def _one_term_inputs(S, P, views):
+    gen = torch.Generator().manual_seed(6)
+    N = sum(views)
+    Fs, Ys = [torch.randn(S, N, P, generator=gen)], [torch.randn(N, P, generator=gen)]
+    ws = [torch.rand(len(views), generator=gen, dtype=torch.float64) * 3 + 0.5]
+    _, _, noise, _, _, kl = _weighted_inputs()
+    return Fs, Ys, noise, [views], ws, kl
+
+
 def test_unit_weights_equal_the_unweighted_kernels():
     _lib()
-    Fs, Ys, noise, views, ws, kl = _weighted_inputs()
-    ones = [torch.ones_like(w) for w in ws]
-    idx, ks, gl = [2, 3], 0.7, 1.3
-    loss, ll, dF, dn, dkl = _run_weighted(Fs, Ys, noise, views, ones, kl, ks, gl, idx)
-    d = lambda t: t.to(DEV).contiguous()
-    Fd, Yd, nd, kd = [d(f) for f in Fs], [d(y) for y in Ys], d(noise), d(kl)
-    l2 = torch.empty(1, device=DEV)
-    ll2 = torch.empty(2, dtype=torch.float64, device=DEV)
-    work = torch.empty(8 * 4100 * 2 + 64, dtype=torch.uint8, device=DEV)
-    torch.ops.gpsa.elbo_loss_fwd(Fd, Yd, nd, idx, kd, ks, l2, ll2, work)
-    dF2 = [torch.empty_like(f) for f in Fd]
-    dn2 = torch.empty(4, device=DEV)
-    dkl2 = torch.empty(7, dtype=torch.float64, device=DEV)
-    torch.ops.gpsa.elbo_loss_bwd(Fd, Yd, nd, idx, torch.tensor([gl], device=DEV), 7, ks, dF2, dn2, dkl2, work)
-    assert abs(loss - float(l2)) <= 1e-6 * abs(float(l2))
-    assert _rel(ll, ll2) <= 1e-9
-    for a, b in zip(dF, dF2):
-        assert torch.equal(a, b.cpu())  # same per-element arithmetic
-    assert _rel(dn, dn2) <= 1e-6 and torch.equal(dkl, dkl2.cpu())
+    assert len(MANY_VIEWS[2]) == 64
+    for inputs, idx in [(_weighted_inputs(), [2, 3]), (_one_term_inputs(*UNEQUAL_VIEWS), [2]),
+                        (_one_term_inputs(*MANY_VIEWS), [3])]:
+        Fs, Ys, noise, views, ws, kl = inputs
+        ones = [torch.ones_like(w) for w in ws]
+        ks, gl = 0.7, 1.3
+        loss, ll, dF, dn, dkl = _run_weighted(Fs, Ys, noise, views, ones, kl, ks, gl, idx)
+        d = lambda t: t.to(DEV).contiguous()
+        Fd, Yd, nd, kd = [d(f) for f in Fs], [d(y) for y in Ys], d(noise), d(kl)
+        l2 = torch.empty(1, device=DEV)
+        ll2 = torch.empty(len(Fs), dtype=torch.float64, device=DEV)
+        work = torch.empty(8 * 4100 * 2 + 64, dtype=torch.uint8, device=DEV)
+        torch.ops.gpsa.elbo_loss_fwd(Fd, Yd, nd, idx, kd, ks, l2, ll2, work)
+        dF2 = [torch.empty_like(f) for f in Fd]
+        dn2 = torch.empty(4, device=DEV)
+        dkl2 = torch.empty(7, dtype=torch.float64, device=DEV)
+        torch.ops.gpsa.elbo_loss_bwd(Fd, Yd, nd, idx, torch.tensor([gl], device=DEV), 7, ks, dF2, dn2, dkl2, work)
+        print(f"[unit weights] {len(views[0])} views: ll rel {_rel(ll, ll2):.3g}, dnoise rel {_rel(dn, dn2):.3g}")
+        assert abs(loss - float(l2)) <= 1e-6 * abs(float(l2))
+        assert _rel(ll, ll2) <= 1e-9
+        for a, b in zip(dF, dF2):
+            assert torch.equal(a, b.cpu())  # same per-element arithmetic
+        assert _rel(dn, dn2) <= 1e-6 and torch.equal(dkl, dkl2.cpu())
 
 
 # ---- the model ----------------------------------------------------------------------------------------------------
