@@ -4,6 +4,13 @@
 // The declarations CARRY the launch bounds: an instantiation takes its attributes from the first declaration, and
 // without them here every kernel was built for 1024 threads - 128 registers, the accumulators in scratch, 4.7x slower
 // (tests/test_cabi.py::test_kernel_resources now reads the code objects' metadata).
+//
+// A register-resident family's instantiated shapes are ONE list here, GPSA_*_SHAPES(X): the ``extern template``
+// declarations, the definitions in the family's unit, the launchers' ``switch`` in quadform.hip and the *_nct_for /
+// gram_max_nl look-ups the workspace queries use are all generated from it - a shape is added or removed on its line
+// of the list and nowhere else.  Workgroups per CU are constexpr functions (panel_wgs_per_cu, elbo_wgs_per_cu) read by
+// the kernels' __launch_bounds__ and by the launchers' grids.  Workspaces are laid out in quadform.hip ("workspace
+// layouts": one struct of offsets + total per entry point, used by its query and by its launcher).
 #pragma once
 #include <stdlib.h>
 
@@ -285,9 +292,17 @@ extern template __global__ void big_quad_kernel<false, true, 3>(BigQuadArgs);
 extern template __global__ void big_accum_kernel<3>(BigAccumArgs);
 extern template __global__ void gram_big_reduce_kernel<float>(const float* __restrict__, int, int, float* __restrict__);
 
+// workgroups per CU of the persistent kernels (by the registers of one wave: accumulators + alpha slab ~ MB * NCT): the
+// kernel's __launch_bounds__ and its launcher's grid both read these
+constexpr int panel_wgs_per_cu(int MB, int NCT) { return (MB * NCT >= 24) ? 1 : 2; }
+constexpr int elbo_wgs_per_cu(int MB, int NCT) { return (MB * NCT >= 14) ? 1 : 2; }
+// body of a look-up over a GPSA_*_SHAPES list: the second entry (NCT / NL) of row tile count ``mb``
+#define GPSA_SHAPE_SECOND(MB, SECOND, ...) \
+  if (mb == MB) return SECOND;
+
 // ---- register-resident panel kernels (M <= 512): qf_panel_quad.hip / qf_panel_accum.hip / qf_panel_store.hip
 template <int MB, int NCT, int MODE, int RL>
-__global__ void __launch_bounds__(256, (MB * NCT >= 24) ? 1 : 2) panel_mfma_kernel(const float* __restrict__ Ppk, const float* __restrict__ X, const float* __restrict__ g, int M, long long C, int L, float* __restrict__ out, float* __restrict__ colsq, float out_scale, float* __restrict__ slab, float* __restrict__ keep);
+__global__ void __launch_bounds__(256, panel_wgs_per_cu(MB, NCT)) panel_mfma_kernel(const float* __restrict__ Ppk, const float* __restrict__ X, const float* __restrict__ g, int M, long long C, int L, float* __restrict__ out, float* __restrict__ colsq, float out_scale, float* __restrict__ slab, float* __restrict__ keep);
 #define GPSA_PANEL_SIG (const float* __restrict__ Ppk, const float* __restrict__ X, const float* __restrict__ g, int M, long long C, int L, float* __restrict__ out, float* __restrict__ colsq, float out_scale, float* __restrict__ slab, float* __restrict__ keep)
 #define GPSA_PANEL_SHAPES(X, MODE) X(2, 4, MODE) X(4, 4, MODE) X(7, 4, MODE) X(13, 3, MODE) X(16, 2, MODE)
 #define GPSA_PANEL_SHAPES_BIG(X, MODE) X(24, 1, MODE) X(32, 1, MODE)  // accumulate only; one unit per instantiation:
@@ -302,6 +317,12 @@ GPSA_PANEL_SHAPES(GPSA_PANEL_EXTERN, MODE_QUAD)
 GPSA_PANEL_SHAPES(GPSA_PANEL_EXTERN, MODE_STORE)
 GPSA_PANEL_SHAPES(GPSA_PANEL_EXTERN, MODE_ACCUM)
 GPSA_PANEL_SHAPES_BIG(GPSA_PANEL_EXTERN, MODE_ACCUM)
+// column tiles per wave of the panel kernels (and of kept_wsum_kernel, which reads their kept products); 0: no such shape
+constexpr int panel_nct_for(int mb) {
+  GPSA_PANEL_SHAPES(GPSA_SHAPE_SECOND, 0)
+  GPSA_PANEL_SHAPES_BIG(GPSA_SHAPE_SECOND, 0)
+  return 0;
+}
 
 // ---- forward + likelihood + abar in one pass: qf_elbo.hip
 struct ElboArgs {
@@ -328,8 +349,9 @@ struct ElboArgs {
 };
 
 template <int MB, int NCT, int RL, bool FULLT = false, bool PAIRB = false>
-__global__ void __launch_bounds__(256, (MB * NCT >= 14) ? 1 : 2) panel_elbo_kernel(ElboArgs a);
-#define GPSA_ELBO_SHAPES(X) X(2, 4) X(4, 4) X(7, 4) X(13, 2) X(13, 1) X(16, 2)
+__global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT)) panel_elbo_kernel(ElboArgs a);
+// (13 row tiles: one wave per SIMD with 32 columns; 16 row tiles, M <= 256: 3 x 128 registers + the working set)
+#define GPSA_ELBO_SHAPES(X) X(2, 4) X(4, 4) X(7, 4) X(13, 2) X(16, 2)
 #define GPSA_ELBO_EXTERN(MB, NCT)                                          \
   extern template __global__ void panel_elbo_kernel<MB, NCT, 2>(ElboArgs); \
   extern template __global__ void panel_elbo_kernel<MB, NCT, 4>(ElboArgs);
@@ -337,21 +359,29 @@ __global__ void __launch_bounds__(256, (MB * NCT >= 14) ? 1 : 2) panel_elbo_kern
   template __global__ void panel_elbo_kernel<MB, NCT, 2>(ElboArgs); \
   template __global__ void panel_elbo_kernel<MB, NCT, 4>(ElboArgs);
 GPSA_ELBO_SHAPES(GPSA_ELBO_EXTERN)
-// M > 16 (MB - 1) (every row tile but the last inside the matrix), the 13-tile shape: the headline configuration's
-extern template __global__ void panel_elbo_kernel<13, 2, 2, true>(ElboArgs);
-extern template __global__ void panel_elbo_kernel<13, 2, 4, true>(ElboArgs);
-// ... with one barrier per two K chunks (qf_elbo.hip: PAIRB)
+constexpr int elbo_nct_for(int mb) {
+  GPSA_ELBO_SHAPES(GPSA_SHAPE_SECOND)
+  return 0;
+}
+// M > 16 (MB - 1) (every row tile but the last inside the matrix), the 13-tile shape: the headline configuration's,
+// with one barrier per two K chunks (qf_elbo.hip: PAIRB)
 extern template __global__ void panel_elbo_kernel<13, 2, 2, true, true>(ElboArgs);
 extern template __global__ void panel_elbo_kernel<13, 2, 4, true, true>(ElboArgs);
 
 // the same pass with the contraction on the bf16 matrix instructions in three pieces (qf_x3.hip; gpsa_step_desc.contraction
 // = 1): Ppk is then pack_x3_kernel's three-plane bf16 image of Omega
+// (one workgroup per CU: the ring takes most of the LDS.  One column tile per wave at MB >= 13: at two, the alpha planes
+// (2 x 7 x 12) and the product's accumulators (104) do not fit the 256 arch VGPRs together and the allocator spills)
 template <int MB, int NCT>
 __global__ void __launch_bounds__(256, 1) panel_elbo_x3_kernel(ElboArgs a);
 #define GPSA_ELBO_X3_SHAPES(X) X(2, 2) X(4, 2) X(7, 2) X(13, 1) X(16, 1)
 #define GPSA_ELBO_X3_EXTERN(MB, NCT) extern template __global__ void panel_elbo_x3_kernel<MB, NCT>(ElboArgs);
 #define GPSA_ELBO_X3_DEFINE(MB, NCT) template __global__ void panel_elbo_x3_kernel<MB, NCT>(ElboArgs);
 GPSA_ELBO_X3_SHAPES(GPSA_ELBO_X3_EXTERN)
+constexpr int elbo_x3_nct_for(int mb) {
+  GPSA_ELBO_X3_SHAPES(GPSA_SHAPE_SECOND)
+  return 0;
+}
 template <typename TS>
 __global__ void __launch_bounds__(256) pack_x3_kernel(const TS* __restrict__ src, int M, int MB, int KB, int L,
                                                        unsigned short* __restrict__ dst, const float* __restrict__ drow);
@@ -362,7 +392,7 @@ extern template __global__ void pack_x3_kernel<double>(const double* __restrict_
 
 // ---- symmetric quadratic form: qf_sym.hip
 template <int MB, int NCT, int RL>
-__global__ void __launch_bounds__(256, (MB * NCT >= 24) ? 1 : 2) quad_sym_mfma_kernel(const float* __restrict__ Ppk, const float* __restrict__ X, int M, long long C, int L, float* __restrict__ out);
+__global__ void __launch_bounds__(256, panel_wgs_per_cu(MB, NCT)) quad_sym_mfma_kernel(const float* __restrict__ Ppk, const float* __restrict__ X, int M, long long C, int L, float* __restrict__ out);
 #define GPSA_SYM_SIG (const float* __restrict__ Ppk, const float* __restrict__ X, int M, long long C, int L, float* __restrict__ out)
 #define GPSA_SYM_SHAPES(X) X(2, 4) X(4, 4) X(7, 4) X(13, 3) X(16, 2) X(24, 1)
 #define GPSA_SYM_EXTERN(MB, NCT)                                                 \
@@ -420,6 +450,11 @@ struct GramPlan {
   template __global__ void gram_mfma_kernel<MB, true, NL> GPSA_GRAM_SIG; \
   template __global__ void gram_mfma_kernel<MB, false, NL> GPSA_GRAM_SIG;
 GPSA_GRAM_SHAPES(GPSA_GRAM_EXTERN)
+// the most outputs per workgroup (NL) a row tile count is instantiated for (the list has the larger NL first); 0: none
+constexpr int gram_max_nl(int mb) {
+  GPSA_GRAM_SHAPES(GPSA_SHAPE_SECOND)
+  return 0;
+}
 template <typename TO>
 __global__ void gram_reduce_kernel(const float* __restrict__ part, int M, int MP, int L, int nsplit, TO* __restrict__ out,
                                    float* __restrict__ ddelta, float dbeta);

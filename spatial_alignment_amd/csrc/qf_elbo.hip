@@ -26,7 +26,7 @@ namespace gpsa {
 // A chunk's pieces go to the slot of chunk c - 2, which every wave has finished before the barrier it has last
 // passed (at the end of chunk c - 1 or c - 2).
 template <int MB, int NCT, int RL, bool FULLT, bool PAIRB>
-__global__ void __launch_bounds__(256, (MB * NCT >= 14) ? 1 : 2) panel_elbo_kernel(ElboArgs a) {
+__global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT)) panel_elbo_kernel(ElboArgs a) {
   constexpr int MP = MB * 16;
   constexpr int WGCOLS = 64 * NCT;
   constexpr int CHUNK = MP * 16;
@@ -333,8 +333,6 @@ __global__ void __launch_bounds__(256, (MB * NCT >= 14) ? 1 : 2) panel_elbo_kern
 }
 
 GPSA_ELBO_SHAPES(GPSA_ELBO_DEFINE)
-template __global__ void panel_elbo_kernel<13, 2, 2, true>(ElboArgs);
-template __global__ void panel_elbo_kernel<13, 2, 4, true>(ElboArgs);
 template __global__ void panel_elbo_kernel<13, 2, 2, true, true>(ElboArgs);
 template __global__ void panel_elbo_kernel<13, 2, 4, true, true>(ElboArgs);
 

@@ -13,7 +13,7 @@ namespace gpsa {
 // RL: MFMA steps of the last K chunk that are issued (4, or 2 when M % 16 <= 8 leaves the rest padding;
 // ACCUM / STORE only, see PACK_KSTEP).
 template <int MB, int NCT, int MODE, int RL>
-__global__ void __launch_bounds__(256, (MB * NCT >= 24) ? 1 : 2)
+__global__ void __launch_bounds__(256, panel_wgs_per_cu(MB, NCT))
 panel_mfma_kernel(const float* __restrict__ Ppk,  // [L][MB][MP][16]
                   const float* __restrict__ X,    // [M][C]
                   const float* __restrict__ g,    // [L][C]   (ACCUM)

@@ -15,7 +15,7 @@ namespace gpsa {
 // slab, LDS-DMA staging, persistent balanced items and in-register closing as panel_mfma_kernel.
 // ------------------------------------------------------------------------------------------------
 template <int MB, int NCT, int RL>
-__global__ void __launch_bounds__(256, (MB * NCT >= 24) ? 1 : 2)
+__global__ void __launch_bounds__(256, panel_wgs_per_cu(MB, NCT))
 quad_sym_mfma_kernel(const float* __restrict__ Ppk,  // [L][MB][MB][256] PACK_SYM_UPPER-packed
                      const float* __restrict__ X, int M, long long C, int L,
                      float* __restrict__ out) {

@@ -478,7 +478,19 @@ static inline int gram_mb_for(int M) {
   return mb <= 16 ? mb : 0;
 }
 
-static inline int panel_nct_for(int MB) { return MB >= 24 ? 1 : (MB == 16 ? 2 : (MB == 13 ? 3 : 4)); }
+// The last row tile with at most 8 rows of the matrix runs the RL = 2 instantiations: they skip the all-padding K steps
+// of the last chunk, and so expect that chunk packed in K-step order.  Every launcher takes BOTH its RL template
+// argument and its pack layout from these two.
+constexpr int last_tile_rl(int M, int MB) { return (M - 16 * (MB - 1) <= 8) ? 2 : 4; }
+constexpr int last_chunk_layout(int M, int MB) { return last_tile_rl(M, MB) == 2 ? PACK_KSTEP_LAST : 0; }
+// row M is a padding row of the LAST row tile: the products' spare row that carries delta / d delta
+constexpr bool has_padding_row(int M, int MB) { return M > 16 * (MB - 1) && M < 16 * MB; }
+
+// workgroups of a persistent kernel: ``wgs_per_cu`` per CU, at most one per work item
+static inline long long persistent_grid(int wgs_per_cu, long long items) {
+  const long long grid = (long long)num_cus() * wgs_per_cu;
+  return grid < items ? grid : items;
+}
 
 static inline bool force_generic() {
   static int v = -1;
@@ -614,90 +626,104 @@ kept_wsum_kernel(const float* __restrict__ keep, const float* __restrict__ g, in
   }
 }
 
-template <int MODE>
-int panel_mfma_launch(int MBsel, const float* Ppk, const float* X, const float* g, int M,
-                      long long C, int L, float* out, float* colsq, float scale, float* slab,
-                      hipStream_t st, float* keep = nullptr) {
-#define GPSA_PANEL_CASE(MBV, NCTV)                                                              \
-  case MBV:                                                                                     \
-    if constexpr (MBV <= 16 || MODE == MODE_ACCUM) {  /* 24 / 32 row tiles: accumulate only */  \
-    const long long ntiles = cdiv(C, 64 * NCTV), T = ntiles * L;                                \
-    const int wgs_per_cu = (MBV * NCTV >= 24) ? 1 : 2;                                          \
-    long long grid = (long long)num_cus() * wgs_per_cu;                                         \
-    if (MODE == MODE_STORE) grid = T;              /* L == 1: one item per tile */              \
-    if (grid > T) grid = T;                                                                     \
-    constexpr int RLV = 2;  /* QUAD: the caller packs the last chunk in K-step order (PACK_KSTEP_LAST) */ \
-    if (RLV == 2 && M - 16 * (MBV - 1) <= 8)                                                    \
-      panel_mfma_kernel<MBV, NCTV, MODE, RLV><<<(unsigned)grid, 256, 0, st>>>(                  \
-          Ppk, X, g, M, C, L, out, colsq, scale, slab, keep);                                   \
-    else                                                                                        \
-      panel_mfma_kernel<MBV, NCTV, MODE, 4><<<(unsigned)grid, 256, 0, st>>>(                    \
-          Ppk, X, g, M, C, L, out, colsq, scale, slab, keep);                                   \
-    if (MODE == MODE_ACCUM) {                                                                   \
-      /* few tiles (a short column range): more blocks per tile, the reduce is latency-bound */ \
-      dim3 rg((unsigned)ntiles, ntiles >= 512 ? 8 : (ntiles >= 128 ? 16 : 32));               \
-      panel_slab_reduce_kernel<<<rg, 256, 0, st>>>(slab, M, MBV * 16, 64 * NCTV, C, L, ntiles,  \
-                                                   (int)grid, out);                             \
-    }                                                                                           \
-    } else {                                                                                    \
-      return GPSA_EUNSUPPORTED;                                                                 \
-    }                                                                                           \
-    break;
-  switch (MBsel) {
-    GPSA_PANEL_CASE(2, 4)
-    GPSA_PANEL_CASE(4, 4)
-    GPSA_PANEL_CASE(7, 4)
-    GPSA_PANEL_CASE(13, 3)
-    GPSA_PANEL_CASE(16, 2)
-    GPSA_PANEL_CASE(24, 1)
-    GPSA_PANEL_CASE(32, 1)
-    default:
-      return GPSA_EUNSUPPORTED;
-  }
-#undef GPSA_PANEL_CASE
+// floats of the partial-tile slabs of a persistent grid of G workgroups: 2 partial tiles each
+static inline long long slab_floats(long long G, int MB, int NCT) { return G * 2 * (long long)MB * 16 * 64 * NCT; }
+
+// out = the slabs' partial tiles added up (panel_slab_reduce_kernel), for the grid of G workgroups that wrote them
+static int slab_reduce_launch(const float* slab, int M, int MB, int NCT, long long C, int L, long long ntiles,
+                              long long G, float* out, hipStream_t st) {
+  // few tiles (a short column range): more blocks per tile, the reduce is latency-bound
+  dim3 rg((unsigned)ntiles, ntiles >= 512 ? 8 : (ntiles >= 128 ? 16 : 32));
+  panel_slab_reduce_kernel<<<rg, 256, 0, st>>>(slab, M, MB * 16, 64 * NCT, C, L, ntiles, (int)G, out);
   GPSA_LAUNCH_CHECK();
   return 0;
 }
 
-// floats of slab space behind the packed operand: 2 partial tiles per workgroup of the persistent grid
-static inline long long accum_slab_floats(int MB) {
-  const int nct = panel_nct_for(MB);
-  const long long G = (long long)num_cus() * ((MB * nct >= 24) ? 1 : 2);
-  return G * 2 * (long long)MB * 16 * 64 * nct;
+// The M x M operands (Omega_l, L^-1) may arrive in either precision: the MFMA paths convert while
+// packing, the generic paths take a converted copy from the head of the workspace.
+static int pack_any(int p_dtype, const void* src, int M, int MB, int L, int transpose, float* dst,
+                    hipStream_t st, int layout = 0, const float* drow = nullptr) {
+  const long long tot = (long long)L * MB * 16 * MB * 16;
+  const unsigned grid = (unsigned)cdiv(tot, 256);
+  if (p_dtype == GPSA_F32)
+    pack_panels_kernel<float><<<grid, 256, 0, st>>>((const float*)src, M, MB, L, transpose, dst, layout, drow);
+  else if (p_dtype == GPSA_F64)
+    pack_panels_kernel<double><<<grid, 256, 0, st>>>((const double*)src, M, MB, L, transpose, dst, layout, drow);
+  else
+    return GPSA_EINVAL;
+  GPSA_LAUNCH_CHECK();
+  return 0;
 }
 
-static int quad_sym_launch(int MBsel, const float* Ppk, const float* X, int M, long long C, int L,
-                           float* out, hipStream_t st) {
-#define GPSA_QS_CASE(MBV, NCTV)                                                                  \
-  case MBV: {                                                                                    \
-    const long long T = cdiv(C, 64 * NCTV) * L;                                                  \
-    long long grid = (long long)num_cus() * ((MBV * NCTV >= 24) ? 1 : 2);                        \
-    if (grid > T) grid = T;                                                                      \
-    if (M - 16 * (MBV - 1) <= 8)                                                                 \
-      quad_sym_mfma_kernel<MBV, NCTV, 2><<<(unsigned)grid, 256, 0, st>>>(Ppk, X, M, C, L, out);  \
-    else                                                                                         \
-      quad_sym_mfma_kernel<MBV, NCTV, 4><<<(unsigned)grid, 256, 0, st>>>(Ppk, X, M, C, L, out);  \
-  } break;
+template <int MB, int NCT, int MODE>
+static int panel_mfma_shape(const float* Ppk, const float* X, const float* g, int M, long long C, int L, float* out,
+                            float* colsq, float scale, float* slab, hipStream_t st, float* keep) {
+  const long long ntiles = cdiv(C, 64 * NCT), T = ntiles * L;
+  // (STORE, L == 1: one item per tile)
+  const long long grid = MODE == MODE_STORE ? T : persistent_grid(panel_wgs_per_cu(MB, NCT), T);
+  if (last_tile_rl(M, MB) == 2)
+    panel_mfma_kernel<MB, NCT, MODE, 2><<<(unsigned)grid, 256, 0, st>>>(Ppk, X, g, M, C, L, out, colsq, scale, slab, keep);
+  else
+    panel_mfma_kernel<MB, NCT, MODE, 4><<<(unsigned)grid, 256, 0, st>>>(Ppk, X, g, M, C, L, out, colsq, scale, slab, keep);
+  GPSA_LAUNCH_CHECK();
+  return MODE == MODE_ACCUM ? slab_reduce_launch(slab, M, MB, NCT, C, L, ntiles, grid, out, st) : 0;
+}
+
+// packs P ([L][M][M] of p_dtype, optionally transposed) into Ppk in the layout the mode's kernel reads - QUAD: the
+// interleaved order, the last chunk in K-step order where the RL = 2 kernel runs; ACCUM / STORE: K-step order
+// throughout - and launches that kernel
+template <int MODE>
+static int panel_mfma_launch(int MBsel, int p_dtype, const void* P, int transpose, float* Ppk, const float* X,
+                             const float* g, int M, long long C, int L, float* out, float* colsq, float scale,
+                             float* slab, hipStream_t st, float* keep = nullptr) {
+  const int rc = pack_any(p_dtype, P, M, MBsel, L, transpose, Ppk, st,
+                          MODE == MODE_QUAD ? last_chunk_layout(M, MBsel) : PACK_KSTEP);
+  if (rc) return rc;
+#define GPSA_PANEL_CASE(MBV, NCTV, MODEV) \
+  case MBV: return panel_mfma_shape<MBV, NCTV, MODEV>(Ppk, X, g, M, C, L, out, colsq, scale, slab, st, keep);
   switch (MBsel) {
-    GPSA_QS_CASE(2, 4)
-    GPSA_QS_CASE(4, 4)
-    GPSA_QS_CASE(7, 4)
-    GPSA_QS_CASE(13, 3)
-    GPSA_QS_CASE(16, 2)
-    GPSA_QS_CASE(24, 1)
-    default:
-      return GPSA_EUNSUPPORTED;
+    GPSA_PANEL_SHAPES(GPSA_PANEL_CASE, MODE)
+    default: break;
+  }
+  if constexpr (MODE == MODE_ACCUM)  // 24 / 32 row tiles: accumulate only
+    switch (MBsel) {
+      GPSA_PANEL_SHAPES_BIG(GPSA_PANEL_CASE, MODE)
+      default: break;
+    }
+#undef GPSA_PANEL_CASE
+  return GPSA_EUNSUPPORTED;
+}
+
+template <int MB, int NCT>
+static int quad_sym_shape(const float* Ppk, const float* X, int M, long long C, int L, float* out, hipStream_t st) {
+  const long long grid = persistent_grid(panel_wgs_per_cu(MB, NCT), cdiv(C, 64 * NCT) * L);
+  if (last_tile_rl(M, MB) == 2)
+    quad_sym_mfma_kernel<MB, NCT, 2><<<(unsigned)grid, 256, 0, st>>>(Ppk, X, M, C, L, out);
+  else
+    quad_sym_mfma_kernel<MB, NCT, 4><<<(unsigned)grid, 256, 0, st>>>(Ppk, X, M, C, L, out);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+// packs Omega as the symmetric form's operand (into Ppk) and launches quad_sym_mfma_kernel
+static int quad_sym_launch(int MBsel, int omega_dtype, const void* Omega, float* Ppk, const float* X, int M, long long C,
+                           int L, float* out, hipStream_t st) {
+  const int rc = pack_any(omega_dtype, Omega, M, MBsel, L, 0, Ppk, st, PACK_SYM_UPPER | last_chunk_layout(M, MBsel));
+  if (rc) return rc;
+#define GPSA_QS_CASE(MBV, NCTV) \
+  case MBV: return quad_sym_shape<MBV, NCTV>(Ppk, X, M, C, L, out, st);
+  switch (MBsel) {
+    GPSA_SYM_SHAPES(GPSA_QS_CASE)
+    default: return GPSA_EUNSUPPORTED;
   }
 #undef GPSA_QS_CASE
-  GPSA_LAUNCH_CHECK();
-  return 0;
 }
 
-static inline int gram_nsplit(long long C, int L) {
+static inline int gram_nsplit(long long C, int L, int chunk) {
   // grid = L x nsplit workgroups, one per CU: ONE round of workgroups that (nearly) fills the chip beat
   // 2-4 rounds at every size measured (2.44 vs 2.52 ms at C = 100k, 0.34 vs 0.43 ms at C = 12.5k; L = 50):
   // fewer prologues, and a third of the partial sums for gram_reduce_kernel to add
-  const long long nch = cdiv(C, GR_KC);
+  const long long nch = cdiv(C, chunk);  // (GR_KC columns for gram_mfma_kernel, 32 for gram_x3_kernel)
   const int cus = num_cus();
   // W workgroups per output group fill the chip once; each takes c = ceil(nch / W) chunks.  (Few outputs -
   // the warp GPs' L = 2 - used to be held to >= 4 chunks per workgroup, i.e. 39 workgroups on 256 CUs at
@@ -720,27 +746,115 @@ __global__ void pad_rows_kernel(const float* __restrict__ g, int L, long long C,
   gpad[idx] = c < C ? g[l * C + c] : 0.f;
 }
 
-static inline long long gram_gpad_floats(long long C, int L) { return (long long)L * cdiv(C, GR_KC) * GR_KC; }
-
 // outputs per workgroup: two where the accumulators of both fit (MB <= 13), there are at least two, and
 // the column range is long enough for the saved staging to outweigh the doubled number of partial slabs
 // the reduce kernel adds (2.05 vs 2.28 ms at C = 100k, 0.28 vs 0.30 ms at C = 12.5k; L = 50)
 static inline int gram_nl(int MB, int L, long long C) {
-  const bool can = L >= 2 && MB <= 13;
+  const bool can = L >= 2 && gram_max_nl(MB) >= 2;
   return (can && C >= 8192) ? 2 : 1;
+}
+
+// panel_elbo_kernel for one shape of GPSA_ELBO_SHAPES
+template <int MB, int NCT>
+static void elbo_shape(const ElboArgs& a, unsigned grid, hipStream_t st) {
+  // the 13-tile shape with every row tile but the last inside the matrix (the headline configuration): the
+  // instantiation without row clamps and with one barrier per two K chunks
+  constexpr bool HEAD = MB == 13 && NCT == 2;
+  const bool rl2 = last_tile_rl(a.M, MB) == 2;
+  if (HEAD && a.M > 16 * (MB - 1)) {
+    if (rl2) panel_elbo_kernel<MB, NCT, 2, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
+    else panel_elbo_kernel<MB, NCT, 4, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
+  } else {
+    if (rl2) panel_elbo_kernel<MB, NCT, 2><<<grid, 256, 0, st>>>(a);
+    else panel_elbo_kernel<MB, NCT, 4><<<grid, 256, 0, st>>>(a);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// workspace layouts: byte offsets and the total of every workspace an MFMA entry point carves, each computed by ONE
+// function of the shape.  The *_workspace query returns ``total``; the launcher takes its pointers from the offsets.
+// ------------------------------------------------------------------------------------------------
+static inline long long packed_bytes(int MB, int L) { return (long long)L * MB * 16 * MB * 16 * 4; }
+
+// [packed operand | partial-tile slabs | ring slack]: the persistent panel kernels
+struct PanelWs {
+  long long slab;        // offset of the slabs (= end of the packed operand)
+  long long ring_slack;  // bytes behind everything else that the staging ring may request and never multiplies
+  long long total;
+};
+// gpsa_quadform_bwd_alpha's ACCUM path: the slabs of panel_mfma_kernel<ACCUM>'s own grid
+static inline PanelWs accum_ws(int MB, int L) {
+  const int nct = panel_nct_for(MB);
+  const long long pk = packed_bytes(MB, L);
+  return {pk, 0, pk + slab_floats((long long)num_cus() * panel_wgs_per_cu(MB, nct), MB, nct) * 4};
+}
+// gpsa_quadform_fwd_keep_f32 (MB <= 16): no slabs, and four chunks of slack behind the packed operand (round 6): the
+// staging ring of the panel kernels keeps requesting chunks behind a workgroup's last one until its loop ends (values
+// it never multiplies); for the workgroup that owns the LAST chunk those requests used to leave the workspace - a
+// device fault when the workspace happened to end at a mapping boundary (found by tools/fuzz_kernels.py through the raw
+// C ABI; inside the step engine the bytes behind it were the arena's own).  The sibling workspaces have their slabs there.
+static inline PanelWs keep_ws(int MB, int L) {
+  const long long pk = packed_bytes(MB, L), slack = 4LL * MB * 16 * 16 * 4;
+  return {pk, slack, pk + slack};
+}
+// gpsa_quadform_elbo_f32 / _x3_f32 (total 0: no fused kernel for this shape).  fp32: slabs for two workgroups per CU,
+// whatever the shape's own grid (gpsa_quadform_elbo_parts).  x3: the packed operand is pack_x3_kernel's three-plane bf16
+// image, one workgroup per CU, and two chunks of slack for the ring stages that walk past the last chunk.
+static inline long long elbo_x3_pack_bytes(int MB, int L) {
+  return (((long long)L * ((MB + 1) / 2) * MB * 3 * 1024) + 255) / 256 * 256;
+}
+static inline PanelWs elbo_ws(bool x3, int MB, int L) {
+  if (x3) {
+    const long long pk = elbo_x3_pack_bytes(MB, L), slack = 2LL * MB * 3 * 1024;
+    return {pk, slack, pk + slab_floats(num_cus(), MB, elbo_x3_nct_for(MB)) * 4 + slack};
+  }
+  const long long pk = packed_bytes(MB, L);
+  return {pk, 0, pk + slab_floats(2LL * num_cus(), MB, elbo_nct_for(MB)) * 4};
+}
+
+// [g zero-padded to whole chunks, or alpha's bf16 image | partial sums [L][nsplit][MP][MP]]: the Gram kernels
+struct GramWs {
+  int nl, nsplit;  // outputs per workgroup, workgroups per output group
+  long long part;  // offset of the partial sums
+  long long total;
+};
+static inline long long gram_gpad_floats(long long C, int L) { return (long long)L * cdiv(C, GR_KC) * GR_KC; }
+static inline GramWs gram_ws(int MB, long long C, int L) {
+  const int nl = gram_nl(MB, L, C), ns = gram_nsplit(C, (L + nl - 1) / nl, GR_KC);
+  const long long part = ((gram_gpad_floats(C, L) + 63) / 64) * 64 * 4;
+  return {nl, ns, part, part + (long long)L * ns * MB * 16 * MB * 16 * 4};
+}
+static inline GramWs gram_x3_ws(int MB, long long C, int L) {
+  const int ns = gram_nsplit(C, L, 32);
+  const long long part = cdiv(C, 32) * MB * 3 * 1024;
+  return {1, ns, part, part + (long long)L * ns * MB * 16 * MB * 16 * 4};
+}
+
+// dOmega (and, with ddelta, row M of the partial sums into d delta) = the nsplit partial sums added up
+static int gram_reduce_launch(const float* part, int M, int MB, int L, int ns, void* dOmega, int out_dtype, float* ddelta,
+                              float dbeta, hipStream_t st) {
+  dim3 rgrid((unsigned)cdiv(M, 32), (unsigned)cdiv(M + (ddelta != nullptr ? 1 : 0), 8), (unsigned)L);
+  if (out_dtype == GPSA_F64)
+    gram_reduce_kernel<double><<<rgrid, 256, 0, st>>>(part, M, MB * 16, L, ns, (double*)dOmega, ddelta, dbeta);
+  else
+    gram_reduce_kernel<float><<<rgrid, 256, 0, st>>>(part, M, MB * 16, L, ns, (float*)dOmega, ddelta, dbeta);
+  GPSA_LAUNCH_CHECK();
+  return 0;
 }
 
 // dmean / ddelta (both or neither; the d-delta option of gram_mfma_kernel): ddelta [M][L] = dbeta ddelta + alpha dmean^T
 // out of the first padding row of the LAST tile row; the caller has checked gram_delta_ok
 static int gram_mfma_launch(int MBsel, const float* alpha, const float* g, int M, long long C, int L,
-                            void* dOmega, int out_dtype, float* ws, hipStream_t st, const float* dmean = nullptr,
-                            float* ddelta = nullptr, float dbeta = 0.f) {
-  const int nl = gram_nl(MBsel, L, C);
-  const int ns = gram_nsplit(C, (L + nl - 1) / nl);
+                            void* dOmega, int out_dtype, void* workspace, long long workspace_bytes, hipStream_t st,
+                            const float* dmean = nullptr, float* ddelta = nullptr, float dbeta = 0.f) {
+  const GramWs lay = gram_ws(MBsel, C, L);
+  if (workspace_bytes < lay.total) return GPSA_EWORKSPACE;
+  const int ns = lay.nsplit;
   const long long Cpad = cdiv(C, GR_KC) * GR_KC;
+  float* ws = (float*)workspace;
   const float* gpad = ws;
   long long gstride = Cpad;
-  float* part = ws + ((gram_gpad_floats(C, L) + 63) / 64) * 64;
+  float* part = (float*)((char*)workspace + lay.part);
   const bool al = (C % 4 == 0) && (C >= 8) && ((reinterpret_cast<uintptr_t>(alpha) & 15) == 0);
   if (dmean != nullptr && !(al && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dmean)) & 15) == 0))
     return GPSA_EUNSUPPORTED;
@@ -752,57 +866,20 @@ static int gram_mfma_launch(int MBsel, const float* alpha, const float* g, int M
     pad_rows_kernel<<<(unsigned)cdiv((long long)L * Cpad, 256), 256, 0, st>>>(g, L, C, Cpad, ws);
     GPSA_LAUNCH_CHECK();
   }
-  dim3 grid((unsigned)((L + nl - 1) / nl), (unsigned)ns);
-#define GPSA_GRAM_CASE(MBV)                                                                        \
-  case MBV:                                                                                        \
-    if (nl == 2 && MBV <= 13) {                                                                    \
-      if (al) gram_mfma_kernel<MBV, true, (MBV <= 13 ? 2 : 1)><<<grid, 256, 0, st>>>(alpha, gpad, gstride, M, C, L, ns, part, dmean);  \
-      else gram_mfma_kernel<MBV, false, (MBV <= 13 ? 2 : 1)><<<grid, 256, 0, st>>>(alpha, gpad, gstride, M, C, L, ns, part, nullptr);    \
-    } else {                                                                                       \
-      if (al) gram_mfma_kernel<MBV, true, 1><<<grid, 256, 0, st>>>(alpha, gpad, gstride, M, C, L, ns, part, dmean); \
-      else gram_mfma_kernel<MBV, false, 1><<<grid, 256, 0, st>>>(alpha, gpad, gstride, M, C, L, ns, part, nullptr);   \
-    }                                                                                              \
+  dim3 grid((unsigned)((L + lay.nl - 1) / lay.nl), (unsigned)ns);
+#define GPSA_GRAM_CASE(MBV, NLV)                                                                                      \
+  case MBV * 8 + NLV:                                                                                                 \
+    if (al) gram_mfma_kernel<MBV, true, NLV><<<grid, 256, 0, st>>>(alpha, gpad, gstride, M, C, L, ns, part, dmean);   \
+    else gram_mfma_kernel<MBV, false, NLV><<<grid, 256, 0, st>>>(alpha, gpad, gstride, M, C, L, ns, part, nullptr);   \
     break;
-  switch (MBsel) {
-    GPSA_GRAM_CASE(2)
-    GPSA_GRAM_CASE(4)
-    GPSA_GRAM_CASE(7)
-    GPSA_GRAM_CASE(13)
-    GPSA_GRAM_CASE(16)
+  switch (MBsel * 8 + lay.nl) {
+    GPSA_GRAM_SHAPES(GPSA_GRAM_CASE)
     default:
       return GPSA_EUNSUPPORTED;
   }
 #undef GPSA_GRAM_CASE
   GPSA_LAUNCH_CHECK();
-  dim3 rgrid((unsigned)cdiv(M, 32), (unsigned)cdiv(M + (ddelta != nullptr ? 1 : 0), 8), (unsigned)L);
-  if (out_dtype == GPSA_F64)
-    gram_reduce_kernel<double><<<rgrid, 256, 0, st>>>(part, M, MBsel * 16, L, ns, (double*)dOmega, ddelta, dbeta);
-  else
-    gram_reduce_kernel<float><<<rgrid, 256, 0, st>>>(part, M, MBsel * 16, L, ns, (float*)dOmega, ddelta, dbeta);
-  GPSA_LAUNCH_CHECK();
-  return 0;
-}
-
-static inline long long gram_ws_bytes(int MB, long long C, int L) {
-  const int nl = gram_nl(MB, L, C);
-  return (((gram_gpad_floats(C, L) + 63) / 64) * 64 +
-          (long long)L * gram_nsplit(C, (L + nl - 1) / nl) * MB * 16 * MB * 16) * 4;
-}
-
-// The M x M operands (Omega_l, L^-1) may arrive in either precision: the MFMA paths convert while
-// packing, the generic paths take a converted copy from the head of the workspace.
-static int pack_any(int p_dtype, const void* src, int M, int MB, int L, int transpose, float* dst,
-                    hipStream_t st, int layout = 0, const float* drow = nullptr) {
-  const long long tot = (long long)L * MB * 16 * MB * 16;
-  const unsigned grid = (unsigned)cdiv(tot, 256);
-  if (p_dtype == GPSA_F32)
-    pack_panels_kernel<float><<<grid, 256, 0, st>>>((const float*)src, M, MB, L, transpose, dst, layout, drow);
-  else if (p_dtype == GPSA_F64)
-    pack_panels_kernel<double><<<grid, 256, 0, st>>>((const double*)src, M, MB, L, transpose, dst, layout, drow);
-  else
-    return GPSA_EINVAL;
-  GPSA_LAUNCH_CHECK();
-  return 0;
+  return gram_reduce_launch(part, M, MBsel, L, ns, dOmega, out_dtype, ddelta, dbeta, st);
 }
 
 template <typename TS, typename TD>
@@ -924,8 +1001,8 @@ long long gpsa_quadform_workspace(int dtype, int M, long long C, int L) {
   const int MB = gpsa::mfma_mb_for(M);
   long long mfma = 0;
   if (dtype == GPSA_F32 && MB) {
-    mfma = ((long long)L * MB * 16 * MB * 16 + gpsa::accum_slab_floats(MB)) * 4;
-    const long long gw = gpsa::gram_mb_for(M) ? gpsa::gram_ws_bytes(MB, C, L) : 0;
+    mfma = gpsa::accum_ws(MB, L).total;
+    const long long gw = gpsa::gram_mb_for(M) ? gpsa::gram_ws(MB, C, L).total : 0;
     if (gw > mfma) mfma = gw;
   }
   int lc = L < 4 ? L : 4;
@@ -955,13 +1032,8 @@ int gpsa_quadform_fwd(int dtype, int omega_dtype, const void* alpha, const void*
   if (dtype == GPSA_F32) {
     const int MB = mfma_mb_for(M);
     if (MB && MB <= MB_MAX_QUAD && !force_generic()) {
-      if (workspace_bytes < (long long)L * MB * 16 * MB * 16 * 4) return GPSA_EWORKSPACE;
-      float* Ppk = (float*)workspace;
-      // (the last chunk goes in K-step order exactly when quad_sym_launch picks the step-skipping kernel)
-      const int sym = PACK_SYM_UPPER | ((M - 16 * (MB - 1) <= 8) ? PACK_KSTEP_LAST : 0);
-      int rc = pack_any(omega_dtype, Omega, M, MB, L, 0, Ppk, st, sym);
-      if (rc) return rc;
-      return quad_sym_launch(MB, Ppk, (const float*)alpha, M, C, L, (float*)v, st);
+      if (workspace_bytes < packed_bytes(MB, L)) return GPSA_EWORKSPACE;
+      return quad_sym_launch(MB, omega_dtype, Omega, (float*)workspace, (const float*)alpha, M, C, L, (float*)v, st);
     }
     if (big_wants_pad(M, C)) {  // unaligned column count: the same kernels on zero-padded copies
       const long long Cp = pad4(C);
@@ -1027,15 +1099,7 @@ static inline bool keep_mfma_path(int M) {
 
 long long gpsa_quadform_keep_f32_workspace(int M, int L) {
   if (M < 1 || L < 1) return 0;
-  if (keep_mfma_path(M)) {
-    const int MB = gpsa::mfma_mb_for(M);
-    // + four chunks of slack behind the packed operand (round 6): the staging ring of the panel kernels keeps
-    // requesting chunks behind a workgroup's last one until its loop ends (values it never multiplies); for the
-    // workgroup that owns the LAST chunk those requests used to leave the workspace - a device fault when the
-    // workspace happened to end at a mapping boundary (found by tools/fuzz_kernels.py through the raw C ABI; inside the
-    // step engine the bytes behind it were the arena's own).  The sibling workspaces have their slabs there.
-    return (long long)L * MB * 16 * MB * 16 * 4 + 4LL * MB * 16 * 16 * 4;
-  }
+  if (keep_mfma_path(M)) return gpsa::keep_ws(gpsa::mfma_mb_for(M), L).total;
   return (long long)L * M * ((M + 15) / 16 * 16) * 4 + 256;  // fp32 copy of Omega, contraction index padded to 16
 }
 
@@ -1059,12 +1123,8 @@ int gpsa_quadform_fwd_keep_f32(int omega_dtype, const float* alpha, const void* 
   if (workspace_bytes < gpsa_quadform_keep_f32_workspace(M, L)) return GPSA_EWORKSPACE;
   hipStream_t st = as_stream(stream);
   if (keep_mfma_path(M)) {
-    const int MB = mfma_mb_for(M);
-    float* Ppk = (float*)workspace;
-    const int klast = (M - 16 * (MB - 1) <= 8) ? PACK_KSTEP_LAST : 0;  // matches panel_mfma_launch's RL choice
-    int rc = pack_any(omega_dtype, Omega, M, MB, L, 0, Ppk, st, klast);
-    if (rc) return rc;
-    return panel_mfma_launch<MODE_QUAD>(MB, Ppk, alpha, nullptr, M, C, L, v, nullptr, 1.f, nullptr, st, W);
+    return panel_mfma_launch<MODE_QUAD>(mfma_mb_for(M), omega_dtype, Omega, 0, (float*)workspace, alpha, nullptr, M, C, L, v,
+                                        nullptr, 1.f, nullptr, st, W);
   }
   if (C > 0x7fffffffLL) return GPSA_EINVAL;
   {
@@ -1124,13 +1184,7 @@ int gpsa_quadform_fwd_keep_f32(int omega_dtype, const float* alpha, const void* 
   return 0;
 }
 
-/* ---- forward + likelihood + abar in one pass (panel_elbo_kernel) ------------------------------------------ */
-// MB = 13: one wave per SIMD with 32 columns (NCT = 2), or - GPSA_ELBO_NCT=1 - two workgroups per CU with 16 columns per
-// wave and half the register file each (the other wave's MFMAs fill the matrix pipe during a wave's closing and ring issues)
-static inline int elbo_nct_for(int MB) {
-  static const int nct13 = [] { const char* e = getenv("GPSA_ELBO_NCT"); return (e && e[0] == '1') ? 1 : 2; }();
-  return MB == 13 ? nct13 : (MB == 16 ? 2 : 4);  // (16 row tiles, M <= 256: 3 x 128 registers + the working set)
-}
+/* ---- forward + likelihood + abar in one pass (panel_elbo_kernel; x3: panel_elbo_x3_kernel, qf_x3.hip) ------------ */
 static inline bool elbo_path(int M) {
   const int MB = gpsa::mfma_mb_for(M);
   return MB && MB <= 16 && !gpsa::force_generic();
@@ -1138,22 +1192,20 @@ static inline bool elbo_path(int M) {
 
 int gpsa_quadform_elbo_parts(void) { return gpsa::num_cus() * 2; }
 
-long long gpsa_quadform_elbo_f32_workspace(int M, long long C, int L) {
+static long long elbo_workspace(bool x3, int M, long long C, int L) {
   if (M < 1 || C < 1 || L < 1 || !elbo_path(M) || C > GPSA_PANEL_MAX_C) return 0;
-  const int MB = gpsa::mfma_mb_for(M), nct = elbo_nct_for(MB);
-  const long long G = gpsa_quadform_elbo_parts();
-  return ((long long)L * MB * 16 * MB * 16 + G * 2 * (long long)MB * 16 * 64 * nct) * 4;
+  return gpsa::elbo_ws(x3, gpsa::mfma_mb_for(M), L).total;
 }
+long long gpsa_quadform_elbo_f32_workspace(int M, long long C, int L) { return elbo_workspace(false, M, C, L); }
+long long gpsa_quadform_elbo_x3_f32_workspace(int M, long long C, int L) { return elbo_workspace(true, M, C, L); }
 
 // the mean can ride in the product's first padding row (gpsa_quadform_elbo_delta_f32) when row M lies in the LAST row tile
-static inline bool elbo_delta_ok(int M) {
-  const int MB = gpsa::mfma_mb_for(M);
-  return elbo_path(M) && M > 16 * (MB - 1) && M < 16 * MB;
-}
+static inline bool elbo_delta_ok(int M) { return elbo_path(M) && gpsa::has_padding_row(M, gpsa::mfma_mb_for(M)); }
 
 int gpsa_quadform_elbo_takes_delta(int M) { return M >= 1 && elbo_delta_ok(M) ? 1 : 0; }
 
-static int elbo_launch(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+// x3: the contraction on the bf16 matrix instructions in three pieces (pack_x3_kernel's image of Omega, panel_elbo_x3_kernel)
+static int elbo_launch(bool x3, int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
                        const float* meanT, const float* delta, const double* q, const float* var_u, const float* eps,
                        const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
                        double* part, float* FT, void* workspace, long long workspace_bytes, void* stream) {
@@ -1161,55 +1213,50 @@ static int elbo_launch(int omega_dtype, const float* alpha, const void* Omega, i
   if (M < 1 || C < 1 || L < 1 || N < 1 || S < 1 || !alpha || !Omega || (!meanT && !delta) || !q || !var_u || !eps || !Y ||
       !noise_u || !g || !dmeanT || !abar || !part)
     return GPSA_EINVAL;
+  if (x3 && omega_dtype != GPSA_F32 && omega_dtype != GPSA_F64) return GPSA_EINVAL;
   if (delta != nullptr && !elbo_delta_ok(M)) return GPSA_EUNSUPPORTED;
   if (!elbo_path(M) || C > GPSA_PANEL_MAX_C) return GPSA_EUNSUPPORTED;
-  if (workspace_bytes < gpsa_quadform_elbo_f32_workspace(M, C, L)) return GPSA_EWORKSPACE;
+  const int MB = mfma_mb_for(M), nct = x3 ? elbo_x3_nct_for(MB) : elbo_nct_for(MB);
+  const PanelWs lay = elbo_ws(x3, MB, L);
+  if (workspace_bytes < lay.total) return GPSA_EWORKSPACE;
   hipStream_t st = as_stream(stream);
-  const int MB = mfma_mb_for(M);
-  float* Ppk = (float*)workspace;
-  float* slab = Ppk + (long long)L * MB * 16 * MB * 16;
-  const int klast = (M - 16 * (MB - 1) <= 8) ? PACK_KSTEP_LAST : 0;
-  int rc = pack_any(omega_dtype, Omega, M, MB, L, 0, Ppk, st, klast, delta);
-  if (rc) return rc;
+  float* slab = (float*)((char*)workspace + lay.slab);
+  if (x3) {
+    const int KB = (MB + 1) / 2;
+    const unsigned pgrid = (unsigned)cdiv((long long)L * KB * MB * 64, 256);
+    if (omega_dtype == GPSA_F64)
+      pack_x3_kernel<double><<<pgrid, 256, 0, st>>>((const double*)Omega, M, MB, KB, L, (unsigned short*)workspace, delta);
+    else
+      pack_x3_kernel<float><<<pgrid, 256, 0, st>>>((const float*)Omega, M, MB, KB, L, (unsigned short*)workspace, delta);
+    GPSA_LAUNCH_CHECK();
+  } else {
+    const int rc = pack_any(omega_dtype, Omega, M, MB, L, 0, (float*)workspace, st, last_chunk_layout(M, MB), delta);
+    if (rc) return rc;
+  }
   if (delta != nullptr) meanT = nullptr;  // the kernel reads the mean from row M of its own product
-  const int gmax = gpsa_quadform_elbo_parts();
-  ElboArgs a{Ppk, alpha, M, C, L, meanT, q, var_u, eps, Y, noise_u, N, S, g, dmeanT, FT, abar, slab, part, gmax};
-  long long grid = 0;
-#define GPSA_ELBO_CASE(MBV, NCTV)                                                                       \
-  case MBV * 8 + NCTV: {                                                                                        \
-    const long long ntiles = cdiv(C, 64 * NCTV), T = ntiles * L;                                        \
-    grid = (long long)num_cus() * ((MBV * NCTV >= 14) ? 1 : 2);                                         \
-    if (grid > T) grid = T;                                                                             \
-    constexpr bool HEAD = MBV == 13 && NCTV == 2;  /* M > 16 (MB - 1): the instantiation without row clamps */ \
-    static const bool pair = [] { const char* e = getenv("GPSA_ELBO_PAIR"); return !(e && e[0] == '0'); }();  \
-    if (HEAD && pair && M > 16 * (MBV - 1) && M - 16 * (MBV - 1) <= 8)                                  \
-      panel_elbo_kernel<MBV, NCTV, 2, HEAD, HEAD><<<(unsigned)grid, 256, 0, st>>>(a);                   \
-    else if (HEAD && pair && M > 16 * (MBV - 1))                                                        \
-      panel_elbo_kernel<MBV, NCTV, 4, HEAD, HEAD><<<(unsigned)grid, 256, 0, st>>>(a);                   \
-    else if (HEAD && M > 16 * (MBV - 1) && M - 16 * (MBV - 1) <= 8)                                     \
-      panel_elbo_kernel<MBV, NCTV, 2, HEAD><<<(unsigned)grid, 256, 0, st>>>(a);                         \
-    else if (HEAD && M > 16 * (MBV - 1))                                                                \
-      panel_elbo_kernel<MBV, NCTV, 4, HEAD><<<(unsigned)grid, 256, 0, st>>>(a);                         \
-    else if (M - 16 * (MBV - 1) <= 8)                                                                   \
-      panel_elbo_kernel<MBV, NCTV, 2><<<(unsigned)grid, 256, 0, st>>>(a);                               \
-    else                                                                                                \
-      panel_elbo_kernel<MBV, NCTV, 4><<<(unsigned)grid, 256, 0, st>>>(a);                               \
-    dim3 rg((unsigned)ntiles, ntiles >= 512 ? 8 : (ntiles >= 128 ? 16 : 32));                           \
-    panel_slab_reduce_kernel<<<rg, 256, 0, st>>>(slab, M, MBV * 16, 64 * NCTV, C, L, ntiles, (int)grid, abar); \
-  } break;
-  switch (MB * 8 + elbo_nct_for(MB)) {
-    GPSA_ELBO_CASE(2, 4)
-    GPSA_ELBO_CASE(4, 4)
-    GPSA_ELBO_CASE(7, 4)
-    GPSA_ELBO_CASE(13, 2)
-    GPSA_ELBO_CASE(13, 1)
-    GPSA_ELBO_CASE(16, 2)
-    default:
-      return GPSA_EUNSUPPORTED;
+  ElboArgs a{(const float*)workspace, alpha, M, C, L, meanT, q, var_u, eps, Y, noise_u, N, S, g, dmeanT, FT, abar, slab, part,
+             gpsa_quadform_elbo_parts()};
+  const long long ntiles = cdiv(C, 64 * nct);
+  const long long grid = persistent_grid(x3 ? 1 : elbo_wgs_per_cu(MB, nct), ntiles * L);
+#define GPSA_ELBO_CASE(MBV, NCTV) \
+  case MBV: elbo_shape<MBV, NCTV>(a, (unsigned)grid, st); break;
+#define GPSA_ELBO_X3_CASE(MBV, NCTV) \
+  case MBV: panel_elbo_x3_kernel<MBV, NCTV><<<(unsigned)grid, 256, 0, st>>>(a); break;
+  if (x3) {
+    switch (MB) {
+      GPSA_ELBO_X3_SHAPES(GPSA_ELBO_X3_CASE)
+      default: return GPSA_EUNSUPPORTED;
+    }
+  } else {
+    switch (MB) {
+      GPSA_ELBO_SHAPES(GPSA_ELBO_CASE)
+      default: return GPSA_EUNSUPPORTED;
+    }
   }
 #undef GPSA_ELBO_CASE
+#undef GPSA_ELBO_X3_CASE
   GPSA_LAUNCH_CHECK();
-  return 0;
+  return slab_reduce_launch(slab, M, MB, nct, C, L, ntiles, grid, abar, st);
 }
 
 int gpsa_quadform_elbo_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
@@ -1217,7 +1264,7 @@ int gpsa_quadform_elbo_f32(int omega_dtype, const float* alpha, const void* Omeg
                            long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
                            float* FT, void* workspace, long long workspace_bytes, void* stream) {
   if (!meanT) return GPSA_EINVAL;
-  return elbo_launch(omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
+  return elbo_launch(false, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
                      part, FT, workspace, workspace_bytes, stream);
 }
 
@@ -1227,73 +1274,8 @@ int gpsa_quadform_elbo_delta_f32(int omega_dtype, const float* alpha, const void
                                  float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
                                  void* stream) {
   if (!delta) return GPSA_EINVAL;
-  return elbo_launch(omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
+  return elbo_launch(false, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
                      part, FT, workspace, workspace_bytes, stream);
-}
-
-/* ---- the same pass with the bf16x3 contraction (panel_elbo_x3_kernel, qf_x3.hip) ------------------------------- */
-// one column tile per wave at MB >= 13: at two, the alpha planes (2 x 7 x 12) and the product's accumulators (104) do not
-// fit the 256 arch VGPRs together and the allocator spills
-static inline int elbo_x3_nct_for(int MB) { return MB >= 13 ? 1 : 2; }
-static inline long long elbo_x3_pack_bytes(int M, int L) {
-  const int MB = gpsa::mfma_mb_for(M), KB = (MB + 1) / 2;
-  return (((long long)L * KB * MB * 3 * 1024) + 255) / 256 * 256;
-}
-
-long long gpsa_quadform_elbo_x3_f32_workspace(int M, long long C, int L) {
-  if (M < 1 || C < 1 || L < 1 || !elbo_path(M) || C > GPSA_PANEL_MAX_C) return 0;
-  const int MB = gpsa::mfma_mb_for(M), nct = elbo_x3_nct_for(MB);
-  const long long G = gpsa::num_cus();
-  // behind the packed operand: the slabs, and two chunks of slack for the ring stages that walk past the last chunk
-  return elbo_x3_pack_bytes(M, L) + G * 2 * (long long)MB * 16 * 64 * nct * 4 + 2LL * MB * 3 * 1024;
-}
-
-static int elbo_x3_launch(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
-                          const float* meanT, const float* delta, const double* q, const float* var_u, const float* eps,
-                          const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
-                          double* part, float* FT, void* workspace, long long workspace_bytes, void* stream) {
-  using namespace gpsa;
-  if (M < 1 || C < 1 || L < 1 || N < 1 || S < 1 || !alpha || !Omega || (!meanT && !delta) || !q || !var_u || !eps || !Y ||
-      !noise_u || !g || !dmeanT || !abar || !part)
-    return GPSA_EINVAL;
-  if (omega_dtype != GPSA_F32 && omega_dtype != GPSA_F64) return GPSA_EINVAL;
-  if (delta != nullptr && !elbo_delta_ok(M)) return GPSA_EUNSUPPORTED;
-  if (!elbo_path(M) || C > GPSA_PANEL_MAX_C) return GPSA_EUNSUPPORTED;
-  if (workspace_bytes < gpsa_quadform_elbo_x3_f32_workspace(M, C, L)) return GPSA_EWORKSPACE;
-  hipStream_t st = as_stream(stream);
-  const int MB = mfma_mb_for(M), KB = (MB + 1) / 2;
-  unsigned short* Ppk = (unsigned short*)workspace;
-  float* slab = (float*)((char*)workspace + elbo_x3_pack_bytes(M, L));
-  const long long nthr = (long long)L * KB * MB * 64;
-  if (omega_dtype == GPSA_F64)
-    pack_x3_kernel<double><<<(unsigned)cdiv(nthr, 256), 256, 0, st>>>((const double*)Omega, M, MB, KB, L, Ppk, delta);
-  else
-    pack_x3_kernel<float><<<(unsigned)cdiv(nthr, 256), 256, 0, st>>>((const float*)Omega, M, MB, KB, L, Ppk, delta);
-  GPSA_LAUNCH_CHECK();
-  if (delta != nullptr) meanT = nullptr;
-  const int gmax = gpsa_quadform_elbo_parts();
-  ElboArgs a{(const float*)Ppk, alpha, M, C, L, meanT, q, var_u, eps, Y, noise_u, N, S, g, dmeanT, FT, abar, slab, part, gmax};
-#define GPSA_ELBO_X3_CASE(MBV, NCTV)                                                                   \
-  case MBV: {                                                                                          \
-    const long long ntiles = cdiv(C, 64 * NCTV), T = ntiles * L;                                       \
-    long long grid = num_cus(); /* one workgroup per CU: the ring takes most of the LDS */             \
-    if (grid > T) grid = T;                                                                            \
-    panel_elbo_x3_kernel<MBV, NCTV><<<(unsigned)grid, 256, 0, st>>>(a);                                \
-    dim3 rg((unsigned)ntiles, ntiles >= 512 ? 8 : (ntiles >= 128 ? 16 : 32));                          \
-    panel_slab_reduce_kernel<<<rg, 256, 0, st>>>(slab, M, MBV * 16, 64 * NCTV, C, L, ntiles, (int)grid, abar); \
-  } break;
-  switch (MB) {
-    GPSA_ELBO_X3_CASE(2, 2)
-    GPSA_ELBO_X3_CASE(4, 2)
-    GPSA_ELBO_X3_CASE(7, 2)
-    GPSA_ELBO_X3_CASE(13, 1)
-    GPSA_ELBO_X3_CASE(16, 1)
-    default:
-      return GPSA_EUNSUPPORTED;
-  }
-#undef GPSA_ELBO_X3_CASE
-  GPSA_LAUNCH_CHECK();
-  return 0;
 }
 
 int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
@@ -1301,7 +1283,7 @@ int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* O
                               long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
                               float* FT, void* workspace, long long workspace_bytes, void* stream) {
   if (!meanT) return GPSA_EINVAL;
-  return elbo_x3_launch(omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
+  return elbo_launch(true, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
                         abar, part, FT, workspace, workspace_bytes, stream);
 }
 
@@ -1311,7 +1293,7 @@ int gpsa_quadform_elbo_delta_x3_f32(int omega_dtype, const float* alpha, const v
                                     float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
                                     void* stream) {
   if (!delta) return GPSA_EINVAL;
-  return elbo_x3_launch(omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
+  return elbo_launch(true, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
                         abar, part, FT, workspace, workspace_bytes, stream);
 }
 
@@ -1328,21 +1310,14 @@ int gpsa_quadform_bwd_alpha_kept_f32(const float* W, const float* g, int M, long
     GPSA_LAUNCH_CHECK();
     return 0;
   }
-  const int MB = mfma_mb_for(M);
-#define GPSA_KEPT_CASE(MBV, NCTV)                                                                        \
-  case MBV: {                                                                                            \
-    const long long ntiles = cdiv(C, 64 * NCTV);                                                         \
-    constexpr int RTB = 4;                                                                                \
-    kept_wsum_kernel<MBV, NCTV, RTB><<<dim3((unsigned)ntiles, NCTV, (MBV + RTB - 1) / RTB), 256, 0, st>>>( \
-        W, g, M, C, L, ntiles, 2.f, dcT, dmeanT, dalpha);                                                \
-    break;                                                                                               \
-  }
-  switch (MB) {
-    GPSA_KEPT_CASE(2, 4)
-    GPSA_KEPT_CASE(4, 4)
-    GPSA_KEPT_CASE(7, 4)
-    GPSA_KEPT_CASE(13, 3)
-    GPSA_KEPT_CASE(16, 2)
+  constexpr int RTB = 4;
+#define GPSA_KEPT_CASE(MBV, NCTV, MODEV)                                                                        \
+  case MBV:                                                                                                     \
+    kept_wsum_kernel<MBV, NCTV, RTB><<<dim3((unsigned)cdiv(C, 64 * NCTV), NCTV, (MBV + RTB - 1) / RTB), 256, 0, st>>>( \
+        W, g, M, C, L, cdiv(C, 64 * NCTV), 2.f, dcT, dmeanT, dalpha);                                           \
+    break;
+  switch (mfma_mb_for(M)) {  // the shapes whose QUAD kernel kept the products
+    GPSA_PANEL_SHAPES(GPSA_KEPT_CASE, MODE_QUAD)
     default:
       return GPSA_EUNSUPPORTED;
   }
@@ -1378,13 +1353,11 @@ int gpsa_quadform_bwd_alpha(int dtype, int omega_dtype, const void* alpha, const
     }
     // 256 < M <= 512: the register-resident kernel stays ahead of the LDS-DMA one (BASELINE config 4: 319 vs 342 ms)
     if (MB && MB <= MB_MAX_ACCUM && !force_generic()) {
-      const long long pk = (long long)L * MB * 16 * MB * 16;
-      if (workspace_bytes < (pk + accum_slab_floats(MB)) * 4) return GPSA_EWORKSPACE;
-      float* Ppk = (float*)workspace;
-      int rc = pack_any(omega_dtype, Omega, M, MB, L, 0, Ppk, st, PACK_KSTEP);
-      if (rc) return rc;
-      return panel_mfma_launch<MODE_ACCUM>(MB, Ppk, (const float*)alpha, (const float*)g, M, C, L,
-                                           (float*)dalpha, nullptr, 2.f, Ppk + pk, st);
+      const PanelWs lay = accum_ws(MB, L);
+      if (workspace_bytes < lay.total) return GPSA_EWORKSPACE;
+      return panel_mfma_launch<MODE_ACCUM>(MB, omega_dtype, Omega, 0, (float*)workspace, (const float*)alpha, (const float*)g,
+                                           M, C, L, (float*)dalpha, nullptr, 2.f,
+                                           (float*)((char*)workspace + lay.slab), st);
     }
     {
       const int rc = big_accum_launch(omega_dtype, (const float*)alpha, Omega, (const float*)g, M, C, L, (float*)dalpha,
@@ -1446,9 +1419,8 @@ int gpsa_quadform_bwd_omega(int dtype, int out_dtype, const void* alpha, const v
   if (dtype == GPSA_F32) {
     const int MB = gram_mb_for(M);
     if (MB && !force_generic()) {
-      if (workspace_bytes < gram_ws_bytes(MB, C, L)) return GPSA_EWORKSPACE;
-      return gram_mfma_launch(MB, (const float*)alpha, (const float*)g, M, C, L, dOmega, out_dtype,
-                              (float*)workspace, st);
+      return gram_mfma_launch(MB, (const float*)alpha, (const float*)g, M, C, L, dOmega, out_dtype, workspace,
+                              workspace_bytes, st);
     }
     if (out_dtype != dtype) return GPSA_EUNSUPPORTED;
     if (big_wants_pad(M, C)) {  // unaligned column count: the LDS-DMA Gram kernel on zero-padded copies
@@ -1477,7 +1449,7 @@ int gpsa_quadform_bwd_omega(int dtype, int out_dtype, const void* alpha, const v
 // the d-delta option of the Gram kernel: M in the last row tile with a padding row behind it, the MFMA path, 4-column alignment
 static inline bool gram_delta_ok(int M, long long C) {
   const int MB = gpsa::gram_mb_for(M);
-  return MB != 0 && !gpsa::force_generic() && M > 16 * (MB - 1) && M < 16 * MB && (C % 4 == 0) && C >= 8;
+  return MB != 0 && !gpsa::force_generic() && gpsa::has_padding_row(M, MB) && (C % 4 == 0) && C >= 8;
 }
 
 int gpsa_quadform_bwd_omega_takes_delta(int M, long long C) { return M >= 1 && C >= 1 && gram_delta_ok(M, C) ? 1 : 0; }
@@ -1489,67 +1461,44 @@ int gpsa_quadform_bwd_omega_delta_f32(int out_dtype, const float* alpha, const f
   if (M < 1 || C < 1 || L < 1 || !alpha || !g || !dmeanT || !dOmega || !ddelta) return GPSA_EINVAL;
   if (out_dtype != GPSA_F32 && out_dtype != GPSA_F64) return GPSA_EINVAL;
   if (!gram_delta_ok(M, C)) return GPSA_EUNSUPPORTED;
-  const int MB = gram_mb_for(M);
-  if (workspace_bytes < gram_ws_bytes(MB, C, L)) return GPSA_EWORKSPACE;
-  return gram_mfma_launch(MB, alpha, g, M, C, L, dOmega, out_dtype, (float*)workspace, as_stream(stream), dmeanT, ddelta,
-                          (float)dbeta);
+  return gram_mfma_launch(gram_mb_for(M), alpha, g, M, C, L, dOmega, out_dtype, workspace, workspace_bytes, as_stream(stream),
+                          dmeanT, ddelta, (float)dbeta);
 }
 
 /* ---- dOmega with the bf16x3 contraction (gram_x3_kernel, qf_x3.hip) ------------------------------------------ */
-// workgroups per output: the 32-column chunks dealt so that L x nsplit workgroups fill the chip about once (gram_nsplit's rule)
-static inline int gram_x3_nsplit(long long C, int L) {
-  using namespace gpsa;
-  const long long nch = cdiv(C, 32);
-  long long W = num_cus() / (L > 0 ? L : 1);
-  if (W < 1) W = 1;
-  const long long c = cdiv(nch, W);
-  long long ns = cdiv(nch, c);
-  return (int)(ns > 256 ? 256 : (ns < 1 ? 1 : ns));
-}
-static inline long long gram_x3_img_bytes(int MB, long long C) { return cdiv(C, 32) * MB * 3 * 1024; }
-
 long long gpsa_quadform_bwd_omega_x3_workspace(int M, long long C, int L) {
   using namespace gpsa;
   if (M < 1 || C < 1 || L < 1 || L > 65535) return 0;
   const int MB = gram_mb_for(M);
   if (!MB || force_generic()) return 0;
-  return gram_x3_img_bytes(MB, C) + (long long)L * gram_x3_nsplit(C, L) * MB * 16 * MB * 16 * 4;
+  return gram_x3_ws(MB, C, L).total;
 }
 
 static int gram_x3_launch(int out_dtype, const float* alpha, const float* g, const float* dmean, int M, long long C, int L,
                           void* dOmega, float* ddelta, float dbeta, void* workspace, long long workspace_bytes,
                           hipStream_t st) {
   using namespace gpsa;
-  const long long need = gpsa_quadform_bwd_omega_x3_workspace(M, C, L);
-  if (need == 0) return GPSA_EUNSUPPORTED;
-  if (workspace_bytes < need) return GPSA_EWORKSPACE;
-  const int MB = gram_mb_for(M), ns = gram_x3_nsplit(C, L);
+  if (gpsa_quadform_bwd_omega_x3_workspace(M, C, L) == 0) return GPSA_EUNSUPPORTED;
+  const int MB = gram_mb_for(M);
+  const GramWs lay = gram_x3_ws(MB, C, L);
+  if (workspace_bytes < lay.total) return GPSA_EWORKSPACE;
+  const int ns = lay.nsplit;
   const long long KBc = cdiv(C, 32);
   unsigned short* img = (unsigned short*)workspace;
-  float* part = (float*)((char*)workspace + gram_x3_img_bytes(MB, C));
+  float* part = (float*)((char*)workspace + lay.part);
   split_image_kernel<<<(unsigned)cdiv(KBc * MB * 64, 256), 256, 0, st>>>(alpha, M, MB, C, KBc, img);
   GPSA_LAUNCH_CHECK();
   dim3 grid((unsigned)L, (unsigned)ns);
-  switch (MB) {
 #define GPSA_GX3_CASE(MBV) \
   case MBV: gram_x3_kernel<MBV><<<grid, 256, 0, st>>>(img, g, dmean, M, C, L, ns, part); break;
-    GPSA_GX3_CASE(2)
-    GPSA_GX3_CASE(4)
-    GPSA_GX3_CASE(7)
-    GPSA_GX3_CASE(13)
-    GPSA_GX3_CASE(16)
-#undef GPSA_GX3_CASE
+  switch (MB) {
+    GPSA_GRAM_X3_SHAPES(GPSA_GX3_CASE)
     default:
       return GPSA_EUNSUPPORTED;
   }
+#undef GPSA_GX3_CASE
   GPSA_LAUNCH_CHECK();
-  dim3 rgrid((unsigned)cdiv(M, 32), (unsigned)cdiv(M + (ddelta != nullptr ? 1 : 0), 8), (unsigned)L);
-  if (out_dtype == GPSA_F64)
-    gram_reduce_kernel<double><<<rgrid, 256, 0, st>>>(part, M, MB * 16, L, ns, (double*)dOmega, ddelta, dbeta);
-  else
-    gram_reduce_kernel<float><<<rgrid, 256, 0, st>>>(part, M, MB * 16, L, ns, (float*)dOmega, ddelta, dbeta);
-  GPSA_LAUNCH_CHECK();
-  return 0;
+  return gram_reduce_launch(part, M, MB, L, ns, dOmega, out_dtype, ddelta, dbeta, st);
 }
 
 int gpsa_quadform_bwd_omega_x3(int dtype, int out_dtype, const void* alpha, const void* g, int M, long long C, int L,
@@ -1569,7 +1518,7 @@ int gpsa_quadform_bwd_omega_delta_x3(int out_dtype, const float* alpha, const fl
   if (M < 1 || C < 1 || L < 1 || !alpha || !g || !dmeanT || !dOmega || !ddelta) return GPSA_EINVAL;
   if (out_dtype != GPSA_F32 && out_dtype != GPSA_F64) return GPSA_EINVAL;
   const int MB = gram_mb_for(M);
-  if (!MB || !(M > 16 * (MB - 1) && M < 16 * MB)) return GPSA_EUNSUPPORTED;  // row M must be a padding row of the last tile row
+  if (!MB || !has_padding_row(M, MB)) return GPSA_EUNSUPPORTED;
   return gram_x3_launch(out_dtype, alpha, g, dmeanT, M, C, L, dOmega, ddelta, (float)dbeta, workspace, workspace_bytes,
                         as_stream(stream));
 }
@@ -1654,12 +1603,9 @@ int gpsa_panel_mm(int dtype, int p_dtype, int transP, const void* P, const void*
   if (dtype == GPSA_F32) {
     const int MB = mfma_mb_for(M);
     if (MB && MB <= MB_MAX_STORE && !force_generic()) {
-      if (workspace_bytes < (long long)MB * 16 * MB * 16 * 4) return GPSA_EWORKSPACE;
-      float* Ppk = (float*)workspace;
-      int rc = pack_any(p_dtype, P, M, MB, 1, tp, Ppk, st, PACK_KSTEP);
-      if (rc) return rc;
-      return panel_mfma_launch<MODE_STORE>(MB, Ppk, (const float*)X, nullptr, M, C, 1, (float*)Y,
-                                           (float*)colsq, 1.f, nullptr, st);
+      if (workspace_bytes < packed_bytes(MB, 1)) return GPSA_EWORKSPACE;
+      return panel_mfma_launch<MODE_STORE>(MB, p_dtype, P, tp, (float*)workspace, (const float*)X, nullptr, M, C, 1,
+                                           (float*)Y, (float*)colsq, 1.f, nullptr, st);
     }
     const float* Pc;
     int rc = operand_as<float>(p_dtype, P, (long long)M * M, &Pc, &workspace, &workspace_bytes, st);

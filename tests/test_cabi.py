@@ -107,9 +107,59 @@ def test_kernel_resources():
         # (the alpha slab's loads are branch-free on wave-uniform row bases; round 4: 300 bytes, a memory round trip in
         # front of a third of the slab's loads), a handful of VGPR spills into the other register file, and the SGPR
         # spills (to VGPR lanes, outside the K loop) bounded
-        if "panel_elbo_kernel<13, 2, 2, true" in nm or "panel_elbo_kernel<13, 2, 4, true" in nm:
+        if "panel_elbo_kernel<13, 2, 2, true, true>" in nm or "panel_elbo_kernel<13, 2, 4, true, true>" in nm:
             heads += 1
             assert k["scratch"] == 0 and k["vgpr_spill"] <= 16 and k["sgpr_spill"] <= 400, (nm, k)
         if "gram_mfma_kernel<13, true, 2>" in nm:
             assert k["scratch"] == 0 and k["sgpr_spill"] == 0 and k["vgpr_spill"] == 0, (nm, k)
-    assert heads == 4  # (RL 2 / 4) x (one barrier per chunk / per two chunks)
+    assert heads == 2  # RL 2 / 4, one barrier per two chunks
+
+
+# every workspace / size query of csrc/quadform.hip: name -> (argument axes, trailing constant arguments)
+_WS_QUERIES = {
+    "gpsa_quadform_workspace/f32": ("gpsa_quadform_workspace", "MCL", (0,), ()),
+    "gpsa_quadform_workspace/f64": ("gpsa_quadform_workspace", "MCL", (1,), ()),
+    "gpsa_quadform_keep_f32_workspace": ("gpsa_quadform_keep_f32_workspace", "ML", (), ()),
+    "gpsa_quadform_keep_f32_bytes": ("gpsa_quadform_keep_f32_bytes", "MCL", (), ()),
+    "gpsa_quadform_elbo_f32_workspace": ("gpsa_quadform_elbo_f32_workspace", "MCL", (), ()),
+    "gpsa_quadform_elbo_x3_f32_workspace": ("gpsa_quadform_elbo_x3_f32_workspace", "MCL", (), ()),
+    "gpsa_quadform_bwd_omega_x3_workspace": ("gpsa_quadform_bwd_omega_x3_workspace", "MCL", (), ()),
+    "gpsa_gram_batched_workspace/batch1": ("gpsa_gram_batched_workspace", "MCL", (), (1,)),
+    "gpsa_gram_batched_workspace/batch3": ("gpsa_gram_batched_workspace", "MCL", (), (3,)),
+    "gpsa_quadform_elbo_takes_delta": ("gpsa_quadform_elbo_takes_delta", "M", (), ()),
+    "gpsa_quadform_bwd_omega_takes_delta": ("gpsa_quadform_bwd_omega_takes_delta", "MC", (), ()),
+}
+_WS_AXES = {"M": [1, 5, 16, 17, 100, 193, 200, 201, 208, 256, 257, 300, 500, 512, 513, 1000],
+            "C": [1, 67, 260, 12500, 100000], "L": [1, 2, 50]}
+
+
+def _workspace_table(lib):
+    """{query: its values over the product of its axes (M outermost)}; the queries are pure host functions"""
+    import itertools
+
+    table = {}
+    for key, (fn, axes, head, tail) in _WS_QUERIES.items():
+        f = getattr(lib, fn)
+        table[key] = [int(f(*head, *args, *tail)) for args in itertools.product(*[_WS_AXES[a] for a in axes])]
+    return table
+
+
+def test_quadform_workspace_queries_match_the_recorded_table():
+    """tests/golden/quadform_workspaces.json holds what every workspace / size query of csrc/quadform.hip returned at
+    the commit named in it, on a device with ``cus`` compute units (the slab terms scale with that count): the
+    layouts behind the queries may be restated, the numbers may not move.  Off a device the library assumes 256 CUs."""
+    import json
+
+    import pytest
+
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "tests", "golden", "quadform_workspaces.json")) as f:
+        rec = json.load(f)
+    assert rec["axes"] == _WS_AXES and sorted(rec["values"]) == sorted(_WS_QUERIES)
+    cus = lib.gpsa_quadform_elbo_parts() // 2
+    if cus != rec["cus"]:
+        pytest.skip(f"recorded on {rec['cus']} compute units, this device has {cus}")
+    got = _workspace_table(lib)
+    for key, want in rec["values"].items():
+        bad = [i for i, (a, b) in enumerate(zip(got[key], want)) if a != b]
+        assert len(got[key]) == len(want) and not bad, (key, bad[:5], [got[key][i] for i in bad[:5]], [want[i] for i in bad[:5]])

@@ -125,7 +125,7 @@ def _run_kernel(x3, delta_form, om_dtype, Om64, al, delta, meanT, q, var_u, eps,
     ws_fn = lib.gpsa_quadform_elbo_x3_f32_workspace if x3 else lib.gpsa_quadform_elbo_f32_workspace
     wsb = int(ws_fn(M, C_, L))
     assert wsb > 0
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+    ws = torch.full((wsb,), 0xFF, dtype=torch.uint8, device=DEV)  # exactly the query's size, NaN throughout
     g = torch.empty(L, C_, device=DEV)
     dF = torch.empty(L, C_, device=DEV)
     abar = torch.empty(M, C_, device=DEV)
@@ -146,14 +146,21 @@ def _run_kernel(x3, delta_form, om_dtype, Om64, al, delta, meanT, q, var_u, eps,
     return g.double().cpu(), dF.double().cpu(), abar.double().cpu(), part.sum().cpu()
 
 
+# the edges of every row-tile class MB (tests/test_hip_kernels.py: TILE_EDGE_M), at a small shape: C = 260, L = 3
+TILE_EDGE_M = [16 * (mb - 1) + d for mb in (2, 4, 7, 13, 16) for d in (1, 8, 9, 15, 16)]
+LONG_M = [16, 25, 64, 100, 200, 208, 240]  # at C ~ 10 000, L = 5
+SHAPE_IDS = [str(m) for m in LONG_M] + [f"{m}-edge" for m in TILE_EDGE_M]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("M", [16, 25, 64, 100, 200, 208, 240])
-def test_x3_kernel_matches_fp64_contract(M):
+@pytest.mark.parametrize("M,L,N", [(m, 5, 4999) for m in LONG_M] + [(m, 3, 130) for m in TILE_EDGE_M], ids=SHAPE_IDS)
+def test_x3_kernel_matches_fp64_contract(M, L, N):
     """C = 9998 (not a multiple of 64) and L = 5: more items than workgroups, so column tiles are cut between them and
-    their abar leaves through the slabs.  Both mean forms (the delta one where M allows it), fp64 and fp32 Omega."""
+    their abar leaves through the slabs.  Both mean forms (the delta one where M allows it), fp64 and fp32 Omega.
+    C = 260, L = 3: the edges of the row-tile classes."""
     lib = _lib.load()
     gen = torch.Generator().manual_seed(M)
-    L, N, S = 5, 4999, 2
+    S = 2
     C_ = N * S
     A = torch.randn(L, M, M, generator=gen, dtype=torch.float64)
     Om64 = 0.1 * A @ A.transpose(1, 2) / M
@@ -324,7 +331,7 @@ def _gram(x3, delta_form, al, g, dmean, ddelta0):
     M, C_ = al.shape
     L = g.shape[0]
     wsb = int(lib.gpsa_quadform_bwd_omega_x3_workspace(M, C_, L) if x3 else lib.gpsa_quadform_workspace(F32, M, C_, L))
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=DEV)
+    ws = torch.full((max(wsb, 1),), 0xFF, dtype=torch.uint8, device=DEV)  # exactly the query's size, NaN throughout
     out = torch.empty(L, M, M, dtype=torch.float64, device=DEV)
     dd = ddelta0.clone()
     st = torch.cuda.current_stream().cuda_stream
@@ -341,13 +348,13 @@ def _gram(x3, delta_form, al, g, dmean, ddelta0):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("M", [16, 25, 64, 100, 200, 208, 240])
-def test_x3_gram_matches_fp64_contract(M):
+@pytest.mark.parametrize("M,L,C_", [(m, 5, 9996) for m in LONG_M] + [(m, 3, 260) for m in TILE_EDGE_M], ids=SHAPE_IDS)
+def test_x3_gram_matches_fp64_contract(M, L, C_):
     """dOmega_l = sum_c g[l,c] alpha_c alpha_c^T (and d delta = beta d delta + alpha dmean^T in the delta form) against
-    fp64, next to the fp32 kernel on the same inputs; C = 9996 (not a multiple of 32 or 64), L = 5"""
+    fp64, next to the fp32 kernel on the same inputs; C = 9996 (not a multiple of 32 or 64), L = 5, and the edges of the
+    row-tile classes at C = 260, L = 3"""
     lib = _lib.load()
     gen = torch.Generator().manual_seed(1000 + M)
-    L, C_ = 5, 9996
     al = (0.3 * torch.randn(M, C_, generator=gen)).float()
     g = torch.randn(L, C_, generator=gen).float()
     dmean = torch.randn(L, C_, generator=gen).float()

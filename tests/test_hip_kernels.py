@@ -35,6 +35,25 @@ def close(got, want, tol):
 
 TOL = {torch.float32: 2e-5, torch.float64: 1e-11}
 
+# The edges of every row-tile class MB of the register-resident contraction kernels, M = 16 (MB - 1) + {1, 8, 9}, 16 MB - 1
+# and 16 MB: the two sides of "the last row tile has at most 8 rows" (the RL = 2 kernels and the K-step packing of the
+# last chunk that goes with them), the two sides of "row M is a padding row of the last tile" (the delta forms), and
+# the class's first member.  Run at C = 260 (one column tile and a ragged tail; 263: not a multiple of 4) and L = 3.
+TILE_EDGE_M = [16 * (mb - 1) + d for mb in (2, 4, 7, 13, 16) for d in (1, 8, 9, 15, 16)]
+# the same edges of the accumulate / symmetric-form kernels' classes 24 and 32 (M <= 512)
+TILE_EDGE_M_BIG = [376, 377, 384, 385, 504, 505, 512]
+
+
+@pytest.fixture
+def exact_ws(hip, monkeypatch):
+    """every workspace the ops layer hands to the library is a fresh buffer of EXACTLY the size the query returned,
+    filled with NaN (all-ones bytes: a NaN in every float format the kernels read): a launcher that carves more than
+    its query reported, or a kernel that multiplies what nobody wrote, shows in the results"""
+    def ws(nbytes, like):
+        return torch.full((int(nbytes),), 0xFF, dtype=torch.uint8, device=like.device)
+
+    monkeypatch.setattr(hip, "_ws", ws)
+
 
 def _lib_einval():
     from spatial_alignment_amd import _lib
@@ -167,8 +186,9 @@ def test_omega_fwd_bwd(hip, M, B):
 
 
 @pytest.mark.parametrize("M,C,L", [(200, 1000, 50), (64, 333, 7), (16, 70, 5), (256, 513, 6), (130, 4099, 10),
-                                   (300, 1000, 3), (500, 1302, 4), (1000, 640, 2)])
-def test_quadform_keep_f32(hip, M, C, L):
+                                   (300, 1000, 3), (500, 1302, 4), (1000, 640, 2)] +
+                         [(m, 260, 3) for m in TILE_EDGE_M])
+def test_quadform_keep_f32(hip, exact_ws, M, C, L):
     """the data GP's form with its products kept (gpsa_quadform_fwd_keep_f32, opaque buffer) and the streaming
     backward over them (gpsa_quadform_bwd_alpha_kept_f32) against the recomputing pair"""
     al = rnd(M, C, seed=1)
@@ -185,7 +205,7 @@ def test_quadform_keep_f32(hip, M, C, L):
         assert nb == 0
         nb = L * M * C * 4
     assert wsb > 0 and L * M * C * 4 <= nb <= 1.6 * L * (M + 16) * (C + 256) * 4
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+    ws = torch.full((wsb,), 0xFF, dtype=torch.uint8, device=DEV)  # exactly the query's size, NaN throughout
     v = torch.empty(L, C, device=DEV)
     W = torch.full((nb // 4,), float("nan"), device=DEV)
     rc = hip.lib.gpsa_quadform_fwd_keep_f32(1, ald.data_ptr(), Omd.data_ptr(), M, C, L, v.data_ptr(), W.data_ptr(),
@@ -217,9 +237,10 @@ def test_quadform_keep_f32(hip, M, C, L):
 @pytest.mark.parametrize("M,N,S,L", [(200, 700, 3, 50), (64, 333, 1, 7), (16, 70, 2, 5), (100, 5000, 2, 9),
                                      (208, 129, 5, 3), (30, 64, 1, 1), (200, 20000, 2, 4), (5, 1, 1, 2), (200, 3, 2, 1),
                                      (1, 17, 1, 3), (240, 600, 2, 5), (256, 333, 1, 3), (209, 100, 3, 2),
-                                     (200, 20000, 5, 50)])  # the headline step's exact launch (column tiles split over
-                                                            # workgroups, partial tiles leaving through the slabs)
-def test_quadform_elbo(hip, M, N, S, L):
+                                     (200, 20000, 5, 50)] +  # the headline step's exact launch (column tiles split over
+                                                             # workgroups, partial tiles leaving through the slabs)
+                         [(m, 130, 2, 3) for m in TILE_EDGE_M])
+def test_quadform_elbo(hip, exact_ws, M, N, S, L):
     """variance + draw + Gaussian likelihood + abar in one pass over the products (gpsa_quadform_elbo_f32) against
     the formulas of the separate kernels (elementwise.hip) evaluated in fp64"""
     C = S * N
@@ -472,11 +493,12 @@ QF = [(10, 100, 3), (25, 1000, 5), (50, 333, 2), (100, 500, 4), (200, 2100, 7), 
       (500, 1300, 20), (1000, 3968, 9), (260, 128, 17), (300, 2052, 33),
       # ... and column counts that are not multiples of 4 (S * N is whatever the data has): padded copies
       (1000, 1302, 3), (600, 131, 5), (700, 2050, 2), (300, 1001, 4)]
+QF += [(m, c, 3) for m in TILE_EDGE_M for c in (260, 263)] + [(m, 260, 2) for m in TILE_EDGE_M_BIG]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("M,C,L", QF)
-def test_quadform(hip, dtype, M, C, L):
+def test_quadform(hip, exact_ws, dtype, M, C, L):
     al = rnd(M, C, dtype=dtype)
     A = rnd(L, M, M, dtype=torch.float64, seed=1, scale=0.3)
     Om = (A @ A.transpose(1, 2)).to(dtype)
@@ -493,8 +515,9 @@ def test_quadform(hip, dtype, M, C, L):
 
 
 @pytest.mark.parametrize("M,C,L", [(200, 2100, 7), (200, 20000, 50), (100, 5000, 3), (25, 1000, 5), (10, 100, 1), (250, 260, 2),
-                                   (200, 100000, 3), (208, 400, 2), (200, 2102, 2), (300, 400, 2), (120, 4000, 2)])
-def test_quadform_bwd_omega_with_ddelta(hip, M, C, L):
+                                   (200, 100000, 3), (208, 400, 2), (200, 2102, 2), (300, 400, 2), (120, 4000, 2)] +
+                         [(m, c, 3) for m in TILE_EDGE_M for c in (260, 263)])
+def test_quadform_bwd_omega_with_ddelta(hip, exact_ws, M, C, L):
     """gpsa_quadform_bwd_omega_delta_f32: the Gram sums and, out of the first padding row of the kernel's last row tile,
     d delta_F = alpha dmean^T (accumulated onto a given ddelta with beta); refused (None) where M fills its last row tile,
     lies before it, is beyond the kernel, or C is not a multiple of 4"""
