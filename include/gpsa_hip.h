@@ -221,6 +221,20 @@ int gpsa_quadform_elbo_delta_x3_f32(int omega_dtype, const float* alpha, const v
                                     const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
                                     float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
                                     void* stream);
+/* gpsa_quadform_elbo_f32 / _delta_f32 over partly observed outputs: Y[n,l] != Y[n,l] (a NaN) marks a missing entry,
+ * which is left out - z = 0, dmeanT = 0 and g = 0 exactly there, nothing of it in abar or part (the count of observed
+ * entries the loss needs: gpsa_count_observed).  fp32 contraction only; same arguments, sizes, workspace query
+ * (gpsa_quadform_elbo_f32_workspace) and GPSA_EUNSUPPORTED cases.  Without a NaN in Y they compute what the plain entries
+ * compute (their own kernels, panel_elbo_skip_kernel: equal to rounding, not necessarily bitwise). */
+int gpsa_quadform_elbo_skip_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                                long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
+                                double* part, float* FT, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_quadform_elbo_delta_skip_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                      const float* delta, const double* q, const float* var_u, const float* eps,
+                                      const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                      float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
+                                      void* stream);
 /* dOmega[l] = sum_c g[l,c] * alpha[:,c] alpha[:,c]^T  (full symmetric [L,M,M]), stored as out_dtype
  * (out_dtype != dtype only on the fp32 MFMA path, whose partial sums are widened while they are added:
  * GPSA_EUNSUPPORTED otherwise, and the caller converts) */
@@ -636,6 +650,11 @@ typedef struct gpsa_step_io {
    * (bwd_acc_mode 0 or 3) writes it. */
   const float* loss_src;
   float* loss_dst;
+  /* Partly observed outputs (model.skip_missing): nonzero = a NaN in Y[m] is a missing observation, and the fused ELBO
+   * pass runs gpsa_quadform_elbo_skip_f32 / _delta_skip_f32 (ll_part then goes to gpsa_elbo_loss_skip_fwd / _bwd with the
+   * counts of gpsa_count_observed).  Also in a bf16x3 plan: there is no x3 skip closing, the pass runs the fp32 skip
+   * kernel (the Gram stays on x3) and gpsa_step_contraction reports it.  0 (a zero-initialised io): today's kernels. */
+  int skip_missing;
 } gpsa_step_io;
 
 typedef struct gpsa_step_out_grads {        /* gradients of the caller's scalar wrt the forward's outputs */
@@ -659,7 +678,9 @@ long long gpsa_step_saved_bytes_nokeep(const void* plan);  /* arena of a forward
 int gpsa_step_fused(const void* plan, int m);         /* 1: modality m's training pass can run the fused ELBO kernel */
 int gpsa_step_contraction(const void* plan, int m);   /* bit mask of modality m's bf16x3 kernels in a training step: 1 =
                                                          the fused ELBO pass (when gpsa_step_io.fuse_elbo is set: the
-                                                         unfused path runs the fp32 kernels), 2 = the data GP's Gram */
+                                                         unfused path runs the fp32 kernels; cleared once a fused pass
+                                                         of the plan has run with gpsa_step_io.skip_missing, set again
+                                                         by one without), 2 = the data GP's Gram */
 long long gpsa_step_scratch_bytes(const void* plan);
 long long gpsa_step_bwd_acc_bytes(const void* plan);  /* gpsa_step_io.bwd_acc */
 int gpsa_step_n_kl(const void* plan);                 /* V*D + sum_m L_m */
@@ -793,6 +814,42 @@ int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* co
                                 const long long* const* view_off, const double* const* w, const float* gloss, int n_kl,
                                 double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all,
                                 int n_noise, double* dkl, void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- partly observed outputs (csrc/missing.hip; opt-in: model.skip_missing) -------------------------------------------
+ * A NaN in Y is a missing observation; the ELBO is the one of the observed entries:
+ *   LL_i = sum_v w_i[v] sum_{(n,p) observed in view v} log N(Y_i[n,p]; F_i[s,n,p], s_i) / S_i,   KL terms whole.
+ * gpsa_count_observed: nobs[i][v] = number of non-NaN entries of Y_i [N_i, P_i] in the rows of view v (view_off as in
+ * gpsa_elbo_loss_weighted_fwd; n_views == view_off == NULL: one view per term, all rows), written as DEVICE doubles by a
+ * counting launch over all (term, view) pairs (64 to a launch; a call with more pairs loops over them) and a fixed-order
+ * fp64 closing - no atomics, no host read: a captured step counts the batch it is replayed on.
+ * workspace >= gpsa_count_observed_workspace() bytes. */
+long long gpsa_count_observed_workspace(void);
+int gpsa_count_observed(int n_ll, const float* const* Y, const long long* N, const int* P, const int* n_views,
+                        const long long* const* view_off, double* const* nobs, void* workspace,
+                        long long workspace_bytes, void* stream);
+/* gpsa_elbo_loss_fwd / _bwd over the observed entries.  zpart (NULL, or per term NULL / nparts partial sums of z^2 from
+ * gpsa_quadform_elbo_skip_f32, gpsa_lmc_loglik_fused_skip_f32: F[i] / dF[i] ignored; such a term has one view);
+ * n_views / view_off / w: per-view weights as gpsa_elbo_loss_weighted_fwd (all NULL: one view of weight 1 per term; w
+ * alone NULL: the views weigh 1); nobs[i]: DEVICE array of the term's views' counts (gpsa_count_observed with the same
+ * views), which stand where S N P stands in the plain closings (the constant term, dnoise).  A term from draws applies
+ * the select per element: dF = 0 exactly at a missing entry.  A view or term without an observed entry adds exactly 0 to
+ * the loss and to dnoise.  workspace >= 8 * 4100 * n_ll bytes. */
+int gpsa_elbo_loss_skip_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const double* kl, int n_kl, double kl_scale, float* loss,
+                            double* ll_out, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_elbo_loss_skip_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const float* gloss, int n_kl, double kl_scale, float* const* dF,
+                            float* const* dnoise, float* dnoise_all, int n_noise, double* dkl, void* workspace,
+                            long long workspace_bytes, void* stream);
+/* gpsa_lmc_loglik_fused_f32 over the observed entries: a missing (n, p) has dF_obs = 0 BEFORE the dF_latent and dW
+ * products and z = 0.  Matrix-core kernel only (L <= 64); workspace: gpsa_lmc_loglik_workspace. */
+int gpsa_lmc_loglik_fused_skip_f32(const float* F, const float* W, const float* Y, const float* noise_u, int S, long long N,
+                                   int L, int P, double* zpart, int nparts, float* dF, float* dW, void* workspace,
+                                   long long workspace_bytes, void* stream);
 
 /* ---- prediction: closed-form moments of the data GP (csrc/predict.hip) ----------------------------------------------
  * The counterpart of gpsa_data_sample_fwd: from a chunk of c rows evaluated at S warp samples - meanT, v [L, S*c] fp32

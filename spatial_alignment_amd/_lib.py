@@ -113,7 +113,7 @@ class StepIO(C.Structure):
         ("F_obs_test", _vp * MAX_MODS), ("mu_z", _vp), ("kl", _vp), ("flag", _vp), ("keep_products", _i),
         ("reuse_mm", _i), ("fuse_elbo", _i), ("Y", _vp * MAX_MODS), ("noise_u", _vp * MAX_MODS),
         ("ll_part", _vp * MAX_MODS), ("F_fused_T", _vp * MAX_MODS), ("bwd_acc", _vp), ("bwd_acc_mode", _i),
-        ("f_event", _vp), ("loss_src", _vp), ("loss_dst", _vp),
+        ("f_event", _vp), ("loss_src", _vp), ("loss_dst", _vp), ("skip_missing", _i),
     ]
 
 
@@ -209,6 +209,17 @@ SIGNATURES.update({
                                          C.POINTER(_i), _pp, _pp, _vp, _i, _d, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_elbo_loss_weighted_bwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i),
                                          C.POINTER(_i), _pp, _pp, _vp, _i, _d, _pp, _pp, _vp, _i, _vp, _vp, _ll, _vp]),
+    "gpsa_quadform_elbo_skip_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_quadform_elbo_delta_skip_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_count_observed_workspace": (_ll, []),
+    "gpsa_count_observed": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _pp, _vp, _ll, _vp]),
+    "gpsa_elbo_loss_skip_fwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i), _pp, _i,
+                                     C.POINTER(_i), _pp, _pp, _pp, _vp, _i, _d, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_elbo_loss_skip_bwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i), _pp, _i,
+                                     C.POINTER(_i), _pp, _pp, _pp, _vp, _i, _d, _pp, _pp, _vp, _i, _vp, _vp, _ll, _vp]),
+    "gpsa_lmc_loglik_fused_skip_f32": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp, _i, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_predict_moments_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp]),
 })

@@ -40,6 +40,9 @@ int mvn_kl_grouped_fwd_copy(const double* mats, const double* inv, const double*
 // (zpart [nparts >= G], dWpart [G][L][P]); GPSA_EUNSUPPORTED beyond 64 latent outputs
 int lmc_mfma_launch(const float* F, const float* W, const float* Y, const float* noise_u, int S, long long N, int L,
                     int P, double* zpart, int nparts, float* dF, float* dWpart, int G, hipStream_t st);
+// ... with the NaN entries of Y left out of all of it (lmc_mfma_skip_kernel)
+int lmc_mfma_skip_launch(const float* F, const float* W, const float* Y, const float* noise_u, int S, long long N, int L,
+                         int P, double* zpart, int nparts, float* dF, float* dWpart, int G, hipStream_t st);
 
 // proj64.hip: alpha = Kinv X (fp64 matrix cores) as a persistent output-stationary kernel over pack_whiten_kernel's
 // packed inverse(s); proj64_ok says which shapes it takes; q is closed by atomic adds onto

@@ -367,6 +367,19 @@ constexpr int elbo_nct_for(int mb) {
 // with one barrier per two K chunks (qf_elbo.hip: PAIRB)
 extern template __global__ void panel_elbo_kernel<13, 2, 2, true, true>(ElboArgs);
 extern template __global__ void panel_elbo_kernel<13, 2, 4, true, true>(ElboArgs);
+// the same kernels with the NaN entries of Y left out of the likelihood (qf_elbo_skip.hip; gpsa_quadform_elbo_skip_f32):
+// a name of their own over the shared body (qf_elbo_body.hpp), the same shapes
+template <int MB, int NCT, int RL, bool FULLT = false, bool PAIRB = false>
+__global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT)) panel_elbo_skip_kernel(ElboArgs a);
+#define GPSA_ELBO_SKIP_EXTERN(MB, NCT)                                          \
+  extern template __global__ void panel_elbo_skip_kernel<MB, NCT, 2>(ElboArgs); \
+  extern template __global__ void panel_elbo_skip_kernel<MB, NCT, 4>(ElboArgs);
+#define GPSA_ELBO_SKIP_DEFINE(MB, NCT)                                   \
+  template __global__ void panel_elbo_skip_kernel<MB, NCT, 2>(ElboArgs); \
+  template __global__ void panel_elbo_skip_kernel<MB, NCT, 4>(ElboArgs);
+GPSA_ELBO_SHAPES(GPSA_ELBO_SKIP_EXTERN)
+extern template __global__ void panel_elbo_skip_kernel<13, 2, 2, true, true>(ElboArgs);
+extern template __global__ void panel_elbo_skip_kernel<13, 2, 4, true, true>(ElboArgs);
 
 // the same pass with the contraction on the bf16 matrix instructions in three pieces (qf_x3.hip; gpsa_step_desc.contraction
 // = 1): Ppk is then pack_x3_kernel's three-plane bf16 image of Omega

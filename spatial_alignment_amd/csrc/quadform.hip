@@ -754,14 +754,22 @@ static inline int gram_nl(int MB, int L, long long C) {
   return (can && C >= 8192) ? 2 : 1;
 }
 
-// panel_elbo_kernel for one shape of GPSA_ELBO_SHAPES
+// panel_elbo_kernel (skip: panel_elbo_skip_kernel, the NaN entries of Y left out) for one shape of GPSA_ELBO_SHAPES
 template <int MB, int NCT>
-static void elbo_shape(const ElboArgs& a, unsigned grid, hipStream_t st) {
+static void elbo_shape(const ElboArgs& a, unsigned grid, hipStream_t st, bool skip) {
   // the 13-tile shape with every row tile but the last inside the matrix (the headline configuration): the
   // instantiation without row clamps and with one barrier per two K chunks
   constexpr bool HEAD = MB == 13 && NCT == 2;
   const bool rl2 = last_tile_rl(a.M, MB) == 2;
-  if (HEAD && a.M > 16 * (MB - 1)) {
+  if (skip) {
+    if (HEAD && a.M > 16 * (MB - 1)) {
+      if (rl2) panel_elbo_skip_kernel<MB, NCT, 2, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
+      else panel_elbo_skip_kernel<MB, NCT, 4, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
+    } else {
+      if (rl2) panel_elbo_skip_kernel<MB, NCT, 2><<<grid, 256, 0, st>>>(a);
+      else panel_elbo_skip_kernel<MB, NCT, 4><<<grid, 256, 0, st>>>(a);
+    }
+  } else if (HEAD && a.M > 16 * (MB - 1)) {
     if (rl2) panel_elbo_kernel<MB, NCT, 2, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
     else panel_elbo_kernel<MB, NCT, 4, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
   } else {
@@ -1205,7 +1213,8 @@ static inline bool elbo_delta_ok(int M) { return elbo_path(M) && gpsa::has_paddi
 int gpsa_quadform_elbo_takes_delta(int M) { return M >= 1 && elbo_delta_ok(M) ? 1 : 0; }
 
 // x3: the contraction on the bf16 matrix instructions in three pieces (pack_x3_kernel's image of Omega, panel_elbo_x3_kernel)
-static int elbo_launch(bool x3, int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+// skip (fp32 contraction only): panel_elbo_skip_kernel - a NaN in Y is a missing observation
+static int elbo_launch(bool x3, bool skip, int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
                        const float* meanT, const float* delta, const double* q, const float* var_u, const float* eps,
                        const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
                        double* part, float* FT, void* workspace, long long workspace_bytes, void* stream) {
@@ -1239,7 +1248,7 @@ static int elbo_launch(bool x3, int omega_dtype, const float* alpha, const void*
   const long long ntiles = cdiv(C, 64 * nct);
   const long long grid = persistent_grid(x3 ? 1 : elbo_wgs_per_cu(MB, nct), ntiles * L);
 #define GPSA_ELBO_CASE(MBV, NCTV) \
-  case MBV: elbo_shape<MBV, NCTV>(a, (unsigned)grid, st); break;
+  case MBV: elbo_shape<MBV, NCTV>(a, (unsigned)grid, st, skip); break;
 #define GPSA_ELBO_X3_CASE(MBV, NCTV) \
   case MBV: panel_elbo_x3_kernel<MBV, NCTV><<<(unsigned)grid, 256, 0, st>>>(a); break;
   if (x3) {
@@ -1264,7 +1273,7 @@ int gpsa_quadform_elbo_f32(int omega_dtype, const float* alpha, const void* Omeg
                            long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
                            float* FT, void* workspace, long long workspace_bytes, void* stream) {
   if (!meanT) return GPSA_EINVAL;
-  return elbo_launch(false, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
+  return elbo_launch(false, false, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
                      part, FT, workspace, workspace_bytes, stream);
 }
 
@@ -1274,8 +1283,27 @@ int gpsa_quadform_elbo_delta_f32(int omega_dtype, const float* alpha, const void
                                  float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
                                  void* stream) {
   if (!delta) return GPSA_EINVAL;
-  return elbo_launch(false, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
+  return elbo_launch(false, false, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT, abar,
                      part, FT, workspace, workspace_bytes, stream);
+}
+
+int gpsa_quadform_elbo_skip_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                                long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
+                                double* part, float* FT, void* workspace, long long workspace_bytes, void* stream) {
+  if (!meanT) return GPSA_EINVAL;
+  return elbo_launch(false, true, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g,
+                     dmeanT, abar, part, FT, workspace, workspace_bytes, stream);
+}
+
+int gpsa_quadform_elbo_delta_skip_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                      const float* delta, const double* q, const float* var_u, const float* eps,
+                                      const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                      float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
+                                      void* stream) {
+  if (!delta) return GPSA_EINVAL;
+  return elbo_launch(false, true, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g,
+                     dmeanT, abar, part, FT, workspace, workspace_bytes, stream);
 }
 
 int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
@@ -1283,7 +1311,7 @@ int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* O
                               long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
                               float* FT, void* workspace, long long workspace_bytes, void* stream) {
   if (!meanT) return GPSA_EINVAL;
-  return elbo_launch(true, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
+  return elbo_launch(true, false, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
                         abar, part, FT, workspace, workspace_bytes, stream);
 }
 
@@ -1293,7 +1321,7 @@ int gpsa_quadform_elbo_delta_x3_f32(int omega_dtype, const float* alpha, const v
                                     float* abar, double* part, float* FT, void* workspace, long long workspace_bytes,
                                     void* stream) {
   if (!delta) return GPSA_EINVAL;
-  return elbo_launch(true, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
+  return elbo_launch(true, false, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g, dmeanT,
                         abar, part, FT, workspace, workspace_bytes, stream);
 }
 

@@ -601,6 +601,7 @@ struct Plan {
   // optional HIP-event timing of the three contraction launches of the first data-GP pass (bench.py's
   // roofline figures): slot = step index modulo the ring, 2 events per kernel
   std::vector<hipEvent_t> tev;
+  bool skip_seen = false;  // the last fused ELBO launch left the NaN entries of Y out (gpsa_step_io.skip_missing)
   int tslots = 0, tfwd = 0, tbwd = 0;
   void tick(int kernel, int edge, bool fwd, hipStream_t st) {
     if (tslots == 0) return;
@@ -1350,15 +1351,29 @@ static int data_pass_fwd(Ctx& c, const Pass& ps) {
     float* g_ext = c.sv<float>(ps.o_fuse);
     float* dmeanT = g_ext + (long long)(L + 1) * C;
     float* abar = dmeanT + (long long)L * C;
-    const long long wsb = ps.x3 ? gpsa_quadform_elbo_x3_f32_workspace(Mg, C, L) : gpsa_quadform_elbo_f32_workspace(Mg, C, L);
-    void* ws = c.sc.get<char>(wsb);
+    // io.skip_missing: the fp32 skip kernels (panel_elbo_skip_kernel), also in a bf16x3 plan - there is no x3 skip closing
+    // (gpsa_step_contraction then reports the pass as fp32); such a plan's scratch holds the larger of the two workspaces
+    const bool skip = c.io.skip_missing != 0, x3 = ps.x3 && !skip;
+    const long long ws32 = gpsa_quadform_elbo_f32_workspace(Mg, C, L);
+    const long long wsx3 = ps.x3 ? gpsa_quadform_elbo_x3_f32_workspace(Mg, C, L) : 0;
+    const long long wsb = x3 ? wsx3 : ws32;
+    void* ws = c.sc.get<char>(ps.x3 && ws32 > wsx3 ? ws32 : (ps.x3 ? wsx3 : ws32));
     const bool timed = !dry && !c.quiet && &ps == &P.passes[0];
     if (timed) P.tick(0, 0, true, c.st);
-    if (ps.x3 && mean_in_product)
+    if (!dry) P.skip_seen = skip;
+    if (skip && mean_in_product)
+      GPSA_RUN(gpsa_quadform_elbo_delta_skip_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
+                                                 c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
+                                                 c.io.ll_part[m], c.io.F_fused_T[m], ws, wsb, c.stv()));
+    else if (skip)
+      GPSA_RUN(gpsa_quadform_elbo_skip_f32(GPSA_F64, alpha, Om, Mg, C, L, meanT, q, c.prm.data_var, eps, c.io.Y[m],
+                                           (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
+                                           c.io.ll_part[m], c.io.F_fused_T[m], ws, wsb, c.stv()));
+    else if (x3 && mean_in_product)
       GPSA_RUN(gpsa_quadform_elbo_delta_x3_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
                                                c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
                                                c.io.ll_part[m], c.io.F_fused_T[m], ws, wsb, c.stv()));
-    else if (ps.x3)
+    else if (x3)
       GPSA_RUN(gpsa_quadform_elbo_x3_f32(GPSA_F64, alpha, Om, Mg, C, L, meanT, q, c.prm.data_var, eps, c.io.Y[m],
                                          (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar, c.io.ll_part[m],
                                          c.io.F_fused_T[m], ws, wsb, c.stv()));
@@ -2332,7 +2347,8 @@ int gpsa_step_fused(const void* plan, int m) {
 int gpsa_step_contraction(const void* plan, int m) {
   if (!plan) return 0;
   for (const gpsa::Pass& q : reinterpret_cast<const gpsa::Plan*>(plan)->passes)
-    if (q.m == m && !q.test) return ((q.o_fuse >= 0 && q.x3) ? 1 : 0) | (q.gx3 ? 2 : 0);
+    if (q.m == m && !q.test)  // (skip_seen: the plan's last fused pass took the fp32 skip kernel, gpsa_step_io.skip_missing)
+      return ((q.o_fuse >= 0 && q.x3 && !reinterpret_cast<const gpsa::Plan*>(plan)->skip_seen) ? 1 : 0) | (q.gx3 ? 2 : 0);
   return 0;
 }
 long long gpsa_step_bwd_acc_bytes(const void* plan) { return plan ? reinterpret_cast<const gpsa::Plan*>(plan)->bwd_acc_bytes : -1; }

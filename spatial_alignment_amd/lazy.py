@@ -221,6 +221,7 @@ def run_fused(rec, idx, Ys, parts):
         raise RuntimeError("GPSA: loss_fn on the F_samples of a forward whose backward has already run")
     plan, io, prm, saved, tensors, ins = (live[k] for k in ("plan", "io", "prm", "saved", "tensors", "ins"))
     mask = 0
+    io.skip_missing = 1 if rec.get("skip") else 0  # (gpsa_step_io: the fused pass leaves the NaN entries of Y out)
     for i, Y in zip(idx, Ys):
         io.Y[i] = Y.data_ptr()
         rec["Y"][i] = Y  # (alive until the backward has run: the io struct points into it)
@@ -233,3 +234,10 @@ def run_fused(rec, idx, Ys, parts):
         torch.ops.gpsa.step_forward(list(tensors), ins + list(Ys) + [rec["noise"]], outs, saved, scratch, call, 2 | mask)
     finally:
         TO.CALLS.pop(call, None)
+    # a bf16x3 plan's fused pass takes the fp32 skip kernel under skip_missing: plan.contraction follows the library's
+    # answer (gpsa_step_contraction) when the flag is on and once more after it went off (a model that never sets the
+    # flag makes no such call)
+    skip = bool(rec.get("skip"))
+    if skip or getattr(plan, "skip_ran", False):
+        plan.skip_ran = skip
+        plan.contraction = {m: int(plan.lib.gpsa_step_contraction(plan.handle, j)) for j, m in enumerate(plan.mods)}

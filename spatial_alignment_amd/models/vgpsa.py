@@ -148,6 +148,10 @@ class VariationalGPSA(GPSA):
         # instructions, the default and the headline - or "bf16x3", every operand in three bf16 pieces on the bf16 ones
         # (opt-in; step_engine.py: plan.contraction says which modalities got it).  None: GPSA_CONTRACTION, else "fp32".
         self.contraction = None
+        # partly observed outputs (opt-in): True = a NaN in data_dict[m]["outputs"] is a MISSING observation and loss_fn is
+        # the ELBO of the observed entries - every loss path takes its skip kernels (gpsa_elbo_loss_skip_fwd / _bwd,
+        # gpsa_quadform_elbo_skip_f32, gpsa_lmc_loglik_fused_skip_f32); False: the default kernels, a NaN propagates.
+        self.skip_missing = False
         self._noise = None  # injected Gaussian noise (tests / reproducibility), see inject_noise()
         self._cache = None
 
@@ -218,6 +222,28 @@ class VariationalGPSA(GPSA):
                 self.W_dict[m] = nn.Parameter(torch.randn([self.n_latent_gps[m], self.Ps[m]]))
 
     # ------------------------------------------------------------------------------------------
+    @property
+    def skip_missing(self):
+        return self.__dict__.get("_skip_missing", False)
+
+    @skip_missing.setter
+    def skip_missing(self, value):
+        if not isinstance(value, bool):
+            raise TypeError(f"skip_missing must be True or False, got {value!r}")
+        self.__dict__["_skip_missing"] = value
+
+    def _skip_loss(self, aux, kl, Fs, Ws=(), views=None):
+        """loss_fn's closing under skip_missing: the observed counts of every term (cached for observations that stay -
+        not for a minibatch's gathered rows nor for a converted copy, counted at every step), then SkipElboLossFn"""
+        Ysrc = list(aux["Y"])
+        Yc = [SE._f32c(y) for y in Ysrc]
+        aux["Y"] = Yc
+        if views is not None:
+            aux.update(views)
+        own = all(c is y for c, y in zip(Yc, Ysrc))  # (a copy made here dies with the step: its address says nothing)
+        aux["nobs"] = SE.observed_counts(self, Yc, views, cacheable=views is None and own)
+        return SE.SkipElboLossFn.apply(aux, self.noise_variance, kl, *Fs, *Ws).to(self.Xtilde.dtype)
+
     def _is_fixed(self, v):
         f = self.fixed_view_idx
         if f is None:
@@ -958,6 +984,7 @@ class VariationalGPSA(GPSA):
             raise AttributeError("loss_fn called before forward (no factorisations cached)")
         V, D = self.n_views, self.n_spatial_dims
         weighted = self._view_weights(data_dict)  # minibatch training: per-view likelihood weights (or None)
+        skip = self.skip_missing  # a NaN in the outputs is a missing observation: the skip kernels on every path
         if cache.kl is not None:  # forward ran through the step engine: the KL terms came out of its node
             kl = cache.kl if self.kl_scale != 0 else None  # (a slice without a KL share: no KL backward either)
             if kl is not None and self.kl_weight_G != 1.0:  # output-sharded rank: its share of the warp GPs' terms
@@ -968,9 +995,13 @@ class VariationalGPSA(GPSA):
                 # have no per-view weights)
                 Fs = [F.materialize() if isinstance(F, (LazyDraws, LazyProduct)) else F
                       for F in (F_samples[m] for m in self.modality_names)]
+                if skip:
+                    return self._skip_loss(aux, kl, Fs, views=weighted)
                 aux.update(weighted)
                 return SE.WeightedElboLossFn.apply(aux, self.noise_variance, kl, *Fs).to(self.Xtilde.dtype)
             fuse = getattr(cache, "fuse", None)
+            if fuse is not None:
+                fuse["skip"] = skip  # (run_fused: gpsa_step_io.skip_missing)
             Fs, eff, run_i, run_Y, run_parts = [], [], [], [], []
             lmc_terms, Ws, shapes = {}, [], [None] * self.n_modalities
             for i, m in enumerate(self.modality_names):
@@ -1019,6 +1050,8 @@ class VariationalGPSA(GPSA):
                     if eff[i] and shapes[i] is None:
                         shapes[i] = tuple(fuse["shapes"][i])
                 aux["fuse"], aux["fuse_mods"], aux["lmc"], aux["term_shapes"] = fuse, eff, lmc_terms, shapes
+            if skip:
+                return self._skip_loss(aux, kl, Fs, Ws)
             loss = SE.ElboLossFn.apply(aux, self.noise_variance, kl, *Fs, *Ws)
             return loss.to(self.Xtilde.dtype)
         f64 = torch.float64
@@ -1054,11 +1087,14 @@ class VariationalGPSA(GPSA):
                                              cache.Omega_F_fac[m]), l_first, 1).sum()
                 l_first += int(self.n_latent_outputs[m])
                 kl = term if kl is None else kl + term
-            if weighted is not None:
+            if weighted is not None or skip:
                 continue
             noise_u = self.noise_variance[-self.n_modalities + i]  # quirk 5 (used as a std)
             Y = data_dict[m]["outputs"]
             lls.append(E.LogLikFn.apply(F_samples[m], Y, noise_u))
+        if skip:
+            return self._skip_loss(self._loss_aux(data_dict), kl, [F_samples[m] for m in self.modality_names],
+                                   views=weighted)
         if weighted is not None:
             aux = dict(self._loss_aux(data_dict), **weighted)
             Fs = [F_samples[m] for m in self.modality_names]

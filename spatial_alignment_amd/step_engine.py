@@ -5,13 +5,15 @@
 C++, the warp GPs of all free views share their launches, and every parameter gradient is accumulated in
 fp64 and rounded once.  ``loss_fn`` is a second node, ``ElboLossFn``: ``gpsa_elbo_loss_fused_fwd`` / ``_bwd`` when some
 likelihood terms arrive from the step as partial sums, ``gpsa_elbo_loss_fwd`` / ``_bwd`` (the same host code without
-such terms) otherwise; ``WeightedElboLossFn`` (``gpsa_elbo_loss_weighted_fwd`` / ``_bwd``) under minibatch weights.
+such terms) otherwise; ``WeightedElboLossFn`` (``gpsa_elbo_loss_weighted_fwd`` / ``_bwd``) under minibatch weights;
+``SkipElboLossFn`` (``gpsa_elbo_loss_skip_fwd`` / ``_bwd``) for all of these under ``model.skip_missing``.
 
 PyTorch remains plumbing: it owns the tensors (parameters, outputs, the two arenas), the stream and the
 autograd bookkeeping between the two nodes and the optimiser.
 """
 import ctypes as C
 import os
+import weakref
 
 import torch
 
@@ -881,3 +883,99 @@ class WeightedElboLossFn(torch.autograd.Function):
             kshape, kdt = ctx.kl_meta
             dkl = dkl.reshape(kshape).to(kdt)
         return _loss_grads(ctx, dnoise, dkl, dF)
+
+
+_NOBS_CACHE_MAX = 8
+
+
+def observed_counts(model, Yc, views, cacheable):
+    """-> per term the device fp64 counts of the non-NaN entries of its observations, one per view (``views``: the
+    weighted loss's {"n_views", "view_off"} or None = one view per term); gpsa_count_observed, no host read.  With
+    ``cacheable`` (the caller's own tensors, kept across steps - not a minibatch's gathered rows, not a converted copy -
+    and no stream capture under way) the counts of a Y are kept on the model, keyed by its data pointer, version and
+    shape; the entry holds a weak reference to each keyed tensor and is a hit only for those very tensors (another
+    tensor that landed on a freed one's address is counted again)."""
+    dev = Yc[0].device
+    nv = list(views["n_views"]) if views is not None else []
+    off = list(views["view_off"]) if views is not None else []
+    key = None
+    if cacheable and not torch.cuda.is_current_stream_capturing():
+        cache = model.__dict__.setdefault("_nobs_cache", {})
+        key = tuple((y.data_ptr(), y._version, tuple(y.shape)) for y in Yc) + (tuple(nv), tuple(off))
+        hit = cache.get(key)
+        if hit is not None and all(r() is y for r, y in zip(hit[0], Yc)):
+            return hit[1]
+    nobs = [torch.empty(nv[i] if nv else 1, dtype=torch.float64, device=dev) for i in range(len(Yc))]
+    ws = _ops_mod.get_ops()._ws(TO.count_workspace_bytes(), nobs[0])
+    torch.ops.gpsa.count_observed(Yc, nv, off, nobs, ws)
+    if key is not None:
+        if len(cache) >= _NOBS_CACHE_MAX:
+            cache.clear()
+        cache[key] = ([weakref.ref(y) for y in Yc], nobs)
+    return nobs
+
+
+class SkipElboLossFn(torch.autograd.Function):
+    """ElboLossFn and WeightedElboLossFn over partly observed outputs (``model.skip_missing``): a NaN in Y is a missing
+    observation, and the loss is the ELBO of the observed entries - gpsa_elbo_loss_skip_fwd / _bwd, one C call each way.
+    inputs and aux as ElboLossFn (fused terms: aux["fuse_mods"], aux["lmc"], aux["term_shapes"]; an LMC term runs
+    gpsa_lmc_loglik_fused_skip_f32 here) plus, optionally, WeightedElboLossFn's n_views / view_off / weights (then every
+    term comes from its draws); aux["nobs"]: the terms' observed counts (observed_counts)."""
+
+    @staticmethod
+    def forward(ctx, aux, noise, kl, *ins):
+        n = len(aux["Y"])
+        Fs, Ws = ins[:n], ins[n:]
+        partial = aux.get("fuse_mods") is not None
+        fused = [bool(z) for z in aux["fuse_mods"]] if partial else [False] * n
+        lmc = (aux.get("lmc") or {}) if partial else {}
+        dev = Fs[0].device
+        Fc, Yc, nz, klc = _loss_inputs(Fs, aux["Y"], noise, kl, fused, flat_kl=True)
+        idx = [int(j) for j in aux["noise_idx"]]
+        lmc_saved = {}
+        for i, wpos in lmc.items():
+            Fl, W = Fc[i], Ws[wpos].detach()
+            S_, N_, L_ = (int(d) for d in Fl.shape)
+            nparts = int(_lib.load().gpsa_quadform_elbo_parts())
+            zpart = torch.empty(nparts, dtype=torch.float64, device=dev)
+            dFl, dW = torch.empty_like(Fl), torch.empty_like(W)
+            wsl = _ops_mod.get_ops()._ws(int(_lib.load().gpsa_lmc_loglik_workspace(S_ * N_, L_, int(W.shape[1]), nparts)),
+                                         Fl)
+            torch.ops.gpsa.lmc_loglik_fused_skip(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
+            lmc_saved[i] = (dFl, dW, wpos)
+            Fc[i] = zpart
+        loss, ll, ws = _loss_outputs(n, dev)
+        shapes, fl = [], []
+        if any(fused):
+            for i in range(n):
+                shapes += list(aux["term_shapes"][i]) if fused[i] else [int(d) for d in Fc[i].shape]
+            fl = [int(z) for z in fused]
+        views = (list(aux["n_views"]), list(aux["view_off"]), list(aux["weights"])) if "weights" in aux else ([], [], [])
+        tabs = (shapes, fl) + views + (list(aux["nobs"]),)
+        torch.ops.gpsa.elbo_loss_skip_fwd(Fc, Yc, nz, idx, *tabs, klc, float(aux["kl_scale"]), loss, ll, ws)
+        ctx.aux, ctx.args = aux, (Fc, Yc, nz, idx, tabs, fused)
+        ctx.lmc, ctx.n_w = lmc_saved, len(Ws)
+        ctx.n_kl = 0 if klc is None else klc.numel()
+        ctx.kl_meta = None if kl is None else (kl.shape, kl.dtype)
+        ctx.noise_meta = (noise.shape, noise.dtype)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        aux = ctx.aux
+        fuse = aux.get("fuse")
+        Fc, Yc, nz, idx, tabs, fused = ctx.args
+        g, dF, dnoise, dkl, ws = _loss_grad_buffers(gloss, Fc, nz, ctx.n_kl, fused)
+        if fuse is not None and any(z and i not in ctx.lmc for i, z in enumerate(fused)):
+            fuse["gloss"] = g if fuse.get("gloss") is None else fuse["gloss"] + g
+        dWs = [None] * ctx.n_w
+        for i, (dFl, dW, wpos) in ctx.lmc.items():  # formed at upstream gradient 1 by the forward: scaled here
+            dF[i] = dFl * g
+            dWs[wpos] = dW * g
+        real = [d if not z else g for d, z in zip(dF, fused)]
+        torch.ops.gpsa.elbo_loss_skip_bwd(Fc, Yc, nz, idx, *tabs, g, int(ctx.n_kl), float(aux["kl_scale"]), real, dnoise,
+                                          dkl, ws)
+        if dkl is not None:
+            kshape, kdt = ctx.kl_meta
+            dkl = dkl.reshape(kshape).to(kdt)
+        return _loss_grads(ctx, dnoise, dkl, dF, dWs)

@@ -23,6 +23,8 @@ each with
                                             gpsa::elbo_loss_fwd / _bwd, gpsa::adam_step  grid_example.py:59-78)
    minibatch training (opt-in)              gpsa::row_sample_gather,                   (minibatch.py)
                                             gpsa::elbo_loss_weighted_fwd / _bwd
+   partly observed outputs (opt-in)         gpsa::count_observed, gpsa::elbo_loss_skip_fwd / _bwd,
+                                            gpsa::lmc_loglik_fused_skip                (model.skip_missing)
 
 The step-engine ops are the ones ``VariationalGPSA.forward`` / ``loss_fn`` / ``FusedAdam`` go through
 (step_engine.py, optim.py): they mutate caller-allocated tensors (outputs, arenas, the flat gradient buffer) and
@@ -509,3 +511,86 @@ def _elbo_loss_weighted_bwd(Fs, Ys, noise, noise_idx, n_views, view_off, weights
 _engine_op("elbo_loss_weighted_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] n_views, "
            "int[] view_off, Tensor[] weights, Tensor gloss, int n_kl, float kl_scale, Tensor(a!)[] dFs, "
            "Tensor(b!) dnoise, Tensor(c!)? dkl, Tensor(d!) ws) -> ()", _elbo_loss_weighted_bwd)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# partly observed outputs (model.skip_missing; csrc/missing.hip): a NaN in Y is a missing observation
+# ---------------------------------------------------------------------------------------------------------
+def count_workspace_bytes():
+    return int(_lib.load().gpsa_count_observed_workspace()) + 64
+
+
+def _opt_views(n, n_views, view_off):
+    """(n_views, view_off) of the ops (empty lists: no views) -> the C tables or NULLs, and what keeps them alive"""
+    if not n_views:
+        return None, None, None
+    return _view_arrays(n_views, view_off)
+
+
+def _count_observed(Ys, n_views, view_off, nobs, ws):
+    """gpsa_count_observed: nobs[i][v] = the non-NaN entries of Ys[i] in view v's rows (empty n_views: one view per term),
+    device doubles written without a host read"""
+    n = len(Ys)
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    nv, offp, _keep = _opt_views(n, n_views, view_off)
+    _lib.check(_lib.load().gpsa_count_observed(n, arr(Ys), (C.c_longlong * n)(*[int(y.shape[0]) for y in Ys]),
+                                               (C.c_int * n)(*[int(y.shape[1]) for y in Ys]), nv, offp, arr(nobs),
+                                               ws.data_ptr(), ws.numel(), _raw_stream(ws.device.index)),
+               "gpsa_count_observed")
+
+
+_engine_op("count_observed(Tensor[] Ys, int[] n_views, int[] view_off, Tensor(a!)[] nobs, Tensor(b!) ws) -> ()",
+           _count_observed)
+
+
+def _skip_tables(n, n_views, view_off, weights, nobs):
+    nv, offp, keep = _opt_views(n, n_views, view_off)
+    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights]) if weights else None
+    return nv, offp, Wp, (C.c_void_p * n)(*[t.data_ptr() for t in nobs]), keep
+
+
+def _elbo_loss_skip_fwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, kl, kl_scale, loss, ll,
+                        ws):
+    """gpsa_elbo_loss_skip_fwd: the ELBO loss over the observed entries (fused: per term, "F" is its partial sums of z^2;
+    shapes as elbo_loss_fused_fwd, both empty without fused terms; n_views / view_off / weights empty: none)"""
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
+    nv, offp, Wp, Np, _keep = _skip_tables(n, n_views, view_off, weights, nobs)
+    _lib.check(_lib.load().gpsa_elbo_loss_skip_fwd(n, *terms, Zp, nparts, nv, offp, Wp, Np, *_kl_args(kl), float(kl_scale),
+                                                   loss.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   _raw_stream(loss.device.index)), "gpsa_elbo_loss_skip_fwd")
+
+
+_engine_op("elbo_loss_skip_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
+           "int[] n_views, int[] view_off, Tensor[] weights, Tensor[] nobs, Tensor? kl, float kl_scale, Tensor(a!) loss, "
+           "Tensor(b!) ll, Tensor(c!) ws) -> ()", _elbo_loss_skip_fwd)
+
+
+def _elbo_loss_skip_bwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, gloss, n_kl, kl_scale,
+                        dFs, dnoise, dkl, ws):
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
+    nv, offp, Wp, Np, _keep = _skip_tables(n, n_views, view_off, weights, nobs)
+    grads = _grad_arrays(dFs, dnoise, noise_idx, fused or None)
+    _lib.check(_lib.load().gpsa_elbo_loss_skip_bwd(n, *terms, Zp, nparts, nv, offp, Wp, Np, gloss.data_ptr(), int(n_kl),
+                                                   float(kl_scale), *grads, 0 if dkl is None else dkl.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), _raw_stream(gloss.device.index)),
+               "gpsa_elbo_loss_skip_bwd")
+
+
+_engine_op("elbo_loss_skip_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
+           "int[] n_views, int[] view_off, Tensor[] weights, Tensor[] nobs, Tensor gloss, int n_kl, float kl_scale, "
+           "Tensor(a!)[] dFs, Tensor(b!) dnoise, Tensor(c!)? dkl, Tensor(d!) ws) -> ()", _elbo_loss_skip_bwd)
+
+
+def _lmc_loglik_fused_skip(F, W, Y, noise, noise_idx, zpart, dF, dW, ws):
+    """gpsa_lmc_loglik_fused_skip_f32: lmc_loglik_fused with the NaN entries of Y left out of all three products"""
+    S, N, L = (int(d) for d in F.shape)
+    _lib.check(_lib.load().gpsa_lmc_loglik_fused_skip_f32(F.data_ptr(), W.data_ptr(), Y.data_ptr(),
+                                                          noise.data_ptr() + 4 * int(noise_idx), S, N, L,
+                                                          int(W.shape[1]), zpart.data_ptr(), zpart.numel(),
+                                                          dF.data_ptr(), dW.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                          _raw_stream(F.device.index)),
+               "gpsa_lmc_loglik_fused_skip_f32")
+
+
+_engine_op("lmc_loglik_fused_skip(Tensor F, Tensor W, Tensor Y, Tensor noise, int noise_idx, Tensor(a!) zpart, "
+           "Tensor(b!) dF, Tensor(c!) dW, Tensor(d!) ws) -> ()", _lmc_loglik_fused_skip)
