@@ -784,7 +784,7 @@ int gpsa_adam_step(int n, float* const* params, const float* const* grads, float
                    float* const* exp_avg_sq, const long long* numel, double lr, double beta1, double beta2,
                    double eps, float* step, void* stream);
 
-/* ---- minibatch (stochastic variational) training (csrc/minibatch.hip; opt-in) --------------------------------------
+/* ---- minibatch (stochastic variational) training (csrc/minibatch.hip, csrc/loss_views.hip; opt-in) ----------------
  * gpsa_row_sample_gather: draw step t's batch of every (modality m, view v) and gather it, in one launch plus a one-wave
  * launch that advances the step counter (counter[0] += 1 on the device: a replayed graph draws the next batch).
  * n_views[m] views per modality; n_rows / batch: N_{m,v} and B_{m,v} (1 <= B <= N) flattened over (m, v) in order
@@ -815,7 +815,7 @@ int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* co
                                 double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all,
                                 int n_noise, double* dkl, void* workspace, long long workspace_bytes, void* stream);
 
-/* ---- partly observed outputs (csrc/missing.hip; opt-in: model.skip_missing) -------------------------------------------
+/* ---- partly observed outputs (csrc/missing.hip, csrc/loss_views.hip; opt-in: model.skip_missing) ----------------------
  * A NaN in Y is a missing observation; the ELBO is the one of the observed entries:
  *   LL_i = sum_v w_i[v] sum_{(n,p) observed in view v} log N(Y_i[n,p]; F_i[s,n,p], s_i) / S_i,   KL terms whole.
  * gpsa_count_observed: nobs[i][v] = number of non-NaN entries of Y_i [N_i, P_i] in the rows of view v (view_off as in

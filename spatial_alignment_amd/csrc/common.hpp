@@ -1,5 +1,5 @@
 // Shared device helpers for libgpsa_hip (gfx950 only; wave = 64 lanes), and the workspace slot and host-side argument
-// check that the ELBO loss entries of elementwise.hip and minibatch.hip have in common.
+// check that the ELBO loss entries of elementwise.hip and loss_views.hip have in common.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

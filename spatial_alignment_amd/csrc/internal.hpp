@@ -44,6 +44,30 @@ int lmc_mfma_launch(const float* F, const float* W, const float* Y, const float*
 int lmc_mfma_skip_launch(const float* F, const float* W, const float* Y, const float* noise_u, int S, long long N, int L,
                          int P, double* zpart, int nparts, float* dF, float* dWpart, int G, hipStream_t st);
 
+// loss_views.hip: the per-view row table of a likelihood term (the weighted and the skip loss closings, and the counting
+// of missing.hip): at most LOSS_MAX_VIEWS views, view v = rows off[v] .. off[v + 1]
+constexpr int LOSS_MAX_VIEWS = 64;
+struct ViewRows {
+  long long off[LOSS_MAX_VIEWS + 1];
+};
+static inline bool views_ok(int V, const long long* off, long long N) {
+  if (V < 1 || V > LOSS_MAX_VIEWS || off == nullptr || off[0] != 0 || off[V] != N) return false;
+  for (int v = 0; v < V; ++v)
+    if (off[v + 1] < off[v]) return false;
+  return true;
+}
+// the caller's V views (checked by views_ok), or with off == nullptr one view of all N rows
+static inline ViewRows view_rows(long long N, int V, const long long* off) {
+  ViewRows vr;
+  if (off != nullptr) {
+    for (int v = 0; v <= V; ++v) vr.off[v] = off[v];
+  } else {
+    vr.off[0] = 0;
+    vr.off[1] = N;
+  }
+  return vr;
+}
+
 // proj64.hip: alpha = Kinv X (fp64 matrix cores) as a persistent output-stationary kernel over pack_whiten_kernel's
 // packed inverse(s); proj64_ok says which shapes it takes; q is closed by atomic adds onto
 // zero: q_zeroed says an earlier launch on the stream has cleared it (else a memset node goes in front)

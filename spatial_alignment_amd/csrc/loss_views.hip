@@ -1,0 +1,344 @@
+// The ELBO loss closings over per-view tables: every likelihood term is a sum over its views (row ranges of the term),
+// each with an fp64 weight and, over partly observed outputs, its count of observed entries.
+//   gpsa_elbo_loss_weighted_fwd / _bwd   minibatch training (minibatch.py): loss = -sum_i sum_v w_iv LL_iv + kl_scale sum(kl)
+//   gpsa_elbo_loss_skip_fwd / _bwd       model.skip_missing: the same over the observed entries only (a NaN in Y is a
+//                                        missing observation), with or without views and weights; terms from draws apply
+//                                        the select per element, fused terms arrive as partial sums of z^2 that already
+//                                        left the missing entries out; the counts stand where S N P stands elsewhere
+// Both pairs are argument checks around one views_fwd_impl / views_bwd_impl: the weighted pair passes no counts and no
+// fused terms.  The per-element kernels differ in their arithmetic and stay two (loglik_w_kernel counts per chunk and
+// sums z^2 - 1 in the backward; loglik_skip_kernel leaves the counts to the closing).
+#include "internal.hpp"
+
+namespace gpsa {
+
+// part[v * nb + block] = sum over the block's share of view v of  log N(Y; F, s)  (fwd)  or  z^2 - 1  (bwd, which also
+// writes dF = up w_v (Y - F) / (s^2 S)); F [S, N, P], Y [N, P], grid (nb, V)
+template <bool BWD>
+__global__ void __launch_bounds__(256)
+loglik_w_kernel(const float* __restrict__ F, const float* __restrict__ Y, const float* __restrict__ noise_u, int S,
+                long long NP, int P, ViewRows vr, const double* __restrict__ w, const float* __restrict__ gloss,
+                float* __restrict__ dF, double* __restrict__ part) {
+  __shared__ double red[4];
+  const int v = blockIdx.y, nb = gridDim.x;
+  const long long lo = vr.off[v] * P, per = (vr.off[v + 1] - vr.off[v]) * P, tot = per * S;
+  const double s = exp((double)noise_u[0]) + 1e-5;  // "variance" used as std
+  const float inv = (float)(1.0 / s);
+  const double cst = -log(s) - 0.9189385332046727;
+  const float coef = BWD ? (float)(-(double)gloss[0] * w[v] / (s * s * (double)S)) : 0.f;
+  double acc = 0.0;
+  for (long long i0 = blockIdx.x * 256LL * 4; i0 < tot; i0 += (long long)nb * 256 * 4) {
+    float acc4 = 0.f;
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = i0 + u * 256 + threadIdx.x;
+      if (j < tot) {
+        const long long sm = j / per, k = j - sm * per;
+        const long long i = sm * NP + lo + k;
+        const float r = Y[lo + k] - F[i];
+        const float z = r * inv;
+        if (BWD) {
+          dF[i] = coef * r;
+          acc4 += z * z - 1.f;
+        } else {
+          acc4 += z * z;
+          ++cnt;
+        }
+      }
+    }
+    acc += BWD ? (double)acc4 : -0.5 * (double)acc4 + cst * cnt;
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) part[(long long)v * nb + blockIdx.x] = acc;
+}
+
+// loglik_w_kernel over the observed entries: part[v * nb + block] = sum of z^2 over the block's share of view v (both
+// directions; the counts join in the closings); BWD also writes dF = -gloss w_v (Y - F) / (s^2 S), exactly 0 at a missing
+// entry.  w == nullptr: every view weighs 1.  F [S, N, P], Y [N, P], grid (nb, V)
+template <bool BWD>
+__global__ void __launch_bounds__(256)
+loglik_skip_kernel(const float* __restrict__ F, const float* __restrict__ Y, const float* __restrict__ noise_u, int S,
+                   long long NP, int P, ViewRows vr, const double* __restrict__ w, const float* __restrict__ gloss,
+                   float* __restrict__ dF, double* __restrict__ part) {
+  __shared__ double red[4];
+  const int v = blockIdx.y, nb = gridDim.x;
+  const long long lo = vr.off[v] * P, per = (vr.off[v + 1] - vr.off[v]) * P, tot = per * S;
+  const double s = exp((double)noise_u[0]) + 1e-5;  // "variance" used as std
+  const float inv = (float)(1.0 / s);
+  const double wv = w != nullptr ? w[v] : 1.0;
+  const float coef = BWD ? (float)(-(double)gloss[0] * wv / (s * s * (double)S)) : 0.f;
+  double acc = 0.0;
+  for (long long i0 = blockIdx.x * 256LL * 4; i0 < tot; i0 += (long long)nb * 256 * 4) {
+    float acc4 = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = i0 + u * 256 + threadIdx.x;
+      if (j < tot) {
+        const long long sm = j / per, k = j - sm * per;
+        const long long i = sm * NP + lo + k;
+        const float y = Y[lo + k];
+        const float r = (y == y) ? y - F[i] : 0.f;
+        const float z = r * inv;
+        if (BWD) dF[i] = coef * r;
+        acc4 += z * z;
+      }
+    }
+    acc += (double)acc4;
+  }
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) part[(long long)v * nb + blockIdx.x] = acc;
+}
+
+// thread 0, views in order, fp64:  nobs == nullptr: sum_v w_v t_v with t_v = sum_b part[v * nb + b];  otherwise
+// sum_v w_v (A t_v + B S nobs[v]) with w == nullptr as weights of 1, where a view without an observed entry adds exactly 0
+// whatever A and B are (no 0 * log)
+__device__ double view_total(const double* __restrict__ part, int V, int nb, const double* __restrict__ w,
+                             const double* __restrict__ nobs, int S, double A, double B, double* red) {
+  double tot = 0.0;
+  for (int v = 0; v < V; ++v) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) s += part[(long long)v * nb + b];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) {
+      if (nobs == nullptr)
+        tot += w[v] * s;
+      else if (nobs[v] > 0.0)
+        tot += (w != nullptr ? w[v] : 1.0) * (A * s + B * (double)S * nobs[v]);
+    }
+    __syncthreads();
+  }
+  return tot;
+}
+
+struct ViewFinishArgs {
+  const double* part[GPSA_MAX_MODS];   // [V][nb] partials (a fused term: V = 1, its nparts partial sums of z^2)
+  const double* w[GPSA_MAX_MODS];      // [V]; with counts: or nullptr (= 1)
+  const double* nobs[GPSA_MAX_MODS];   // [V] observed entries of Y per view, or nullptr: the partials are whole LL sums
+  const float* noise_u[GPSA_MAX_MODS];  // (read with counts only)
+  int V[GPSA_MAX_MODS], nb[GPSA_MAX_MODS], S[GPSA_MAX_MODS];
+  int n_ll, n_kl;
+  const double* kl;
+  double kl_scale;
+  double* ll;
+  float* loss;
+};
+// ll[i] = sum_v w_v LL_{i,v} / S_i, with counts LL_{i,v} = -sum z^2 / 2 + (-log s - log(2 pi) / 2) S nobs_v;
+// loss = kl_scale sum(kl) - sum_i ll[i]
+__global__ void __launch_bounds__(256) elbo_views_finish_kernel(ViewFinishArgs a) {
+  __shared__ double red[4];
+  double lsum = 0.0;
+  for (int i = 0; i < a.n_ll; ++i) {
+    double B = 0.0;
+    if (a.nobs[i] != nullptr) {
+      const double sd = exp((double)a.noise_u[i][0]) + 1e-5;
+      B = -log(sd) - 0.9189385332046727;
+    }
+    const double s = view_total(a.part[i], a.V[i], a.nb[i], a.w[i], a.nobs[i], a.S[i], -0.5, B, red);
+    if (threadIdx.x == 0) {
+      const double v = s / (double)a.S[i];
+      a.ll[i] = v;
+      lsum += v;
+    }
+  }
+  double k = 0.0;
+  for (int t = threadIdx.x; t < a.n_kl; t += 256) k += a.kl[t];
+  k = block_sum(k, red);
+  if (threadIdx.x == 0) a.loss[0] = (float)(a.kl_scale * k - lsum);
+}
+
+// dnoise_u = -gloss sum_v w_v (sum z^2 - 1)_v / s / S exp(noise_u)  (with counts: sum z^2 - S nobs_v); the first term
+// also zero-fills the whole noise gradient first and writes dkl = kl_scale gloss
+__global__ void __launch_bounds__(256)
+loglik_views_bwd_finish_kernel(const double* __restrict__ part, int V, int nb, const double* __restrict__ w,
+                               const double* __restrict__ nobs, const float* __restrict__ noise_u, int S,
+                               float* __restrict__ dnoise_u, const float* __restrict__ gloss, double* __restrict__ dkl,
+                               int n_kl, double kl_scale, float* __restrict__ zero_base, int zero_n) {
+  __shared__ double red[4];
+  if (zero_base != nullptr) {
+    for (int t = threadIdx.x; t < zero_n; t += blockDim.x) zero_base[t] = 0.f;
+    __syncthreads();
+  }
+  const double s = view_total(part, V, nb, w, nobs, S, 1.0, -1.0, red);
+  if (threadIdx.x == 0) {
+    const double e = exp((double)noise_u[0]), sc = e + 1e-5;
+    dnoise_u[0] = (float)(-(double)gloss[0] * s / sc / (double)S * e);
+  }
+  if (dkl != nullptr)
+    for (int t = threadIdx.x; t < n_kl; t += blockDim.x) dkl[t] = kl_scale * (double)gloss[0];
+}
+
+// blocks per view: enough for the largest view, at most 4096 partials per term in all
+static inline int view_blocks(int S, const ViewRows& vr, int V, int P) {
+  long long most = 0;
+  for (int v = 0; v < V; ++v) {
+    const long long t = (vr.off[v + 1] - vr.off[v]) * P * (long long)S;
+    if (t > most) most = t;
+  }
+  long long b = cdiv(most, 1024);
+  const long long cap = 4096 / V;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+// the skip pair's tables, checked before any launch: a term is either fused (zpart[i], one view, no weights of its own:
+// the fused kernels sum z^2 over all rows) or comes from its draws, with the caller's views or as one view
+static int skip_args_check(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                           const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                           const int* n_views, const long long* const* view_off, const double* const* w,
+                           const double* const* nobs, long long workspace_bytes) {
+  if (!nobs) return GPSA_EINVAL;
+  if ((n_views == nullptr) != (view_off == nullptr) || (w != nullptr && n_views == nullptr)) return GPSA_EINVAL;
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  for (int i = 0; i < n_ll; ++i) {
+    if (!nobs[i] || !noise_u[i]) return GPSA_EINVAL;
+    const bool fused = zpart && zpart[i];
+    if (fused && (nparts < 1 || (n_views && n_views[i] != 1))) return GPSA_EINVAL;
+    if (!fused && (!F[i] || !Y[i])) return GPSA_EINVAL;
+    if (n_views && !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
+    if (w && !w[i]) return GPSA_EINVAL;
+  }
+  return 0;
+}
+// ... and the weighted pair's: views and weights for every term
+static int weighted_args_check(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                               const int* S, const long long* N, const int* P, const int* n_views,
+                               const long long* const* view_off, const double* const* w, long long workspace_bytes) {
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  for (int i = 0; i < n_ll; ++i)
+    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
+  return 0;
+}
+
+// Both directions take checked arguments.  nobs == nullptr: the weighted closing (loglik_w_kernel; views and weights for
+// every term, no fused term); otherwise the skip closing (loglik_skip_kernel; zpart, n_views / view_off and w may each be
+// nullptr).  Term i's block partials go to its own slot of the workspace; a fused term brings its partials and launches
+// nothing here.
+static int views_fwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                          const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                          const int* n_views, const long long* const* view_off, const double* const* w,
+                          const double* const* nobs, const double* kl, int n_kl, double kl_scale, float* loss,
+                          double* ll_out, void* workspace, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const auto kernel = nobs ? loglik_skip_kernel<false> : loglik_w_kernel<false>;
+  ViewFinishArgs a = {};
+  a.n_ll = n_ll;
+  a.n_kl = kl ? n_kl : 0;
+  a.kl = kl;
+  a.kl_scale = kl_scale;
+  a.ll = ll_out;
+  a.loss = loss;
+  for (int i = 0; i < n_ll; ++i) {
+    a.w[i] = w ? w[i] : nullptr;
+    a.nobs[i] = nobs ? nobs[i] : nullptr;
+    a.noise_u[i] = noise_u[i];
+    a.S[i] = S[i];
+    if (zpart && zpart[i]) {
+      a.part[i] = zpart[i];
+      a.V[i] = 1;
+      a.nb[i] = nparts;
+      continue;
+    }
+    const int V = n_views ? n_views[i] : 1;
+    const ViewRows vr = view_rows(N[i], V, view_off ? view_off[i] : nullptr);
+    const int nb = view_blocks(S[i], vr, V, P[i]);
+    double* part = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
+    kernel<<<dim3(nb, V), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], vr, a.w[i], nullptr, nullptr,
+                                        part);
+    a.part[i] = part;
+    a.V[i] = V;
+    a.nb[i] = nb;
+  }
+  elbo_views_finish_kernel<<<1, 256, 0, st>>>(a);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+static int views_bwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                          const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                          const int* n_views, const long long* const* view_off, const double* const* w,
+                          const double* const* nobs, const float* gloss, int n_kl, double kl_scale, float* const* dF,
+                          float* const* dnoise, float* dnoise_all, int n_noise, double* dkl, void* workspace,
+                          void* stream) {
+  hipStream_t st = as_stream(stream);
+  const auto kernel = nobs ? loglik_skip_kernel<true> : loglik_w_kernel<true>;
+  for (int i = 0; i < n_ll; ++i) {
+    const double* wi = w ? w[i] : nullptr;
+    const double* part = zpart ? zpart[i] : nullptr;
+    int V = 1, nb = nparts;
+    if (part == nullptr) {
+      V = n_views ? n_views[i] : 1;
+      const ViewRows vr = view_rows(N[i], V, view_off ? view_off[i] : nullptr);
+      nb = view_blocks(S[i], vr, V, P[i]);
+      double* slot = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
+      kernel<<<dim3(nb, V), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], vr, wi, gloss, dF[i], slot);
+      part = slot;
+    }
+    // the first term's finishing launch also zero-fills the noise gradient and writes dkl
+    loglik_views_bwd_finish_kernel<<<1, 256, 0, st>>>(part, V, nb, wi, nobs ? nobs[i] : nullptr, noise_u[i], S[i],
+                                                      dnoise[i], gloss, i == 0 ? dkl : nullptr, n_kl, kl_scale,
+                                                      i == 0 ? dnoise_all : nullptr, n_noise);
+  }
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace gpsa
+
+extern "C" {
+
+int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                                const int* S, const long long* N, const int* P, const int* n_views,
+                                const long long* const* view_off, const double* const* w, const double* kl, int n_kl,
+                                double kl_scale, float* loss, double* ll_out, void* workspace,
+                                long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!n_views || !view_off || !w || !loss || !ll_out) return GPSA_EINVAL;
+  if (int rc = weighted_args_check(n_ll, F, Y, noise_u, S, N, P, n_views, view_off, w, workspace_bytes)) return rc;
+  return views_fwd_impl(n_ll, F, Y, noise_u, S, N, P, nullptr, 0, n_views, view_off, w, nullptr, kl, n_kl, kl_scale,
+                        loss, ll_out, workspace, stream);
+}
+
+int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                                const int* S, const long long* N, const int* P, const int* n_views,
+                                const long long* const* view_off, const double* const* w, const float* gloss, int n_kl,
+                                double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all,
+                                int n_noise, double* dkl, void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!n_views || !view_off || !w || !gloss || !dF || !dnoise) return GPSA_EINVAL;
+  if (int rc = weighted_args_check(n_ll, F, Y, noise_u, S, N, P, n_views, view_off, w, workspace_bytes)) return rc;
+  return views_bwd_impl(n_ll, F, Y, noise_u, S, N, P, nullptr, 0, n_views, view_off, w, nullptr, gloss, n_kl, kl_scale,
+                        dF, dnoise, dnoise_all, n_noise, dkl, workspace, stream);
+}
+
+int gpsa_elbo_loss_skip_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const double* kl, int n_kl, double kl_scale, float* loss,
+                            double* ll_out, void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!loss || !ll_out) return GPSA_EINVAL;
+  if (int rc = skip_args_check(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, workspace_bytes))
+    return rc;
+  return views_fwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kl, n_kl, kl_scale, loss,
+                        ll_out, workspace, stream);
+}
+
+int gpsa_elbo_loss_skip_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const float* gloss, int n_kl, double kl_scale, float* const* dF,
+                            float* const* dnoise, float* dnoise_all, int n_noise, double* dkl, void* workspace,
+                            long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!gloss || !dF || !dnoise) return GPSA_EINVAL;
+  if (int rc = skip_args_check(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, workspace_bytes))
+    return rc;
+  for (int i = 0; i < n_ll; ++i)
+    if (!dnoise[i] || (!(zpart && zpart[i]) && !dF[i])) return GPSA_EINVAL;
+  return views_bwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, gloss, n_kl, kl_scale,
+                        dF, dnoise, dnoise_all, n_noise, dkl, workspace, stream);
+}
+
+}  // extern "C"

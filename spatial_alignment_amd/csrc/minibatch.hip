@@ -1,5 +1,6 @@
-// Minibatch (stochastic variational) training: the per-step row sampler-gather and the per-view weighted Gaussian
-// likelihood (include/gpsa_hip.h, "minibatch").  Both are opt-in: no full-batch path launches anything from here.
+// Minibatch (stochastic variational) training: the per-step row sampler-gather (include/gpsa_hip.h, "minibatch"; the
+// per-view weighted likelihood it trains with is in loss_views.hip).  Opt-in: no full-batch path launches anything from
+// here.
 #include "common.hpp"
 
 namespace gpsa {
@@ -90,137 +91,6 @@ __global__ void __launch_bounds__(64) counter_advance_kernel(long long* counter)
   if (threadIdx.x == 0) counter[0] = counter[0] + 1;
 }
 
-// ---- per-view weighted Gaussian likelihood --------------------------------------------------------------------------
-constexpr int LLW_MAX_VIEWS = 64;
-struct ViewRows {
-  long long off[LLW_MAX_VIEWS + 1];  // view v = rows off[v] .. off[v + 1]
-};
-
-// part[v * nb + block] = sum over the block's share of view v of  log N(Y; F, s)  (fwd)  or  z^2 - 1  (bwd, which also
-// writes dF = up w_v (Y - F) / (s^2 S)); F [S, N, P], Y [N, P], grid (nb, V)
-template <bool BWD>
-__global__ void __launch_bounds__(256)
-loglik_w_kernel(const float* __restrict__ F, const float* __restrict__ Y, const float* __restrict__ noise_u, int S,
-                long long NP, int P, ViewRows vr, const double* __restrict__ w, const float* __restrict__ gloss,
-                float* __restrict__ dF, double* __restrict__ part) {
-  __shared__ double red[4];
-  const int v = blockIdx.y, nb = gridDim.x;
-  const long long lo = vr.off[v] * P, per = (vr.off[v + 1] - vr.off[v]) * P, tot = per * S;
-  const double s = exp((double)noise_u[0]) + 1e-5;  // "variance" used as std
-  const float inv = (float)(1.0 / s);
-  const double cst = -log(s) - 0.9189385332046727;
-  const float coef = BWD ? (float)(-(double)gloss[0] * w[v] / (s * s * (double)S)) : 0.f;
-  double acc = 0.0;
-  for (long long i0 = blockIdx.x * 256LL * 4; i0 < tot; i0 += (long long)nb * 256 * 4) {
-    float acc4 = 0.f;
-    int cnt = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long j = i0 + u * 256 + threadIdx.x;
-      if (j < tot) {
-        const long long sm = j / per, k = j - sm * per;
-        const long long i = sm * NP + lo + k;
-        const float r = Y[lo + k] - F[i];
-        const float z = r * inv;
-        if (BWD) {
-          dF[i] = coef * r;
-          acc4 += z * z - 1.f;
-        } else {
-          acc4 += z * z;
-          ++cnt;
-        }
-      }
-    }
-    acc += BWD ? (double)acc4 : -0.5 * (double)acc4 + cst * cnt;
-  }
-  acc = block_sum(acc, red);
-  if (threadIdx.x == 0) part[(long long)v * nb + blockIdx.x] = acc;
-}
-
-// sum_v w_v sum_b part[v * nb + b]   (thread 0; views in order, fp64)
-__device__ double weighted_total(const double* __restrict__ part, int V, int nb, const double* __restrict__ w,
-                                 double* red) {
-  double tot = 0.0;
-  for (int v = 0; v < V; ++v) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) s += part[(long long)v * nb + b];
-    s = block_sum(s, red);
-    if (threadIdx.x == 0) tot += w[v] * s;
-    __syncthreads();
-  }
-  return tot;
-}
-
-struct WeightedFinishArgs {
-  const double* part[GPSA_MAX_MODS];
-  const double* w[GPSA_MAX_MODS];
-  int V[GPSA_MAX_MODS], nb[GPSA_MAX_MODS], S[GPSA_MAX_MODS];
-  int n_ll, n_kl;
-  const double* kl;
-  double kl_scale;
-  double* ll;
-  float* loss;
-};
-// ll[i] = sum_v w_v LL_{i,v} / S_i;  loss = kl_scale sum(kl) - sum_i ll[i]
-__global__ void __launch_bounds__(256) elbo_weighted_finish_kernel(WeightedFinishArgs a) {
-  __shared__ double red[4];
-  double lsum = 0.0;
-  for (int i = 0; i < a.n_ll; ++i) {
-    const double s = weighted_total(a.part[i], a.V[i], a.nb[i], a.w[i], red);
-    if (threadIdx.x == 0) {
-      const double v = s / (double)a.S[i];
-      a.ll[i] = v;
-      lsum += v;
-    }
-  }
-  double k = 0.0;
-  for (int t = threadIdx.x; t < a.n_kl; t += 256) k += a.kl[t];
-  k = block_sum(k, red);
-  if (threadIdx.x == 0) a.loss[0] = (float)(a.kl_scale * k - lsum);
-}
-
-// dnoise_u = -gloss sum_v w_v (sum z^2 - 1)_v / s / S exp(noise_u); the first term also zero-fills the whole noise
-// gradient first and writes dkl = kl_scale gloss
-__global__ void __launch_bounds__(256)
-loglik_w_bwd_finish_kernel(const double* __restrict__ part, int V, int nb, const double* __restrict__ w,
-                           const float* __restrict__ noise_u, int S, float* __restrict__ dnoise_u,
-                           const float* __restrict__ gloss, double* __restrict__ dkl, int n_kl, double kl_scale,
-                           float* __restrict__ zero_base, int zero_n) {
-  __shared__ double red[4];
-  if (zero_base != nullptr) {
-    for (int t = threadIdx.x; t < zero_n; t += blockDim.x) zero_base[t] = 0.f;
-    __syncthreads();
-  }
-  const double s = weighted_total(part, V, nb, w, red);
-  if (threadIdx.x == 0) {
-    const double e = exp((double)noise_u[0]), sc = e + 1e-5;
-    dnoise_u[0] = (float)(-(double)gloss[0] * s / sc / (double)S * e);
-  }
-  if (dkl != nullptr)
-    for (int t = threadIdx.x; t < n_kl; t += blockDim.x) dkl[t] = kl_scale * (double)gloss[0];
-}
-
-// blocks per view: enough for the largest view, at most 4096 partials per term in all
-static inline int loglik_w_blocks(const int S, const long long* off, int V, int P) {
-  long long most = 0;
-  for (int v = 0; v < V; ++v) {
-    const long long t = (off[v + 1] - off[v]) * P * (long long)S;
-    if (t > most) most = t;
-  }
-  long long b = cdiv(most, 1024);
-  const long long cap = 4096 / V;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-static inline bool views_ok(int V, const long long* off, long long N) {
-  if (V < 1 || V > LLW_MAX_VIEWS || off == nullptr || off[0] != 0 || off[V] != N) return false;
-  for (int v = 0; v < V; ++v)
-    if (off[v + 1] < off[v]) return false;
-  return true;
-}
-
 }  // namespace gpsa
 
 extern "C" {
@@ -273,69 +143,6 @@ int gpsa_row_sample_gather(int n_mods, const int* n_views, const long long* n_ro
   hipStream_t st = as_stream(stream);
   row_sample_gather_kernel<<<(unsigned)cdiv(g, 4), 256, 0, st>>>(a);
   counter_advance_kernel<<<1, 64, 0, st>>>(counter);
-  GPSA_LAUNCH_CHECK();
-  return 0;
-}
-
-int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
-                                const int* S, const long long* N, const int* P, const int* n_views,
-                                const long long* const* view_off, const double* const* w, const double* kl, int n_kl,
-                                double kl_scale, float* loss, double* ll_out, void* workspace,
-                                long long workspace_bytes, void* stream) {
-  using namespace gpsa;
-  if (!n_views || !view_off || !w || !loss || !ll_out) return GPSA_EINVAL;
-  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
-  for (int i = 0; i < n_ll; ++i)
-    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
-  hipStream_t st = as_stream(stream);
-  WeightedFinishArgs a = {};
-  a.n_ll = n_ll;
-  a.n_kl = kl ? n_kl : 0;
-  a.kl = kl;
-  a.kl_scale = kl_scale;
-  a.ll = ll_out;
-  a.loss = loss;
-  for (int i = 0; i < n_ll; ++i) {
-    ViewRows vr;
-    for (int v = 0; v <= n_views[i]; ++v) vr.off[v] = view_off[i][v];
-    const int nb = loglik_w_blocks(S[i], view_off[i], n_views[i], P[i]);
-    double* part = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
-    loglik_w_kernel<false><<<dim3(nb, n_views[i]), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], vr,
-                                                                 w[i], nullptr, nullptr, part);
-    a.part[i] = part;
-    a.w[i] = w[i];
-    a.V[i] = n_views[i];
-    a.nb[i] = nb;
-    a.S[i] = S[i];
-  }
-  elbo_weighted_finish_kernel<<<1, 256, 0, st>>>(a);
-  GPSA_LAUNCH_CHECK();
-  return 0;
-}
-
-int gpsa_elbo_loss_weighted_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
-                                const int* S, const long long* N, const int* P, const int* n_views,
-                                const long long* const* view_off, const double* const* w, const float* gloss, int n_kl,
-                                double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all,
-                                int n_noise, double* dkl, void* workspace, long long workspace_bytes, void* stream) {
-  using namespace gpsa;
-  if (!n_views || !view_off || !w || !gloss || !dF || !dnoise) return GPSA_EINVAL;
-  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
-  for (int i = 0; i < n_ll; ++i)
-    if (!w[i] || !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
-  hipStream_t st = as_stream(stream);
-  for (int i = 0; i < n_ll; ++i) {
-    ViewRows vr;
-    for (int v = 0; v <= n_views[i]; ++v) vr.off[v] = view_off[i][v];
-    const int nb = loglik_w_blocks(S[i], view_off[i], n_views[i], P[i]);
-    double* part = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
-    loglik_w_kernel<true><<<dim3(nb, n_views[i]), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], vr,
-                                                                w[i], gloss, dF[i], part);
-    // the first term's finishing launch also zero-fills the noise gradient and writes dkl
-    loglik_w_bwd_finish_kernel<<<1, 256, 0, st>>>(part, n_views[i], nb, w[i], noise_u[i], S[i], dnoise[i], gloss,
-                                                  i == 0 ? dkl : nullptr, n_kl, kl_scale,
-                                                  i == 0 ? dnoise_all : nullptr, n_noise);
-  }
   GPSA_LAUNCH_CHECK();
   return 0;
 }

@@ -232,17 +232,18 @@ class VariationalGPSA(GPSA):
             raise TypeError(f"skip_missing must be True or False, got {value!r}")
         self.__dict__["_skip_missing"] = value
 
-    def _skip_loss(self, aux, kl, Fs, Ws=(), views=None):
-        """loss_fn's closing under skip_missing: the observed counts of every term (cached for observations that stay -
-        not for a minibatch's gathered rows nor for a converted copy, counted at every step), then SkipElboLossFn"""
-        Ysrc = list(aux["Y"])
-        Yc = [SE._f32c(y) for y in Ysrc]
-        aux["Y"] = Yc
-        if views is not None:
-            aux.update(views)
-        own = all(c is y for c, y in zip(Yc, Ysrc))  # (a copy made here dies with the step: its address says nothing)
-        aux["nobs"] = SE.observed_counts(self, Yc, views, cacheable=views is None and own)
-        return SE.SkipElboLossFn.apply(aux, self.noise_variance, kl, *Fs, *Ws).to(self.Xtilde.dtype)
+    def _close_loss(self, aux, kl, Fs, Ws, weighted, skip):
+        """loss_fn's closing through the one loss node: the view tables of ``weighted`` (or None) join ``aux``; under
+        ``skip`` so do the observed counts of every term (cached for observations that stay - not for a minibatch's
+        gathered rows nor for a converted copy, counted at every step); the loss comes back in the model's dtype"""
+        if weighted is not None:
+            aux.update(weighted)
+        if skip:
+            Ysrc = aux["Y"]
+            Yc = aux["Y"] = [SE._f32c(y) for y in Ysrc]
+            own = all(c is y for c, y in zip(Yc, Ysrc))  # (a copy made here dies with the step: its address says nothing)
+            aux["nobs"] = SE.observed_counts(self, Yc, weighted, cacheable=weighted is None and own)
+        return SE.ElboLossFn.apply(aux, self.noise_variance, kl, *Fs, *Ws).to(self.Xtilde.dtype)
 
     def _is_fixed(self, v):
         f = self.fixed_view_idx
@@ -937,9 +938,9 @@ class VariationalGPSA(GPSA):
         return kl.sum()
 
     def _view_weights(self, data_dict):
-        """``{"n_views", "view_off", "weights"}`` for WeightedElboLossFn when any modality of ``data_dict`` carries
-        ``"view_weights"`` (one weight per entry of its ``n_samples_list``; a modality without them weighs 1), else
-        None.  The weights go to the kernels as device fp64 tensors: a tensor that already is one is used as it is (a
+        """``{"n_views", "view_off", "weights"}`` for the loss node's weighted closing when any modality of ``data_dict``
+        carries ``"view_weights"`` (one weight per entry of its ``n_samples_list``; a modality without them weighs 1),
+        else None.  The weights go to the kernels as device fp64 tensors: a tensor that already is one is used as it is (a
         minibatch.RowSampler's batch: the same pointer at every step)."""
         mods = self.modality_names
         if not any("view_weights" in data_dict[m] for m in mods):
@@ -995,10 +996,7 @@ class VariationalGPSA(GPSA):
                 # have no per-view weights)
                 Fs = [F.materialize() if isinstance(F, (LazyDraws, LazyProduct)) else F
                       for F in (F_samples[m] for m in self.modality_names)]
-                if skip:
-                    return self._skip_loss(aux, kl, Fs, views=weighted)
-                aux.update(weighted)
-                return SE.WeightedElboLossFn.apply(aux, self.noise_variance, kl, *Fs).to(self.Xtilde.dtype)
+                return self._close_loss(aux, kl, Fs, (), weighted, skip)
             fuse = getattr(cache, "fuse", None)
             if fuse is not None:
                 fuse["skip"] = skip  # (run_fused: gpsa_step_io.skip_missing)
@@ -1050,10 +1048,7 @@ class VariationalGPSA(GPSA):
                     if eff[i] and shapes[i] is None:
                         shapes[i] = tuple(fuse["shapes"][i])
                 aux["fuse"], aux["fuse_mods"], aux["lmc"], aux["term_shapes"] = fuse, eff, lmc_terms, shapes
-            if skip:
-                return self._skip_loss(aux, kl, Fs, Ws)
-            loss = SE.ElboLossFn.apply(aux, self.noise_variance, kl, *Fs, *Ws)
-            return loss.to(self.Xtilde.dtype)
+            return self._close_loss(aux, kl, Fs, Ws, None, skip)
         f64 = torch.float64
         kl = None
         grouped = cache.batch is not None
@@ -1092,13 +1087,9 @@ class VariationalGPSA(GPSA):
             noise_u = self.noise_variance[-self.n_modalities + i]  # quirk 5 (used as a std)
             Y = data_dict[m]["outputs"]
             lls.append(E.LogLikFn.apply(F_samples[m], Y, noise_u))
-        if skip:
-            return self._skip_loss(self._loss_aux(data_dict), kl, [F_samples[m] for m in self.modality_names],
-                                   views=weighted)
-        if weighted is not None:
-            aux = dict(self._loss_aux(data_dict), **weighted)
+        if weighted is not None or skip:
             Fs = [F_samples[m] for m in self.modality_names]
-            return SE.WeightedElboLossFn.apply(aux, self.noise_variance, kl, *Fs).to(self.Xtilde.dtype)
+            return self._close_loss(self._loss_aux(data_dict), kl, Fs, (), weighted, skip)
         ll = lls[0] if len(lls) == 1 else torch.stack(lls)
         # -LL + kl_scale * KL in one launch (kl: the per-term vector of the grouped path, or a scalar)
         return E.ElboFn.apply(ll, kl, self.kl_scale).to(self.Xtilde.dtype)

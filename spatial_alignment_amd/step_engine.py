@@ -3,10 +3,11 @@
 ``forward`` of the model becomes ONE autograd node whose forward and backward are one C call each
 (``gpsa_step_forward`` / ``gpsa_step_backward``): the launch sequence of the whole step is enqueued from
 C++, the warp GPs of all free views share their launches, and every parameter gradient is accumulated in
-fp64 and rounded once.  ``loss_fn`` is a second node, ``ElboLossFn``: ``gpsa_elbo_loss_fused_fwd`` / ``_bwd`` when some
-likelihood terms arrive from the step as partial sums, ``gpsa_elbo_loss_fwd`` / ``_bwd`` (the same host code without
-such terms) otherwise; ``WeightedElboLossFn`` (``gpsa_elbo_loss_weighted_fwd`` / ``_bwd``) under minibatch weights;
-``SkipElboLossFn`` (``gpsa_elbo_loss_skip_fwd`` / ``_bwd``) for all of these under ``model.skip_missing``.
+fp64 and rounded once.  ``loss_fn`` is a second node, ``ElboLossFn``, whose closing follows from its ``aux``:
+``gpsa_elbo_loss_fused_fwd`` / ``_bwd`` when some likelihood terms arrive from the step as partial sums,
+``gpsa_elbo_loss_fwd`` / ``_bwd`` (the same host code without such terms) otherwise; ``gpsa_elbo_loss_weighted_fwd`` /
+``_bwd`` under minibatch weights (``aux["weights"]``); ``gpsa_elbo_loss_skip_fwd`` / ``_bwd`` for all of these under
+``model.skip_missing`` (``aux["nobs"]``).
 
 PyTorch remains plumbing: it owns the tensors (parameters, outputs, the two arenas), the stream and the
 autograd bookkeeping between the two nodes and the optimiser.
@@ -743,13 +744,15 @@ def _f32c(t):
     return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
 
-def _loss_inputs(Fs, Ys, noise, kl, fused=None, flat_kl=False):
-    """the loss nodes' inputs as the kernels read them -> (Fc, Yc, nz, klc): detached contiguous fp32 draws (a fused
-    term's partial sums stay as they are), observations and noise; kl detached contiguous fp64 (or None)"""
-    Fc = [f.detach() if (fused is not None and fused[i]) else _f32c(f.detach()) for i, f in enumerate(Fs)]
+def _loss_inputs(Fs, Ys, noise, kl, fused):
+    """the loss node's inputs as the kernels read them -> (Fc, Yc, nz, klc): detached contiguous fp32 draws (a fused
+    term's partial sums stay as they are), observations and noise; kl detached, flat, contiguous fp64 (or None)"""
+    Fc = [f.detach() if fused[i] else _f32c(f.detach()) for i, f in enumerate(Fs)]
     klc = None
     if kl is not None:
-        klc = kl.detach().reshape(-1) if flat_kl else kl.detach()
+        klc = kl.detach()
+        if klc.dim() != 1:
+            klc = klc.reshape(-1)
         klc = klc if (klc.dtype == torch.float64 and klc.is_contiguous()) else klc.double().contiguous()
     return Fc, [_f32c(y) for y in Ys], _f32c(noise.detach()), klc
 
@@ -764,43 +767,51 @@ def _loss_outputs(n, dev):
     return loss, torch.empty(n, dtype=torch.float64, device=dev), _loss_ws(n, loss)
 
 
-def _loss_grad_buffers(gloss, Fc, nz, n_kl, fused=None):
+def _loss_grad_buffers(gloss, Fc, nz, n_kl, fused):
     """-> (g, dF, dnoise, dkl, workspace) for a loss backward: the upstream gradient as [1] fp32 and the outputs (a
     fused term's dF is a placeholder: its real gradient travels through the ``fuse`` record)"""
     dev = Fc[0].device
     g = gloss.detach().reshape(1)
     g = g if g.dtype == torch.float32 else g.float()
-    dF = [placeholder_grad(dev, f.numel()) if (fused is not None and fused[i]) else torch.empty_like(f)
-          for i, f in enumerate(Fc)]
+    dF = [placeholder_grad(dev, f.numel()) if fused[i] else torch.empty_like(f) for i, f in enumerate(Fc)]
     dnoise = torch.empty(nz.numel(), dtype=torch.float32, device=dev)  # zero-filled by the first finishing launch
     dkl = torch.empty(n_kl, dtype=torch.float64, device=dev) if n_kl else None
     return g, dF, dnoise, dkl, _loss_ws(len(Fc), g)
 
 
-def _loss_grads(ctx, dnoise, dkl, dF, dWs=()):
+def _loss_grads(ctx, dnoise, dkl, dF, dWs):
     shape, dt = ctx.noise_meta
     return (None, dnoise.reshape(shape).to(dt), dkl) + tuple(dF) + tuple(dWs)
 
 
 class ElboLossFn(torch.autograd.Function):
     """loss = -(sum_i LL_i) + kl_scale * sum(kl_w * kl)   (vgpsa.py:532-540) as one C call each way.
-    inputs: noise_variance [n], kl [T] or None, F_0 .. F_{n_ll-1} (then the W of the LMC terms);
+    inputs: noise_variance [n], kl (any shape) or None, F_0 .. F_{n_ll-1} (then the W of the LMC terms);
     aux: Y tensors, noise indices, kl_scale.  With aux["fuse_mods"] the terms it marks arrive as partial sums of z^2
     instead of draws: from the step (StepFn with aux["fuse"]: the likelihood rode in the data GP's pass), or - an LMC
     modality, aux["lmc"] = {term: index of its W among the trailing inputs} - formed here from (F_latent, W, Y) without
-    F_obs (gpsa_lmc_loglik_fused_f32); aux["term_shapes"] holds such a term's [S, N, P].  A call with at least one such
-    term takes gpsa_elbo_loss_fused_fwd / _bwd, one with none gpsa_elbo_loss_fwd / _bwd."""
+    F_obs (gpsa_lmc_loglik_fused_f32); aux["term_shapes"] holds such a term's [S, N, P].  The closing follows from aux:
+      aux["nobs"] (model.skip_missing: the terms' observed counts, observed_counts)  gpsa_elbo_loss_skip_fwd / _bwd over
+          the observed entries, a NaN in Y being a missing observation (an LMC term: gpsa_lmc_loglik_fused_skip_f32), with
+          the fused tables and the view tables below where aux has them;
+      aux["weights"] (minibatch training, minibatch.py: per term a device fp64 tensor of n_views entries, with
+          aux["n_views"] per term and aux["view_off"], every term's n_views + 1 row offsets concatenated)
+          gpsa_elbo_loss_weighted_fwd / _bwd: loss = -(sum_i sum_v w_iv LL_iv) + kl_scale * sum(kl), every term from
+          its materialised draws;
+      at least one term as partial sums  gpsa_elbo_loss_fused_fwd / _bwd;  none  gpsa_elbo_loss_fwd / _bwd."""
 
     @staticmethod
     def forward(ctx, aux, noise, kl, *ins):
         n = len(aux["Y"])
         Fs, Ws = ins[:n], ins[n:]
+        nobs = aux.get("nobs")
         partial = aux.get("fuse_mods") is not None
         fused = [bool(z) for z in aux["fuse_mods"]] if partial else [False] * n  # partial sums in THIS call
         lmc = (aux.get("lmc") or {}) if partial else {}
         dev = Fs[0].device
         Fc, Yc, nz, klc = _loss_inputs(Fs, aux["Y"], noise, kl, fused)
         idx = [int(j) for j in aux["noise_idx"]]
+        lmc_op = torch.ops.gpsa.lmc_loglik_fused if nobs is None else torch.ops.gpsa.lmc_loglik_fused_skip
         lmc_saved = {}
         for i, wpos in lmc.items():
             Fl, W = Fc[i], Ws[wpos].detach()
@@ -810,22 +821,29 @@ class ElboLossFn(torch.autograd.Function):
             dFl, dW = torch.empty_like(Fl), torch.empty_like(W)
             wsl = _ops_mod.get_ops()._ws(int(_lib.load().gpsa_lmc_loglik_workspace(S_ * N_, L_, int(W.shape[1]), nparts)),
                                          Fl)
-            torch.ops.gpsa.lmc_loglik_fused(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
+            lmc_op(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
             lmc_saved[i] = (dFl, dW, wpos)
             Fc[i] = zpart
         loss, ll, ws = _loss_outputs(n, dev)  # (after the LMC terms: they grow the same per-stream scratch)
-        shapes = None
+        tabs = ()
         if any(fused):
             shapes = []
             for i in range(n):
                 shapes += list(aux["term_shapes"][i]) if fused[i] else [int(d) for d in Fc[i].shape]
-            torch.ops.gpsa.elbo_loss_fused_fwd(Fc, Yc, nz, idx, shapes, [int(z) for z in fused], klc,
-                                               float(aux["kl_scale"]), loss, ll, ws)
+            tabs = (shapes, [int(z) for z in fused])
+        if nobs is not None:
+            views = (list(aux["n_views"]), list(aux["view_off"]), list(aux["weights"])) if "weights" in aux else ([], [], [])
+            name, tabs = "elbo_loss_skip", (tabs or ([], [])) + views + (list(nobs),)
+        elif "weights" in aux:
+            name, tabs = "elbo_loss_weighted", (list(aux["n_views"]), list(aux["view_off"]), list(aux["weights"]))
         else:
-            torch.ops.gpsa.elbo_loss_fwd(Fc, Yc, nz, idx, klc, float(aux["kl_scale"]), loss, ll, ws)
-        ctx.aux, ctx.args = aux, (Fc, Yc, nz, idx, shapes, fused)
+            name = "elbo_loss_fused" if tabs else "elbo_loss"
+        getattr(torch.ops.gpsa, name + "_fwd")(Fc, Yc, nz, idx, *tabs, klc, float(aux["kl_scale"]), loss, ll, ws)
+        ctx.aux, ctx.args = aux, (name, Fc, Yc, nz, idx, tabs, fused)
         ctx.lmc, ctx.n_w = lmc_saved, len(Ws)
         ctx.n_kl = 0 if klc is None else klc.numel()
+        # (the kernels see kl flat and fp64; its gradient goes back in kl's own shape and dtype)
+        ctx.kl_meta = None if (kl is None or (kl.dim() == 1 and kl.dtype == torch.float64)) else (kl.shape, kl.dtype)
         ctx.noise_meta = (noise.shape, noise.dtype)
         return loss.reshape(())
 
@@ -833,7 +851,7 @@ class ElboLossFn(torch.autograd.Function):
     def backward(ctx, gloss):
         aux = ctx.aux
         fuse = aux.get("fuse")
-        Fc, Yc, nz, idx, shapes, fused = ctx.args
+        name, Fc, Yc, nz, idx, tabs, fused = ctx.args
         g, dF, dnoise, dkl, ws = _loss_grad_buffers(gloss, Fc, nz, ctx.n_kl, fused)
         if fuse is not None and any(z and i not in ctx.lmc for i, z in enumerate(fused)):
             # StepFn.backward hands it to the engine (gpsa_step_out_grads.gloss); loss_fn called twice on one forward: summed
@@ -842,47 +860,14 @@ class ElboLossFn(torch.autograd.Function):
         for i, (dFl, dW, wpos) in ctx.lmc.items():  # formed at upstream gradient 1 by the forward: scaled here
             dF[i] = dFl * g
             dWs[wpos] = dW * g
-        if any(fused):
-            real = [d if not z else g for d, z in zip(dF, fused)]  # (mutable-argument list: no expanded tensors in it)
-            torch.ops.gpsa.elbo_loss_fused_bwd(Fc, Yc, nz, idx, shapes, [int(z) for z in fused], g, int(ctx.n_kl),
-                                               float(aux["kl_scale"]), real, dnoise, dkl, ws)
-        else:
-            torch.ops.gpsa.elbo_loss_bwd(Fc, Yc, nz, idx, g, int(ctx.n_kl), float(aux["kl_scale"]), dF, dnoise, dkl, ws)
-        return _loss_grads(ctx, dnoise, dkl, dF, dWs)
-
-
-class WeightedElboLossFn(torch.autograd.Function):
-    """ElboLossFn with per-view weights (minibatch training, minibatch.py):
-    loss = -(sum_i sum_v w_iv LL_iv) + kl_scale * sum(kl)  as one C call each way (gpsa_elbo_loss_weighted_fwd / _bwd).
-    inputs: noise_variance [n], kl (any shape) or None, F_0 .. F_{n_ll-1} (materialised draws [S, N_i, P_i]);
-    aux: Y tensors, noise indices, kl_scale, n_views (per term), view_off (every term's n_views + 1 row offsets,
-    concatenated), weights (per term a device fp64 tensor of n_views entries)"""
-
-    @staticmethod
-    def forward(ctx, aux, noise, kl, *Fs):
-        Fc, Yc, nz, klc = _loss_inputs(Fs, aux["Y"], noise, kl, flat_kl=True)
-        loss, ll, ws = _loss_outputs(len(Fs), Fs[0].device)
-        idx = [int(j) for j in aux["noise_idx"]]
-        torch.ops.gpsa.elbo_loss_weighted_fwd(Fc, Yc, nz, idx, list(aux["n_views"]), list(aux["view_off"]),
-                                              list(aux["weights"]), klc, float(aux["kl_scale"]), loss, ll, ws)
-        ctx.aux, ctx.args = aux, (Fc, Yc, nz, idx)
-        ctx.n_kl = 0 if klc is None else klc.numel()
-        ctx.kl_meta = None if kl is None else (kl.shape, kl.dtype)
-        ctx.noise_meta = (noise.shape, noise.dtype)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, gloss):
-        aux = ctx.aux
-        Fc, Yc, nz, idx = ctx.args
-        g, dF, dnoise, dkl, ws = _loss_grad_buffers(gloss, Fc, nz, ctx.n_kl)
-        torch.ops.gpsa.elbo_loss_weighted_bwd(Fc, Yc, nz, idx, list(aux["n_views"]), list(aux["view_off"]),
-                                              list(aux["weights"]), g, int(ctx.n_kl), float(aux["kl_scale"]), dF,
-                                              dnoise, dkl, ws)
-        if dkl is not None:
+        # (mutable-argument list: no expanded tensors in it - a fused term's slot holds g, its dF is not written)
+        real = [d if not z else g for d, z in zip(dF, fused)] if any(fused) else dF
+        getattr(torch.ops.gpsa, name + "_bwd")(Fc, Yc, nz, idx, *tabs, g, int(ctx.n_kl), float(aux["kl_scale"]), real,
+                                               dnoise, dkl, ws)
+        if ctx.kl_meta is not None:
             kshape, kdt = ctx.kl_meta
             dkl = dkl.reshape(kshape).to(kdt)
-        return _loss_grads(ctx, dnoise, dkl, dF)
+        return _loss_grads(ctx, dnoise, dkl, dF, dWs)
 
 
 _NOBS_CACHE_MAX = 8
@@ -913,69 +898,3 @@ def observed_counts(model, Yc, views, cacheable):
             cache.clear()
         cache[key] = ([weakref.ref(y) for y in Yc], nobs)
     return nobs
-
-
-class SkipElboLossFn(torch.autograd.Function):
-    """ElboLossFn and WeightedElboLossFn over partly observed outputs (``model.skip_missing``): a NaN in Y is a missing
-    observation, and the loss is the ELBO of the observed entries - gpsa_elbo_loss_skip_fwd / _bwd, one C call each way.
-    inputs and aux as ElboLossFn (fused terms: aux["fuse_mods"], aux["lmc"], aux["term_shapes"]; an LMC term runs
-    gpsa_lmc_loglik_fused_skip_f32 here) plus, optionally, WeightedElboLossFn's n_views / view_off / weights (then every
-    term comes from its draws); aux["nobs"]: the terms' observed counts (observed_counts)."""
-
-    @staticmethod
-    def forward(ctx, aux, noise, kl, *ins):
-        n = len(aux["Y"])
-        Fs, Ws = ins[:n], ins[n:]
-        partial = aux.get("fuse_mods") is not None
-        fused = [bool(z) for z in aux["fuse_mods"]] if partial else [False] * n
-        lmc = (aux.get("lmc") or {}) if partial else {}
-        dev = Fs[0].device
-        Fc, Yc, nz, klc = _loss_inputs(Fs, aux["Y"], noise, kl, fused, flat_kl=True)
-        idx = [int(j) for j in aux["noise_idx"]]
-        lmc_saved = {}
-        for i, wpos in lmc.items():
-            Fl, W = Fc[i], Ws[wpos].detach()
-            S_, N_, L_ = (int(d) for d in Fl.shape)
-            nparts = int(_lib.load().gpsa_quadform_elbo_parts())
-            zpart = torch.empty(nparts, dtype=torch.float64, device=dev)
-            dFl, dW = torch.empty_like(Fl), torch.empty_like(W)
-            wsl = _ops_mod.get_ops()._ws(int(_lib.load().gpsa_lmc_loglik_workspace(S_ * N_, L_, int(W.shape[1]), nparts)),
-                                         Fl)
-            torch.ops.gpsa.lmc_loglik_fused_skip(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
-            lmc_saved[i] = (dFl, dW, wpos)
-            Fc[i] = zpart
-        loss, ll, ws = _loss_outputs(n, dev)
-        shapes, fl = [], []
-        if any(fused):
-            for i in range(n):
-                shapes += list(aux["term_shapes"][i]) if fused[i] else [int(d) for d in Fc[i].shape]
-            fl = [int(z) for z in fused]
-        views = (list(aux["n_views"]), list(aux["view_off"]), list(aux["weights"])) if "weights" in aux else ([], [], [])
-        tabs = (shapes, fl) + views + (list(aux["nobs"]),)
-        torch.ops.gpsa.elbo_loss_skip_fwd(Fc, Yc, nz, idx, *tabs, klc, float(aux["kl_scale"]), loss, ll, ws)
-        ctx.aux, ctx.args = aux, (Fc, Yc, nz, idx, tabs, fused)
-        ctx.lmc, ctx.n_w = lmc_saved, len(Ws)
-        ctx.n_kl = 0 if klc is None else klc.numel()
-        ctx.kl_meta = None if kl is None else (kl.shape, kl.dtype)
-        ctx.noise_meta = (noise.shape, noise.dtype)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, gloss):
-        aux = ctx.aux
-        fuse = aux.get("fuse")
-        Fc, Yc, nz, idx, tabs, fused = ctx.args
-        g, dF, dnoise, dkl, ws = _loss_grad_buffers(gloss, Fc, nz, ctx.n_kl, fused)
-        if fuse is not None and any(z and i not in ctx.lmc for i, z in enumerate(fused)):
-            fuse["gloss"] = g if fuse.get("gloss") is None else fuse["gloss"] + g
-        dWs = [None] * ctx.n_w
-        for i, (dFl, dW, wpos) in ctx.lmc.items():  # formed at upstream gradient 1 by the forward: scaled here
-            dF[i] = dFl * g
-            dWs[wpos] = dW * g
-        real = [d if not z else g for d, z in zip(dF, fused)]
-        torch.ops.gpsa.elbo_loss_skip_bwd(Fc, Yc, nz, idx, *tabs, g, int(ctx.n_kl), float(aux["kl_scale"]), real, dnoise,
-                                          dkl, ws)
-        if dkl is not None:
-            kshape, kdt = ctx.kl_meta
-            dkl = dkl.reshape(kshape).to(kdt)
-        return _loss_grads(ctx, dnoise, dkl, dF, dWs)

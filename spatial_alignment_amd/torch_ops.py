@@ -22,9 +22,12 @@ each with
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
                                             gpsa::elbo_loss_fwd / _bwd, gpsa::adam_step  grid_example.py:59-78)
    minibatch training (opt-in)              gpsa::row_sample_gather,                   (minibatch.py)
-                                            gpsa::elbo_loss_weighted_fwd / _bwd
-   partly observed outputs (opt-in)         gpsa::count_observed, gpsa::elbo_loss_skip_fwd / _bwd,
+                                            gpsa::elbo_loss_weighted_fwd / _bwd        (csrc/loss_views.hip)
+   partly observed outputs (opt-in)         gpsa::count_observed, gpsa::elbo_loss_skip_fwd / _bwd (csrc/loss_views.hip),
                                             gpsa::lmc_loglik_fused_skip                (model.skip_missing)
+
+The six elbo_loss ops share their table builders (``_ll_arrays``, ``_grad_arrays``, ``_view_tables``) and are what the
+one loss node, ``step_engine.ElboLossFn``, chooses among.
 
 The step-engine ops are the ones ``VariationalGPSA.forward`` / ``loss_fn`` / ``FusedAdam`` go through
 (step_engine.py, optim.py): they mutate caller-allocated tensors (outputs, arenas, the flat gradient buffer) and
@@ -449,8 +452,8 @@ _engine_op("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avg,
 
 
 # ---------------------------------------------------------------------------------------------------------
-# minibatch (stochastic variational) training: the batch sampler-gather and the per-view weighted likelihood
-# (minibatch.py, csrc/minibatch.hip)
+# minibatch (stochastic variational) training: the batch sampler-gather (minibatch.py, csrc/minibatch.hip) and the
+# per-view weighted likelihood (csrc/loss_views.hip)
 # ---------------------------------------------------------------------------------------------------------
 def _row_sample_gather(Xs, Ys, n_views, n_rows, batch, seed, counter, rows, Xb, Yb):
     """gpsa_row_sample_gather: step counter[0]'s batch of every (modality, view) - row numbers, coordinates and
@@ -470,22 +473,27 @@ _engine_op("row_sample_gather(Tensor[] Xs, Tensor[] Ys, int[] n_views, int[] n_r
            "Tensor(a!) counter, Tensor(b!)[] rows, Tensor(c!)[] Xb, Tensor(d!)[] Yb) -> ()", _row_sample_gather)
 
 
-def _view_arrays(n_views, view_off):
-    """flattened per-term view offsets -> (n_views int array, host array of pointers to each term's offsets, keep)"""
-    n = len(n_views)
-    offs, at = [], 0
-    for nv in n_views:
-        offs.append((C.c_longlong * (int(nv) + 1))(*[int(x) for x in view_off[at:at + int(nv) + 1]]))
-        at += int(nv) + 1
-    return (C.c_int * n)(*[int(x) for x in n_views]), (C.c_void_p * n)(*[C.addressof(o) for o in offs]), offs
+def _view_tables(n, n_views, view_off, weights=(), nobs=()):
+    """the per-view tables of n terms as the C entries take them -> (n_views, view_off, w, nobs, keep): the int array of
+    the terms' view counts, a host array of pointers to each term's row offsets (view_off: every term's n_views + 1
+    offsets, concatenated), host arrays of the terms' weight and count pointers, and what keeps the offsets alive.  An
+    absent table (empty list) is NULL"""
+    ptrs = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts]) if ts else None
+    nv, offp, offs = None, None, []
+    if n_views:
+        at = 0
+        for v in n_views:
+            offs.append((C.c_longlong * (int(v) + 1))(*[int(x) for x in view_off[at:at + int(v) + 1]]))
+            at += int(v) + 1
+        nv, offp = (C.c_int * n)(*[int(x) for x in n_views]), (C.c_void_p * n)(*[C.addressof(o) for o in offs])
+    return nv, offp, ptrs(weights), ptrs(nobs), offs
 
 
 def _elbo_loss_weighted_fwd(Fs, Ys, noise, noise_idx, n_views, view_off, weights, kl, kl_scale, loss, ll, ws):
     """gpsa_elbo_loss_fwd with per-view fp64 weights: loss = -sum_m sum_v w_mv LL_mv + kl_scale * sum(kl)
     (view_off: every term's n_views + 1 row offsets, concatenated)"""
     n, terms, _, _ = _ll_arrays(Fs, Ys, noise, noise_idx)
-    nv, offp, _keep = _view_arrays(n_views, view_off)
-    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
+    nv, offp, Wp, _, _keep = _view_tables(n, n_views, view_off, weights)
     _lib.check(_lib.load().gpsa_elbo_loss_weighted_fwd(n, *terms, nv, offp, Wp, *_kl_args(kl), float(kl_scale),
                                                        loss.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(),
                                                        _raw_stream(loss.device.index)), "gpsa_elbo_loss_weighted_fwd")
@@ -499,8 +507,7 @@ _engine_op("elbo_loss_weighted_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[]
 def _elbo_loss_weighted_bwd(Fs, Ys, noise, noise_idx, n_views, view_off, weights, gloss, n_kl, kl_scale, dFs, dnoise,
                             dkl, ws):
     n, terms, _, _ = _ll_arrays(Fs, Ys, noise, noise_idx)
-    nv, offp, _keep = _view_arrays(n_views, view_off)
-    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights])
+    nv, offp, Wp, _, _keep = _view_tables(n, n_views, view_off, weights)
     grads = _grad_arrays(dFs, dnoise, noise_idx)
     _lib.check(_lib.load().gpsa_elbo_loss_weighted_bwd(n, *terms, nv, offp, Wp, gloss.data_ptr(), int(n_kl),
                                                        float(kl_scale), *grads, 0 if dkl is None else dkl.data_ptr(),
@@ -514,17 +521,10 @@ _engine_op("elbo_loss_weighted_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[]
 
 
 # ---------------------------------------------------------------------------------------------------------
-# partly observed outputs (model.skip_missing; csrc/missing.hip): a NaN in Y is a missing observation
+# partly observed outputs (model.skip_missing; csrc/missing.hip, csrc/loss_views.hip): a NaN in Y is a missing observation
 # ---------------------------------------------------------------------------------------------------------
 def count_workspace_bytes():
     return int(_lib.load().gpsa_count_observed_workspace()) + 64
-
-
-def _opt_views(n, n_views, view_off):
-    """(n_views, view_off) of the ops (empty lists: no views) -> the C tables or NULLs, and what keeps them alive"""
-    if not n_views:
-        return None, None, None
-    return _view_arrays(n_views, view_off)
 
 
 def _count_observed(Ys, n_views, view_off, nobs, ws):
@@ -532,7 +532,7 @@ def _count_observed(Ys, n_views, view_off, nobs, ws):
     device doubles written without a host read"""
     n = len(Ys)
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-    nv, offp, _keep = _opt_views(n, n_views, view_off)
+    nv, offp, _, _, _keep = _view_tables(n, n_views, view_off)
     _lib.check(_lib.load().gpsa_count_observed(n, arr(Ys), (C.c_longlong * n)(*[int(y.shape[0]) for y in Ys]),
                                                (C.c_int * n)(*[int(y.shape[1]) for y in Ys]), nv, offp, arr(nobs),
                                                ws.data_ptr(), ws.numel(), _raw_stream(ws.device.index)),
@@ -543,18 +543,12 @@ _engine_op("count_observed(Tensor[] Ys, int[] n_views, int[] view_off, Tensor(a!
            _count_observed)
 
 
-def _skip_tables(n, n_views, view_off, weights, nobs):
-    nv, offp, keep = _opt_views(n, n_views, view_off)
-    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in weights]) if weights else None
-    return nv, offp, Wp, (C.c_void_p * n)(*[t.data_ptr() for t in nobs]), keep
-
-
 def _elbo_loss_skip_fwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, kl, kl_scale, loss, ll,
                         ws):
     """gpsa_elbo_loss_skip_fwd: the ELBO loss over the observed entries (fused: per term, "F" is its partial sums of z^2;
     shapes as elbo_loss_fused_fwd, both empty without fused terms; n_views / view_off / weights empty: none)"""
     n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
-    nv, offp, Wp, Np, _keep = _skip_tables(n, n_views, view_off, weights, nobs)
+    nv, offp, Wp, Np, _keep = _view_tables(n, n_views, view_off, weights, nobs)
     _lib.check(_lib.load().gpsa_elbo_loss_skip_fwd(n, *terms, Zp, nparts, nv, offp, Wp, Np, *_kl_args(kl), float(kl_scale),
                                                    loss.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(),
                                                    _raw_stream(loss.device.index)), "gpsa_elbo_loss_skip_fwd")
@@ -568,7 +562,7 @@ _engine_op("elbo_loss_skip_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noi
 def _elbo_loss_skip_bwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, gloss, n_kl, kl_scale,
                         dFs, dnoise, dkl, ws):
     n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
-    nv, offp, Wp, Np, _keep = _skip_tables(n, n_views, view_off, weights, nobs)
+    nv, offp, Wp, Np, _keep = _view_tables(n, n_views, view_off, weights, nobs)
     grads = _grad_arrays(dFs, dnoise, noise_idx, fused or None)
     _lib.check(_lib.load().gpsa_elbo_loss_skip_bwd(n, *terms, Zp, nparts, nv, offp, Wp, Np, gloss.data_ptr(), int(n_kl),
                                                    float(kl_scale), *grads, 0 if dkl is None else dkl.data_ptr(),

@@ -163,3 +163,68 @@ def test_quadform_workspace_queries_match_the_recorded_table():
     for key, want in rec["values"].items():
         bad = [i for i, (a, b) in enumerate(zip(got[key], want)) if a != b]
         assert len(got[key]) == len(want) and not bad, (key, bad[:5], [got[key][i] for i in bad[:5]], [want[i] for i in bad[:5]])
+
+
+# ---- the per-view loss entries' argument checks (host only: every refusal returns before a stream is touched) --------
+_VIEW_N = 12  # rows of every term below
+# what is wrong with a term -> (n_views, its row offsets); None: the views are good and the fault is elsewhere
+_BAD_VIEWS = {"off[0] != 0": (3, [1, 4, 8, 12]), "off[V] != N": (3, [0, 4, 8, 11]), "decreasing": (3, [0, 8, 4, 12]),
+              "V = 0": (0, [0]), "V = 65": (65, list(range(65)) + [12]), "null weight row": None,
+              "null counts row": None, "fused term with two views": (2, [0, 5, 12])}
+# the return code of every case at a77545a (read off that commit's checks: views_ok / skip_views_ok, the `!w[i]` and
+# `!nobs[i]` tests and the fused term's `n_views[i] != 1`, all GPSA_EINVAL): the shared check must give the same
+_VIEW_CODES = {kind: -1 for kind in _BAD_VIEWS}
+
+
+def _per_view_call(lib, family, direction, kind, second):
+    """one call of gpsa_elbo_loss_{weighted,skip}_{fwd,bwd} whose last term is wrong in the way ``kind`` names (with
+    ``second`` a good term stands in front of it); device pointers are the dummy address 8, never dereferenced"""
+    import ctypes as C
+
+    n = 2 if second else 1
+    bad = n - 1
+    good_off = (C.c_longlong * 4)(0, 4, 8, _VIEW_N)
+    nv, offs = [3] * n, [good_off] * n
+    if _BAD_VIEWS[kind] is not None:
+        nv[bad] = _BAD_VIEWS[kind][0]
+        offs[bad] = (C.c_longlong * len(_BAD_VIEWS[kind][1]))(*_BAD_VIEWS[kind][1])
+    ptr = lambda null_at=None: (C.c_void_p * n)(*[None if i == null_at else 8 for i in range(n)])
+    terms = (n, ptr(), ptr(), ptr(), (C.c_int * n)(*[2] * n), (C.c_longlong * n)(*[_VIEW_N] * n), (C.c_int * n)(*[3] * n))
+    views = ((C.c_int * n)(*nv), (C.c_void_p * n)(*[C.addressof(o) for o in offs]),
+             ptr(bad if kind == "null weight row" else None))
+    if family == "skip":
+        zpart = (C.c_void_p * n)(*[8 if (kind == "fused term with two views" and i == bad) else None for i in range(n)])
+        views = (zpart, 4) + views + (ptr(bad if kind == "null counts row" else None),)
+    ws = (C.c_void_p(8), 8 * 4100 * n, None)
+    if direction == "fwd":
+        tail = (C.c_void_p(8), 3, 1.0, C.c_void_p(8), C.c_void_p(8)) + ws
+    else:
+        tail = (C.c_void_p(8), 3, 1.0, ptr(), ptr(), C.c_void_p(8), 4, C.c_void_p(8)) + ws
+    return getattr(lib, f"gpsa_elbo_loss_{family}_{direction}")(*terms, *views, *tail)
+
+
+def _per_view_cases(family):
+    return [k for k in _BAD_VIEWS if family == "skip" or k not in ("null counts row", "fused term with two views")]
+
+
+def test_per_view_entries_share_one_check():
+    """the weighted and the skip entries refuse every malformed view table, a missing weight row, a missing counts row
+    and a fused term with views of its own with the code they returned before they shared the check"""
+    lib = _lib.load()
+    for family in ("weighted", "skip"):
+        for kind in _per_view_cases(family):
+            for direction in ("fwd", "bwd"):
+                assert _per_view_call(lib, family, direction, kind, second=False) == _VIEW_CODES[kind], (family, kind,
+                                                                                                          direction)
+
+
+def test_bad_second_term_is_refused_before_any_launch():
+    """the same with a good term in front of the bad one: the refusal is the check's own code, so it came back before the
+    first term's launch (off a device a launch would have answered with the runtime's error, on one it would have
+    written through the dummy pointers)"""
+    lib = _lib.load()
+    for family in ("weighted", "skip"):
+        for kind in _per_view_cases(family):
+            for direction in ("fwd", "bwd"):
+                assert _per_view_call(lib, family, direction, kind, second=True) == _lib.GPSA_EINVAL, (family, kind,
+                                                                                                        direction)

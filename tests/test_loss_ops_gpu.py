@@ -80,14 +80,29 @@ def _guards_nan(buf):
 
 # ---- the terms ------------------------------------------------------------------------------------------------------
 class Term:
-    """one likelihood term on the host: plain (F [S, N, P], Y [N, P]), weighted (the same + views, w) or fused (zpart)"""
+    """one likelihood term on the host: plain (F [S, N, P], Y [N, P]), weighted (the same + views, w) or fused (zpart).
+    For the skip op: miss [N, P] marks the missing entries of Y (the device gets NaN there); a fused term carries its
+    observed count as nobs"""
 
-    def __init__(self, shape, slot, F=None, Y=None, zpart=None, views=None, w=None, sentinels=()):
+    def __init__(self, shape, slot, F=None, Y=None, zpart=None, views=None, w=None, sentinels=(), miss=None, nobs=None):
         self.S, self.N, self.P = shape
         self.tot = self.S * self.N * self.P
         self.slot, self.F, self.Y, self.zpart, self.views, self.w = slot, F, Y, zpart, views, w
         self.fused = zpart is not None
         self.sentinels = list(sentinels)
+        self.miss, self.nobs = miss, nobs
+
+    def view_bounds(self):
+        return [0, self.N] if self.views is None else [int(x) for x in np.cumsum([0] + list(self.views))]
+
+    def counts(self):
+        """the observed entries of Y per view (a fused term: its nobs; no mask: all of them)"""
+        if self.fused:
+            return [float(self.N * self.P if self.nobs is None else self.nobs)]
+        off = self.view_bounds()
+        if self.miss is None:
+            return [float((b - a) * self.P) for a, b in zip(off, off[1:])]
+        return [float((~self.miss[a:b]).sum()) for a, b in zip(off, off[1:])]
 
 
 def _blocks(tot):  # the grid of the plain kernels as the sentinels assume it (the checks do not depend on it)
@@ -139,10 +154,25 @@ def _weighted_term(S, P, views, slot, noise, seed):
     return Term((S, N, P), slot, F=F, Y=Y, views=list(views), w=w, sentinels=pos)
 
 
-def _fused_term(shape, slot, nparts, seed):
+def _fused_term(shape, slot, nparts, seed, nobs=None, w=None):
     gen = torch.Generator().manual_seed(seed)
     zpart = torch.exp(torch.rand(nparts, generator=gen, dtype=torch.float64) * 30 - 20)  # positive, a wide spread
-    return Term(shape, slot, zpart=zpart, Y=torch.zeros(shape[1], shape[2]))
+    return Term(shape, slot, zpart=zpart, Y=torch.zeros(shape[1], shape[2]), nobs=nobs, w=w,
+                views=None if w is None else [shape[1]])
+
+
+def _masked(t, seed, dead_views=()):
+    """t with 30 % of its entries missing - never a sentinel - and every entry of the ``dead_views``, sentinels included"""
+    gen = torch.Generator().manual_seed(seed)
+    NP = t.N * t.P
+    miss = torch.rand(t.N, t.P, generator=gen) < 0.3
+    miss.view(-1)[[i % NP for i in t.sentinels]] = False
+    off = t.view_bounds()
+    for v in dead_views:
+        miss[off[v]:off[v + 1]] = True
+    t.sentinels = [i for i in t.sentinels if not bool(miss.view(-1)[i % NP])]
+    t.miss = miss
+    return t
 
 
 # ---- fp64 reference -------------------------------------------------------------------------------------------------
@@ -162,23 +192,32 @@ def _reference(terms, noise, kl, glosses=GLOSS):
         cst = -torch.log(s) - HALF_LOG_2PI
         if t.fused:
             z2 = math.fsum(t.zpart.tolist())
+            tot = t.S * t.counts()[0]  # (S N P, or S nobs under the skip op)
+            w0 = 1.0 if t.w is None else float(t.w[0])
             # (sum z^2 = Q / s^2 with Q fixed: d ll / d s = (z2 - tot) / s / S)
-            lls.append((-0.5 * z2 * (s.detach() / s) ** 2 + cst * t.tot) / t.S)
+            lls.append(w0 * (-0.5 * z2 * (s.detach() / s) ** 2 + cst * tot) / t.S)
             F64.append(None)
-            r.groups.append([(1.0, z2, t.tot)])
+            r.groups.append([(w0, z2, tot)])
             continue
         F = t.F.double().requires_grad_()
-        z = (t.Y.double() - F) / s
         F64.append(F)
+        if t.miss is None:
+            z = (t.Y.double() - F) / s
+            lp = -0.5 * z ** 2 + cst
+        else:  # the observed entries only (the others' Y is NaN on the device: a zero stands in here)
+            obs = (~t.miss).double()
+            z = (torch.where(t.miss, torch.zeros_like(t.Y), t.Y).double() - F) / s * obs
+            lp = (-0.5 * z ** 2 + cst) * obs
         z2_row = (z.detach() ** 2).sum((0, 2))
         if t.views is None:
-            lls.append((-0.5 * z ** 2 + cst).sum() / t.S)
-            r.groups.append([(1.0, float(z2_row.sum()), t.tot)])
+            lls.append(lp.sum() / t.S)
+            r.groups.append([(1.0, float(z2_row.sum()), t.S * t.counts()[0])])
         else:
-            per_row = (-0.5 * z ** 2 + cst).sum((0, 2)) / t.S
-            off = np.cumsum([0] + t.views)
-            lls.append(sum(t.w[v] * per_row[off[v]:off[v + 1]].sum() for v in range(len(t.views))))
-            r.groups.append([(float(t.w[v]), float(z2_row[off[v]:off[v + 1]].sum()), t.S * t.views[v] * t.P)
+            per_row = lp.sum((0, 2)) / t.S
+            off, cnt = t.view_bounds(), t.counts()
+            w = torch.ones(len(t.views), dtype=torch.float64) if t.w is None else t.w
+            lls.append(sum(w[v] * per_row[off[v]:off[v + 1]].sum() for v in range(len(t.views))))
+            r.groups.append([(float(w[v]), float(z2_row[off[v]:off[v + 1]].sum()), t.S * cnt[v])
                              for v in range(len(t.views))])
     loss = -sum(lls) if k64 is None else KL_SCALE * k64.sum() - sum(lls)
     r.loss, r.ll = float(loss.detach()), [float(x.detach()) for x in lls]
@@ -198,8 +237,8 @@ def _reference(terms, noise, kl, glosses=GLOSS):
 def _ll_bound(t, groups, noise):
     if t.fused:
         _, s = _std(noise, t.slot)
-        (_, z2, tot), = groups
-        return t.zpart.numel() * U52 * (0.5 * z2 + abs(-math.log(s) - HALF_LOG_2PI) * tot) / t.S
+        (w, z2, tot), = groups
+        return abs(w) * t.zpart.numel() * U52 * (0.5 * z2 + abs(-math.log(s) - HALF_LOG_2PI) * tot) / t.S
     return sum(abs(w) * U20 * 0.5 * z2 / t.S for w, z2, _ in groups)
 
 
@@ -236,12 +275,15 @@ class Out:
 
 
 def _device(op, terms, noise, kl, gloss, with_dkl=True, n_kl=None):
-    """forward and backward of one op ("plain", "fused", "weighted") with poisoned workspace and outputs -> Out (CPU)"""
+    """forward and backward of one op ("plain", "fused", "weighted", "skip") with poisoned workspace and outputs -> Out
+    (CPU).  "skip": NaN at the terms' missing entries, the counts as device doubles; the view and weight tables go along
+    when the first term has them (then every term does), the fused tables when a term is fused"""
     _, T = _lib()
     n = len(terms)
     d = lambda t: t.to(DEV).contiguous()
     Fd = [d(t.zpart if t.fused else t.F) for t in terms]
-    Yd, nd = [d(t.Y) for t in terms], d(noise)
+    Yd = [d(t.Y if t.miss is None else torch.where(t.miss, torch.full_like(t.Y, NAN), t.Y)) for t in terms]
+    nd = d(noise)
     kd = None if kl is None else d(kl)
     idx = [t.slot for t in terms]
     shapes = [x for t in terms for x in (t.S, t.N, t.P)]
@@ -259,23 +301,31 @@ def _device(op, terms, noise, kl, gloss, with_dkl=True, n_kl=None):
     dkl = torch.full((n_kl,), NAN, dtype=torch.float64, device=DEV) if with_dkl else None
     gl = torch.tensor([gloss], dtype=torch.float32, device=DEV)
     o = Out()
-    if op == "weighted":
+    nv, off, wd = [], [], []
+    if op == "weighted" or (op == "skip" and terms[0].views is not None):
         nv = [len(t.views) for t in terms]
-        off = [int(x) for t in terms for x in np.cumsum([0] + t.views)]
-        wd = [d(t.w) for t in terms]
+        off = [x for t in terms for x in t.view_bounds()]
+        wd = [d(t.w) for t in terms] if terms[0].w is not None else []
+    if op == "skip":
+        tabs = (shapes, fused) if any(fused) else ([], [])
+        tabs += (nv, off, wd, [torch.tensor(t.counts(), dtype=torch.float64, device=DEV) for t in terms])
     if op == "plain":
         torch.ops.gpsa.elbo_loss_fwd(Fd, Yd, nd, idx, kd, KL_SCALE, loss, ll, ws)
     elif op == "fused":
         torch.ops.gpsa.elbo_loss_fused_fwd(Fd, Yd, nd, idx, shapes, fused, kd, KL_SCALE, loss, ll, ws)
-    else:
+    elif op == "weighted":
         torch.ops.gpsa.elbo_loss_weighted_fwd(Fd, Yd, nd, idx, nv, off, wd, kd, KL_SCALE, loss, ll, ws)
+    else:
+        torch.ops.gpsa.elbo_loss_skip_fwd(Fd, Yd, nd, idx, *tabs, kd, KL_SCALE, loss, ll, ws)
     ws.fill_(0xFF)
     if op == "plain":
         torch.ops.gpsa.elbo_loss_bwd(Fd, Yd, nd, idx, gl, n_kl, KL_SCALE, dFs, dnoise, dkl, ws)
     elif op == "fused":
         torch.ops.gpsa.elbo_loss_fused_bwd(Fd, Yd, nd, idx, shapes, fused, gl, n_kl, KL_SCALE, dFs, dnoise, dkl, ws)
-    else:
+    elif op == "weighted":
         torch.ops.gpsa.elbo_loss_weighted_bwd(Fd, Yd, nd, idx, nv, off, wd, gl, n_kl, KL_SCALE, dFs, dnoise, dkl, ws)
+    else:
+        torch.ops.gpsa.elbo_loss_skip_bwd(Fd, Yd, nd, idx, *tabs, gl, n_kl, KL_SCALE, dFs, dnoise, dkl, ws)
     torch.cuda.synchronize()
     o.loss, o.ll, o.dnoise = float(loss), ll.cpu(), dnoise.cpu()
     o.dkl = None if dkl is None else dkl.cpu()
@@ -299,6 +349,8 @@ def _check(tag, terms, noise, kl, ref, out, g):
         else:
             want = ref.dF[g][i]
             _within(f"{tag} dF", out.dF[i], want, 4 * U24 * want.abs())
+            if t.miss is not None:  # exactly +-0 at a missing entry
+                assert bool((out.dF[i][:, t.miss] == 0).all()), f"{tag}: term {i}: dF at a missing entry"
         want = float(ref.dnoise[g][t.slot])
         _within(f"{tag} dnoise" + (" (fused term)" if t.fused else ""), out.dnoise[t.slot], want,
                 _dnoise_bound(t, ref.groups[i], noise, g, want))
@@ -533,8 +585,76 @@ def test_weighted_refusals(kind):
     assert bool((ws == 0xFF).all()), f"{kind}: the workspace was written by a refused call"
 
 
+# ---- the view table's edges, for both per-view op pairs (weighted, skip) ---------------------------------------------
+ONE_VIEW = (2, 3, [37])  # V = 1
+EDGE_EMPTY = (3, 5, [0, 0] + [i * 5 % 4 + 1 for i in range(38)] + [0] + [i * 3 % 4 + 1 for i in range(22)] + [0])
+# (64 views, four of them empty: the first two, one inside and the last)
+CAP_BINDS = (2, 64, [i % 3 + 1 for i in range(20)] + [600] + [i % 3 + 1 for i in range(43)])
+# (64 views of 1-3 rows and one of 600: 76 800 elements against 4096 / 64 = 64 blocks of 1024, a second sweep)
+VIEW_EDGES = {"one_view": ONE_VIEW, "empty_views": EDGE_EMPTY, "cap_binds": CAP_BINDS}
+
+
+def test_view_edge_cases_are_what_they_say():
+    for S, P, views in (EDGE_EMPTY, CAP_BINDS):
+        assert len(views) == 64
+    v = EDGE_EMPTY[2]
+    assert v[0] == 0 and v[1] == 0 and v[40] == 0 and v[63] == 0 and sum(x == 0 for x in v) == 4
+    S, P, views = CAP_BINDS
+    assert max(views) == 600 and S * P * 600 == 76800 > 64 * 1024 and sorted(set(views) - {600}) == [1, 2, 3]
+
+
+@pytest.mark.parametrize("case", sorted(VIEW_EDGES))
+@pytest.mark.parametrize("op", ["weighted", "skip"])
+def test_view_table_edges(op, case):
+    S, P, views = VIEW_EDGES[case]
+    noise = _noise(1)
+    t = _weighted_term(S, P, views, 1, noise, seed=60)
+    if op == "skip":
+        t = _masked(t, seed=61)
+    ref = _reference([t], noise, _kl(7))
+    whole, whole_dn, own = _sentinels_bite(t, ref.groups[0], noise)
+    assert own > 1000 and whole > 100 and whole_dn > 100, (own, whole, whole_dn)  # (as _check_weighted)
+    for g in GLOSS:
+        _check(op, [t], noise, _kl(7), ref, _device(op, [t], noise, _kl(7), g), g)
+
+
+def test_skip_one_view_without_tables():
+    """the skip op without a view table and without weights: the term is one view of its N rows"""
+    noise = _noise(1)
+    t = _masked(_plain_term((3, 333, 7), 1, noise, seed=62), seed=63)
+    ref = _reference([t], noise, _kl(7))
+    bite_ll, bite_dn, _ = _sentinels_bite(t, ref.groups[0], noise)
+    assert bite_ll > 1000 and bite_dn > 1000, (bite_ll, bite_dn)
+    for g in GLOSS:
+        _check("skip", [t], noise, _kl(7), ref, _device("skip", [t], noise, _kl(7), g), g)
+
+
+@pytest.mark.parametrize("nparts", [1, 257])
+def test_skip_fused_term_then_draws_term(nparts):
+    """two terms in one skip call: term 0 arrives as partial sums (one view, its own weight and count), term 1 comes from
+    its draws into the SECOND workspace slot, with one view that has no observed entry and one that is empty.  The
+    zero-fill of the noise gradient and dkl ride on the first (fused) term's finishing launch: the unnamed noise
+    gradients are +0.0, dkl is written, the fused term's dF is not touched (_check)"""
+    noise = _noise(2)
+    w0 = torch.tensor([1.7], dtype=torch.float64) / 3
+    fused = _fused_term((2, 50, 4), 3, nparts, seed=64, nobs=271.0, w=w0)
+    draws = _masked(_weighted_term(3, 7, [20, 1500, 0, 33], 0, noise, seed=65), seed=66, dead_views=[0])
+    assert draws.counts()[0] == 0.0 and draws.counts()[2] == 0.0 and draws.counts()[1] > 0 and draws.counts()[3] > 0
+    terms = [fused, draws]
+    ref = _reference(terms, noise, _kl(7))
+    whole, whole_dn, own = _sentinels_bite(draws, ref.groups[1], noise)
+    assert own > 1000 and whole > 100 and whole_dn > 100, (own, whole, whole_dn)
+    for g in GLOSS:
+        out = _device("skip", terms, noise, _kl(7), g)
+        _check("skip", terms, noise, _kl(7), ref, out, g)
+        assert out.dkl.numel() == 7
+        alone = _device("skip", [draws], noise, _kl(7), g)  # the draws term's launch and slot do not depend on slot 0
+        assert out.ll[1].view(torch.int64) == alone.ll[0].view(torch.int64) and torch.equal(out.dF[1], alone.dF[0])
+        assert torch.equal(out.dnoise[0].view(torch.int32), alone.dnoise[0].view(torch.int32))
+
+
 # ---- gpsa_elbo_fused_post -------------------------------------------------------------------------------------------
-F32, F64 = 0, 1  # GPSA_F32, GPSA_F64 (include/gpsa_hip.h)
+F32, F64 = 0, 1 # GPSA_F32, GPSA_F64 (include/gpsa_hip.h)
 EINVAL, EWORKSPACE = -1, -2
 VAR_U = 0.3
 

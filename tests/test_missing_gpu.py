@@ -7,6 +7,7 @@ fp64 oracle with the sum restricted to the observed entries:
 (fp64 torch with autograd, so every parameter's gradient comes with it) at the project's hard 1e-4."""
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -434,6 +435,57 @@ def test_step_matches_masked_fp64_reference(name, kind, fuse):
     errs, bad = _against(res, ref)
     print(name, kind, "fused" if fuse else "separate", {k: f"{v:.1e}" for k, v in errs.items()})
     assert not bad, bad
+
+
+# ---- 4b. the loss node's closings, bit for bit -------------------------------------------------------------------------
+# tests/golden/loss_node_closings.npz: the loss and every parameter's gradient of one step per closing of the loss node
+# (plain, fused, per-view weighted, and each of them over partly observed outputs), through the step engine and - where
+# the per-layer path has a closing of its own - through the layers, recorded on one MI355X at a77545a, when the node
+# existed as ElboLossFn, WeightedElboLossFn and SkipElboLossFn.  The one node that replaced them runs the same ops on the
+# same tables: the comparison is byte for byte.  c10 is the smallest case of STEP_CASES (4 unequal views, 211 x 5); c3
+# adds the node's LMC pre-pass (gpsa_lmc_loglik_fused_f32 / _skip_f32).
+NODE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loss_node_closings.npz")
+NODE_CLOSINGS = [("c10_unequal_two_fixed", c, e) for e in ("engine", "layers")
+                 for c in ("plain", "fused", "weighted", "skip_plain", "skip_fused", "skip_weighted")
+                 if e == "engine" or c in ("weighted", "skip_plain", "skip_weighted")]
+NODE_CLOSINGS += [("c3_lmc_matern12_warp", c, "engine") for c in ("fused", "skip_fused")]
+
+
+def _closing_step(name, closing, path):
+    """one step of golden case ``name`` through the named closing -> {"loss", "grad/<parameter>": numpy}"""
+    _build()
+    g = Golden(name)
+    model, dd = build_model(g, device=DEV)
+    kind = closing.split("_")[-1]
+    if closing.startswith("skip"):
+        dd = _masked_dd(dd, g, _step_mask(g, "random"))
+        model.skip_missing = True
+    model.use_step_engine = path == "engine"
+    model.fuse_elbo = kind == "fused"
+    model.fuse_min_flops = 0
+    if kind == "weighted":
+        for m in g.mods:  # fp64 weights that no fp32 holds, one per view
+            nv = len(g.cfg["n_samples"][m])
+            dd[m]["view_weights"] = torch.tensor([(3 + 2 * v) / 7 for v in range(nv)], dtype=torch.float64)
+    loss, out = _run_step(model, dd, g)
+    if kind == "fused" and model.n_latent_gps[g.mods[0]] is None:
+        assert model._cache.fuse is not None and "fused" in model._cache.fuse["state"], "the fused ELBO path did not run"
+    res = _collect(model, loss, out, g)
+    return {k: v for k, v in res.items() if k == "loss" or k.startswith("grad/")}
+
+
+@pytest.mark.parametrize("name,closing,path", NODE_CLOSINGS, ids=["-".join((n.split("_")[0], c, p)) for n, c, p in NODE_CLOSINGS])
+def test_loss_node_closings_are_the_recorded_bits(name, closing, path):
+    rec = np.load(NODE_GOLDEN)
+    got = _closing_step(name, closing, path)
+    pre = f"{name}/{closing}/{path}/"
+    keys = sorted(k[len(pre):] for k in rec.files if k.startswith(pre))
+    assert keys == sorted(got) and "loss" in keys and len(keys) > 5, (keys, sorted(got))
+    for k in keys:
+        want = rec[pre + k]
+        assert got[k].dtype == want.dtype and got[k].shape == want.shape, k
+        assert np.isfinite(want).all(), k
+        assert got[k].tobytes() == want.tobytes(), (k, float(np.abs(got[k].astype(np.float64) - want).max()))
 
 
 def test_bf16x3_plan_takes_the_fp32_skip_kernel_and_goes_back():
