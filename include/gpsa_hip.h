@@ -680,7 +680,8 @@ int gpsa_step_contraction(const void* plan, int m);   /* bit mask of modality m'
                                                          the fused ELBO pass (when gpsa_step_io.fuse_elbo is set: the
                                                          unfused path runs the fp32 kernels; cleared once a fused pass
                                                          of the plan has run with gpsa_step_io.skip_missing, set again
-                                                         by one without), 2 = the data GP's Gram */
+                                                         by one without; clear while gpsa_step_likelihood has
+                                                         made m a Poisson modality), 2 = the data GP's Gram */
 long long gpsa_step_scratch_bytes(const void* plan);
 long long gpsa_step_bwd_acc_bytes(const void* plan);  /* gpsa_step_io.bwd_acc */
 int gpsa_step_n_kl(const void* plan);                 /* V*D + sum_m L_m */
@@ -850,6 +851,77 @@ int gpsa_elbo_loss_skip_bwd(int n_ll, const float* const* F, const float* const*
 int gpsa_lmc_loglik_fused_skip_f32(const float* F, const float* W, const float* Y, const float* noise_u, int S, long long N,
                                    int L, int P, double* zpart, int nparts, float* dF, float* dW, void* workspace,
                                    long long workspace_bytes, void* stream);
+
+/* ---- count outputs: the Poisson likelihood (csrc/poisson.hip, csrc/loss_views.hip, csrc/qf_elbo_pois.hip, csrc/lmc.hip;
+ * opt-in: model.likelihood) ---------------------------------------------------------------------------------------------
+ * For a term of kind GPSA_LIK_POISSON the draws are log rates: with eta[s,n,p] = F[s,n,p] + log_offset[n] (log_offset
+ * [N] fp32 or NULL = 0: per-row log size factors),
+ *   LL = sum_v w[v] ( sum_{s, (n,p) in view v} (y eta - exp(eta)) / S  -  sum_{(n,p) in view v} lgamma(y + 1) ),
+ *   dLoss/dF = gloss w[v] (exp(eta) - y) / S,
+ * the same Monte-Carlo estimator as the Gaussian term's over the same draws.  Y is fp32 and is NOT validated: the formula
+ * is evaluated as written for any real y; exp is the exact expf, and eta > 88 gives inf.  The term's noise_u entry does not
+ * enter; its gradient is written as exactly 0.  skip != 0: a NaN in Y is a missing observation - its dF is exactly 0 and it
+ * adds nothing to either sum (no count table: the term has no per-entry constant that depends on a parameter); skip == 0:
+ * a NaN propagates to the loss.
+ * gpsa_lgamma_sum: out[i][v] = sum of lgamma(Y_i[n,p] + 1) over the rows of view v (views as gpsa_count_observed's; NaN
+ * entries left out when skip != 0), DEVICE doubles from an fp64 partial-sum launch and a fixed-order closing - no atomics,
+ * no host read.  It depends on no parameter: once per Y tensor.  workspace >= gpsa_lgamma_sum_workspace() bytes. */
+#define GPSA_LIK_GAUSSIAN 0
+#define GPSA_LIK_POISSON 1
+long long gpsa_lgamma_sum_workspace(void);
+int gpsa_lgamma_sum(int n_ll, const float* const* Y, const long long* N, const int* P, const int* n_views,
+                    const long long* const* view_off, int skip, double* const* out, void* workspace,
+                    long long workspace_bytes, void* stream);
+/* The ELBO loss closing for a model with at least one Poisson term: the tables of gpsa_elbo_loss_skip_fwd / _bwd (zpart,
+ * n_views / view_off / w, nobs, each nullable as there) plus, per term, kind[i] (GPSA_LIK_*), lgam[i] (gpsa_lgamma_sum
+ * with the same views and skip flag; read for Poisson terms) and log_offset[i] (Poisson terms; NULL entry or NULL table =
+ * 0), and the skip flag.
+ *   Poisson term: from its draws (loglik_pois_kernel) or, zpart[i] non-null, from nparts partial sums of y eta - exp(eta)
+ *     (gpsa_quadform_elbo_pois_f32, gpsa_lmc_loglik_fused_pois_f32; one view); nobs[i] and noise_u[i] are not read.
+ *   Gaussian term: exactly what the other closings do.  nobs[i] non-null: the skip closing's arithmetic over counts (from
+ *     draws only with skip != 0; from partial sums of z^2 also with skip == 0, the caller then passing N_i P_i as the
+ *     count); nobs[i] NULL (or no nobs table): the weighted closing's, which needs views and w[i] (skip == 0, from draws).
+ * Every check runs before the first launch (GPSA_EINVAL / GPSA_EWORKSPACE).  workspace >= 8 * 4100 * n_ll bytes. */
+int gpsa_elbo_loss_pois_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const int* kind, const double* const* lgam,
+                            const float* const* log_offset, int skip, const double* kl, int n_kl, double kl_scale,
+                            float* loss, double* ll_out, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_elbo_loss_pois_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const int* kind, const double* const* lgam,
+                            const float* const* log_offset, int skip, const float* gloss, int n_kl, double kl_scale,
+                            float* const* dF, float* const* dnoise, float* dnoise_all, int n_noise, double* dkl,
+                            void* workspace, long long workspace_bytes, void* stream);
+/* gpsa_quadform_elbo_skip_f32 / _delta_skip_f32 with the Poisson term in the closing (panel_elbo_pois_kernel): per (l, c),
+ * c = s N + n, eta = F + log_offset[n];  dmeanT = dLoss/dF = (exp(eta) - Y[n,l]) / S;  g as there;  part[] sums
+ * y eta - exp(eta).  noise_u is not read (may be NULL); log_offset [N] or NULL; skip as above.  fp32 contraction only; same
+ * sizes, workspace query (gpsa_quadform_elbo_f32_workspace) and GPSA_EUNSUPPORTED cases. */
+int gpsa_quadform_elbo_pois_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                                long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
+                                double* part, float* FT, const float* log_offset, int skip, void* workspace,
+                                long long workspace_bytes, void* stream);
+int gpsa_quadform_elbo_delta_pois_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                      const float* delta, const double* q, const float* var_u, const float* eps,
+                                      const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                      float* abar, double* part, float* FT, const float* log_offset, int skip,
+                                      void* workspace, long long workspace_bytes, void* stream);
+/* gpsa_lmc_loglik_fused_skip_f32 for a Poisson LMC modality (lmc_mfma_pois_kernel): F_obs = F W is the log rate,
+ * dF_obs = (exp(eta) - y) / S in front of the unchanged dF_latent and dW products, zpart sums y eta - exp(eta).
+ * Matrix-core kernel only (L <= 64); workspace: gpsa_lmc_loglik_workspace. */
+int gpsa_lmc_loglik_fused_pois_f32(const float* F, const float* W, const float* Y, const float* log_offset, int skip, int S,
+                                   long long N, int L, int P, double* zpart, int nparts, float* dF, float* dW,
+                                   void* workspace, long long workspace_bytes, void* stream);
+/* The likelihood of modality m's fused ELBO pass in the step engine (gpsa_step_io carries no field for it): kind
+ * GPSA_LIK_POISSON makes stage 2 of gpsa_step_forward run gpsa_quadform_elbo_pois_f32 / _delta_pois_f32 for m with
+ * log_offset ([N_m] or NULL; must stay valid while the plan may run) and gpsa_step_io.skip_missing as the skip flag;
+ * ll_part[m] then goes to gpsa_elbo_loss_pois_fwd / _bwd.  Also in a bf16x3 plan: there is no x3 Poisson closing, the
+ * pass runs the fp32 kernel (the Gram stays on x3) and gpsa_step_contraction reports it for as long as the kind is
+ * set.  GPSA_LIK_GAUSSIAN (a new plan's state; log_offset must be NULL) goes back.  Set it before enqueuing m's pass. */
+int gpsa_step_likelihood(void* plan, int m, int kind, const float* log_offset);
 
 /* ---- prediction: closed-form moments of the data GP (csrc/predict.hip) ----------------------------------------------
  * The counterpart of gpsa_data_sample_fwd: from a chunk of c rows evaluated at S warp samples - meanT, v [L, S*c] fp32

@@ -222,7 +222,24 @@ SIGNATURES.update({
     "gpsa_lmc_loglik_fused_skip_f32": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp, _i, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_predict_moments_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp]),
+    # count outputs (model.likelihood): the Poisson term
+    "gpsa_lgamma_sum_workspace": (_ll, []),
+    "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),
+    "gpsa_elbo_loss_pois_fwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i), _pp, _i,
+                                     C.POINTER(_i), _pp, _pp, _pp, C.POINTER(_i), _pp, _pp, _i, _vp, _i, _d, _vp, _vp,
+                                     _vp, _ll, _vp]),
+    "gpsa_elbo_loss_pois_bwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i), _pp, _i,
+                                     C.POINTER(_i), _pp, _pp, _pp, C.POINTER(_i), _pp, _pp, _i, _vp, _i, _d, _pp, _pp,
+                                     _vp, _i, _vp, _vp, _ll, _vp]),
+    "gpsa_quadform_elbo_pois_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _i, _vp, _ll, _vp]),
+    "gpsa_quadform_elbo_delta_pois_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _i, _vp, _ll, _vp]),
+    "gpsa_lmc_loglik_fused_pois_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _ll, _i, _i, _vp, _i, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_step_likelihood": (_i, [_vp, _i, _i, _vp]),
 })
+
+LIK_KINDS = {"gaussian": 0, "poisson": 1}  # GPSA_LIK_GAUSSIAN / GPSA_LIK_POISSON
 
 _lib = None
 

@@ -68,6 +68,18 @@ static inline ViewRows view_rows(long long N, int V, const long long* off) {
   return vr;
 }
 
+// poisson.hip: the Poisson term's per-element kernel (loglik_pois_kernel<bwd>), grid (nb, V) over the term's views:
+// forward: part[v * nb + block] = sum of y eta - exp(eta) over the block's share of view v; backward: dF = gloss w_v
+// (exp(eta) - y) / S, part untouched.  eta = F + log_offset[row] (nullptr: 0); w == nullptr: every view weighs 1; skip:
+// a NaN in Y is left out (dF exactly 0)
+int pois_loglik_launch(bool bwd, const float* F, const float* Y, const float* log_offset, int S, long long N, int P,
+                       const ViewRows& vr, int V, int nb, const double* w, const float* gloss, int skip, float* dF,
+                       double* part, hipStream_t st);
+// lmc.hip: lmc_mfma_launch for a Poisson modality (lmc_mfma_pois_kernel)
+int lmc_mfma_pois_launch(const float* F, const float* W, const float* Y, const float* log_offset, int skip, int S,
+                         long long N, int L, int P, double* zpart, int nparts, float* dF, float* dWpart, int G,
+                         hipStream_t st);
+
 // proj64.hip: alpha = Kinv X (fp64 matrix cores) as a persistent output-stationary kernel over pack_whiten_kernel's
 // packed inverse(s); proj64_ok says which shapes it takes; q is closed by atomic adds onto
 // zero: q_zeroed says an earlier launch on the stream has cleared it (else a memset node goes in front)

@@ -36,6 +36,8 @@ lmc_mfma_kernel(const float* __restrict__ F, const float* __restrict__ W, const 
                 const float* __restrict__ noise_u, int S, long long N, int L, int P, double* __restrict__ zpart,
                 int nparts, float* __restrict__ dF, float* __restrict__ dWpart) {
   constexpr bool SKIP = false;
+  constexpr int LIK = GPSA_LIK_GAUSSIAN;
+  constexpr const float* log_offset = nullptr;  // (the Poisson kernel's argument)
 #include "lmc_body.hpp"
 }
 template <int NLT, int NPT>
@@ -44,6 +46,21 @@ lmc_mfma_skip_kernel(const float* __restrict__ F, const float* __restrict__ W, c
                      const float* __restrict__ noise_u, int S, long long N, int L, int P, double* __restrict__ zpart,
                      int nparts, float* __restrict__ dF, float* __restrict__ dWpart) {
   constexpr bool SKIP = true;
+  constexpr int LIK = GPSA_LIK_GAUSSIAN;
+  constexpr const float* log_offset = nullptr;  // (the Poisson kernel's argument)
+#include "lmc_body.hpp"
+}
+
+// LIK = GPSA_LIK_POISSON (lmc_mfma_pois_kernel; gpsa_lmc_loglik_fused_pois_f32): F W is the log rate of count outputs;
+// only the closing on the accumulator registers differs (lmc_body.hpp), the NaN select is the argument ``skip``
+template <int NLT, int NPT>
+__global__ void __launch_bounds__(256, 2)
+lmc_mfma_pois_kernel(const float* __restrict__ F, const float* __restrict__ W, const float* __restrict__ Y,
+                     const float* __restrict__ log_offset, int skip, int S, long long N, int L, int P,
+                     double* __restrict__ zpart, int nparts, float* __restrict__ dF, float* __restrict__ dWpart) {
+  constexpr int LIK = GPSA_LIK_POISSON;
+  constexpr const float* noise_u = nullptr;  // (not read)
+  const bool SKIP = skip != 0;
 #include "lmc_body.hpp"
 }
 
@@ -86,6 +103,35 @@ int lmc_mfma_skip_launch(const float* F, const float* W, const float* Y, const f
   if (L <= 16) return lmc_mfma_launch_t<1, 8, true>(F, W, Y, noise_u, S, N, L, P, zpart, nparts, dF, dWpart, G, st);
   if (L <= 32) return lmc_mfma_launch_t<2, 4, true>(F, W, Y, noise_u, S, N, L, P, zpart, nparts, dF, dWpart, G, st);
   if (L <= 64) return lmc_mfma_launch_t<4, 2, true>(F, W, Y, noise_u, S, N, L, P, zpart, nparts, dF, dWpart, G, st);
+  return GPSA_EUNSUPPORTED;
+}
+
+
+template <int NLT, int NPT>
+static int lmc_mfma_pois_launch_t(const float* F, const float* W, const float* Y, const float* log_offset, int skip, int S,
+                                  long long N, int L, int P, double* zpart, int nparts, float* dF, float* dWpart, int G,
+                                  hipStream_t st) {
+  const int sm = (int)lmc_mfma_smem(NLT, NPT);
+  static per_device_flag attr_flag;
+  bool& attr_set = attr_flag.here();
+  if (!attr_set && sm > 65536) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lmc_mfma_pois_kernel<NLT, NPT>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, sm) != hipSuccess)
+      return GPSA_EUNSUPPORTED;
+    attr_set = true;
+  }
+  lmc_mfma_pois_kernel<NLT, NPT><<<G, 256, (size_t)sm, st>>>(F, W, Y, log_offset, skip, S, N, L, P, zpart, nparts, dF,
+                                                             dWpart);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+// ... for a Poisson modality (gpsa_lmc_loglik_fused_pois_f32)
+int lmc_mfma_pois_launch(const float* F, const float* W, const float* Y, const float* log_offset, int skip, int S,
+                         long long N, int L, int P, double* zpart, int nparts, float* dF, float* dWpart, int G,
+                         hipStream_t st) {
+  if (L <= 16) return lmc_mfma_pois_launch_t<1, 8>(F, W, Y, log_offset, skip, S, N, L, P, zpart, nparts, dF, dWpart, G, st);
+  if (L <= 32) return lmc_mfma_pois_launch_t<2, 4>(F, W, Y, log_offset, skip, S, N, L, P, zpart, nparts, dF, dWpart, G, st);
+  if (L <= 64) return lmc_mfma_pois_launch_t<4, 2>(F, W, Y, log_offset, skip, S, N, L, P, zpart, nparts, dF, dWpart, G, st);
   return GPSA_EUNSUPPORTED;
 }
 

@@ -1,9 +1,13 @@
-// The body that lmc_mfma_kernel and lmc_mfma_skip_kernel (lmc.hip) share.  It is a FRAGMENT: each kernel includes it
-// between its braces, after ``constexpr bool SKIP = ...``, with the template parameters NLT, NPT and the kernel's
-// arguments (F, W, Y, noise_u, S, N, L, P, zpart, nparts, dF, dWpart) in scope.  Textual inclusion, not a device
+// The body that lmc_mfma_kernel, lmc_mfma_skip_kernel and lmc_mfma_pois_kernel (lmc.hip) share.  It is a FRAGMENT: each
+// kernel includes it between its braces, after ``constexpr bool SKIP = ...`` and the likelihood selector ``constexpr int
+// LIK = GPSA_LIK_...``, with the template parameters NLT, NPT and the kernel's arguments (F, W, Y, noise_u, S, N, L, P,
+// zpart, nparts, dF, dWpart; the Gaussian kernels define log_offset as a constexpr nullptr, the Poisson kernel has it as
+// an argument, noise_u as a constexpr nullptr and SKIP as a run-time flag) in scope.  Textual inclusion, not a device
 // function: the default kernel's code then is what it was before the skip variant existed, instruction for instruction
 // (an inlined function taking the arguments moved its register allocation: 193/193/223 registers became 200/196/230),
 // and the two kernels differ by the one compare in the residual's select.
+// LIK == GPSA_LIK_POISSON: fo[r] is the log rate, eta = fo + log_offset[row] (a per-row load next to Yr),
+// dfo = (exp(eta) - y) / S with the exact expf, the summed term y eta - exp(eta); the dW and dF chains are unchanged.
   constexpr int LT = 16 * NLT, KB = 4 * NLT, PC = 64 * NPT, WS = PC + 4, FS = LT + 1;
   extern __shared__ __attribute__((aligned(16))) float lm_smem[];
   float* sW = lm_smem;                   // [LT][WS]   W[l][p0 + pp], zero padded
@@ -13,9 +17,9 @@
   __shared__ double red[4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, kq = lane >> 4;
-  const double sN = exp((double)noise_u[0]) + 1e-5;  // "variance" used as std
+  const double sN = LIK == GPSA_LIK_POISSON ? 1.0 : exp((double)noise_u[0]) + 1e-5;  // "variance" used as std
   const float inv = (float)(1.0 / sN);
-  const float coef = (float)(-1.0 / (sN * sN * (double)S));
+  const float coef = LIK == GPSA_LIK_POISSON ? (float)(1.0 / (double)S) : (float)(-1.0 / (sN * sN * (double)S));
   const long long ntiles = (N + 15) / 16;
   double z2 = 0.0;
   float* sTw = sT + w * 16 * 17;
@@ -46,9 +50,14 @@
       const long long n0 = t * 16;
       // the tile's observations in the accumulator layout: column p = lane & 15 of output tile i, rows 4 kq + r
       float Yr[NPT][4];
+      float Or[4];  // (Poisson) the rows' log offsets
       bool rok[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) rok[r] = n0 + 4 * kq + r < N;
+      for (int r = 0; r < 4; ++r) {
+        rok[r] = n0 + 4 * kq + r < N;
+        if constexpr (LIK == GPSA_LIK_POISSON)
+          Or[r] = log_offset != nullptr ? log_offset[rok[r] ? n0 + 4 * kq + r : N - 1] : 0.f;
+      }
 #pragma unroll
       for (int i = 0; i < NPT; ++i)
 #pragma unroll
@@ -83,10 +92,18 @@
           float dfo[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float rr = (rok[r] && pok[i] && (!SKIP || Yr[i][r] == Yr[i][r])) ? Yr[i][r] - fo[r] : 0.f;
-            const float z = rr * inv;
-            z2l = fmaf(z, z, z2l);
-            dfo[r] = coef * rr;
+            if constexpr (LIK == GPSA_LIK_POISSON) {
+              const float eta = fo[r] + Or[r];
+              const float ex = expf(eta);
+              const bool obs = rok[r] && pok[i] && (!SKIP || Yr[i][r] == Yr[i][r]);
+              z2l += obs ? fmaf(Yr[i][r], eta, -ex) : 0.f;
+              dfo[r] = obs ? coef * (ex - Yr[i][r]) : 0.f;
+            } else {
+              const float rr = (rok[r] && pok[i] && (!SKIP || Yr[i][r] == Yr[i][r])) ? Yr[i][r] - fo[r] : 0.f;
+              const float z = rr * inv;
+              z2l = fmaf(z, z, z2l);
+              dfo[r] = coef * rr;
+            }
           }
           // dW[l, p] += sum_c F[c, l] dfo[c, p]: K step r contracts the spots 4 kq + r
 #pragma unroll

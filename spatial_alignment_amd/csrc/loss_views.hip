@@ -5,7 +5,10 @@
 //                                        missing observation), with or without views and weights; terms from draws apply
 //                                        the select per element, fused terms arrive as partial sums of z^2 that already
 //                                        left the missing entries out; the counts stand where S N P stands elsewhere
-// Both pairs are argument checks around one views_fwd_impl / views_bwd_impl: the weighted pair passes no counts and no
+//   gpsa_elbo_loss_pois_fwd / _bwd       model.likelihood: the same tables plus a likelihood kind per term; a Poisson
+//                                        term (count outputs, poisson.hip) sums y eta - exp(eta) and has the lgamma table
+//                                        as its constant, a Gaussian term in the same call is closed as below
+// The first two pairs are argument checks around one views_fwd_impl / views_bwd_impl: the weighted pair passes no counts and no
 // fused terms.  The per-element kernels differ in their arithmetic and stay two (loglik_w_kernel counts per chunk and
 // sums z^2 - 1 in the backward; loglik_skip_kernel leaves the counts to the closing).
 #include "internal.hpp"
@@ -284,9 +287,236 @@ static int views_bwd_impl(int n_ll, const float* const* F, const float* const* Y
   return 0;
 }
 
+// ---- the closing with Poisson terms (gpsa_elbo_loss_pois_fwd / _bwd; the per-element kernel is poisson.hip's) --------
+// A Gaussian term in such a call is closed by the code above (view_total, loglik_views_bwd_finish_kernel, the two
+// per-element kernels); a Poisson term's partials sum y eta - exp(eta), and its constant is the lgamma table.
+struct PoisFinishArgs {
+  ViewFinishArgs g;                    // every term's tables; a Poisson term's nobs / noise_u are not read
+  int kind[GPSA_MAX_MODS];             // GPSA_LIK_*
+  const double* lgam[GPSA_MAX_MODS];   // [V] sum of lgamma(y + 1) per view (Poisson terms)
+};
+// elbo_views_finish_kernel with  ll[i] = sum_v w_v (t_v / S_i - lgam_v)  for a Poisson term (t_v: its view's partials)
+__global__ void __launch_bounds__(256) elbo_pois_finish_kernel(PoisFinishArgs p) {
+  __shared__ double red[4];
+  const ViewFinishArgs& a = p.g;
+  double lsum = 0.0;
+  for (int i = 0; i < a.n_ll; ++i) {
+    if (p.kind[i] == GPSA_LIK_POISSON) {
+      double tot = 0.0;
+      for (int v = 0; v < a.V[i]; ++v) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < a.nb[i]; b += blockDim.x) s += a.part[i][(long long)v * a.nb[i] + b];
+        s = block_sum(s, red);
+        if (threadIdx.x == 0) tot += (a.w[i] != nullptr ? a.w[i][v] : 1.0) * (s / (double)a.S[i] - p.lgam[i][v]);
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) {
+        a.ll[i] = tot;
+        lsum += tot;
+      }
+      continue;
+    }
+    double B = 0.0;
+    if (a.nobs[i] != nullptr) {
+      const double sd = exp((double)a.noise_u[i][0]) + 1e-5;
+      B = -log(sd) - 0.9189385332046727;
+    }
+    const double s = view_total(a.part[i], a.V[i], a.nb[i], a.w[i], a.nobs[i], a.S[i], -0.5, B, red);
+    if (threadIdx.x == 0) {
+      const double v = s / (double)a.S[i];
+      a.ll[i] = v;
+      lsum += v;
+    }
+  }
+  double k = 0.0;
+  for (int t = threadIdx.x; t < a.n_kl; t += 256) k += a.kl[t];
+  k = block_sum(k, red);
+  if (threadIdx.x == 0) a.loss[0] = (float)(a.kl_scale * k - lsum);
+}
+// a Poisson term's share of the backward's closing: its noise gradient is exactly 0; as the first term it also zero-fills
+// the whole noise gradient and writes dkl = kl_scale gloss (what loglik_views_bwd_finish_kernel does for a Gaussian one)
+__global__ void __launch_bounds__(256)
+pois_bwd_finish_kernel(float* __restrict__ dnoise_u, const float* __restrict__ gloss, double* __restrict__ dkl, int n_kl,
+                       double kl_scale, float* __restrict__ zero_base, int zero_n) {
+  if (zero_base != nullptr) {
+    for (int t = threadIdx.x; t < zero_n; t += blockDim.x) zero_base[t] = 0.f;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) dnoise_u[0] = 0.f;
+  if (dkl != nullptr)
+    for (int t = threadIdx.x; t < n_kl; t += blockDim.x) dkl[t] = kl_scale * (double)gloss[0];
+}
+
+// the pair's tables, checked before any launch (the header states the rules per kind)
+static int pois_args_check(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                           const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                           const int* n_views, const long long* const* view_off, const double* const* w,
+                           const double* const* nobs, const int* kind, const double* const* lgam, int skip,
+                           long long workspace_bytes) {
+  if (!kind || !lgam) return GPSA_EINVAL;
+  if ((n_views == nullptr) != (view_off == nullptr) || (w != nullptr && n_views == nullptr)) return GPSA_EINVAL;
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  for (int i = 0; i < n_ll; ++i) {
+    const bool fused = zpart && zpart[i];
+    if (fused && (nparts < 1 || (n_views && n_views[i] != 1))) return GPSA_EINVAL;
+    if (!fused && (!F[i] || !Y[i])) return GPSA_EINVAL;
+    if (n_views && !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
+    if (kind[i] == GPSA_LIK_POISSON) {
+      if (!lgam[i]) return GPSA_EINVAL;
+    } else if (kind[i] == GPSA_LIK_GAUSSIAN) {
+      if (!noise_u[i]) return GPSA_EINVAL;
+      if (nobs && nobs[i]) {  // the skip closing's arithmetic
+        if (!fused && !skip) return GPSA_EINVAL;
+      } else {  // the weighted closing's
+        if (fused || skip || !n_views || !w || !w[i]) return GPSA_EINVAL;
+      }
+    } else {
+      return GPSA_EINVAL;
+    }
+  }
+  return 0;
+}
+
+// term i's views, blocks and workspace slot, as views_fwd_impl / views_bwd_impl lay them out
+struct PoisTerm {
+  ViewRows vr;
+  int V, nb;
+  double* slot;
+};
+static PoisTerm pois_term(int i, const int* S, const long long* N, const int* P, const int* n_views,
+                          const long long* const* view_off, void* workspace) {
+  PoisTerm t;
+  t.V = n_views ? n_views[i] : 1;
+  t.vr = view_rows(N[i], t.V, view_off ? view_off[i] : nullptr);
+  t.nb = view_blocks(S[i], t.vr, t.V, P[i]);
+  t.slot = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * i;
+  return t;
+}
+
+static int pois_fwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                         const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                         const int* n_views, const long long* const* view_off, const double* const* w,
+                         const double* const* nobs, const int* kind, const double* const* lgam,
+                         const float* const* log_offset, int skip, const double* kl, int n_kl, double kl_scale,
+                         float* loss, double* ll_out, void* workspace, void* stream) {
+  hipStream_t st = as_stream(stream);
+  PoisFinishArgs p = {};
+  ViewFinishArgs& a = p.g;
+  a.n_ll = n_ll;
+  a.n_kl = kl ? n_kl : 0;
+  a.kl = kl;
+  a.kl_scale = kl_scale;
+  a.ll = ll_out;
+  a.loss = loss;
+  for (int i = 0; i < n_ll; ++i) {
+    const bool pois = kind[i] == GPSA_LIK_POISSON;
+    p.kind[i] = kind[i];
+    p.lgam[i] = lgam[i];
+    a.w[i] = w ? w[i] : nullptr;
+    a.nobs[i] = (!pois && nobs) ? nobs[i] : nullptr;
+    a.noise_u[i] = noise_u[i];
+    a.S[i] = S[i];
+    if (zpart && zpart[i]) {
+      a.part[i] = zpart[i];
+      a.V[i] = 1;
+      a.nb[i] = nparts;
+      continue;
+    }
+    const PoisTerm t = pois_term(i, S, N, P, n_views, view_off, workspace);
+    if (pois) {
+      if (int rc = pois_loglik_launch(false, F[i], Y[i], log_offset ? log_offset[i] : nullptr, S[i], N[i], P[i], t.vr,
+                                      t.V, t.nb, a.w[i], nullptr, skip, nullptr, t.slot, st))
+        return rc;
+    } else {
+      const auto kernel = a.nobs[i] ? loglik_skip_kernel<false> : loglik_w_kernel<false>;
+      kernel<<<dim3(t.nb, t.V), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], t.vr, a.w[i], nullptr,
+                                              nullptr, t.slot);
+    }
+    a.part[i] = t.slot;
+    a.V[i] = t.V;
+    a.nb[i] = t.nb;
+  }
+  elbo_pois_finish_kernel<<<1, 256, 0, st>>>(p);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+static int pois_bwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                         const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                         const int* n_views, const long long* const* view_off, const double* const* w,
+                         const double* const* nobs, const int* kind, const float* const* log_offset, int skip,
+                         const float* gloss, int n_kl, double kl_scale, float* const* dF, float* const* dnoise,
+                         float* dnoise_all, int n_noise, double* dkl, void* workspace, void* stream) {
+  hipStream_t st = as_stream(stream);
+  for (int i = 0; i < n_ll; ++i) {
+    const bool pois = kind[i] == GPSA_LIK_POISSON;
+    const double* wi = w ? w[i] : nullptr;
+    const double* ni = (!pois && nobs) ? nobs[i] : nullptr;
+    const double* part = zpart ? zpart[i] : nullptr;
+    int V = 1, nb = nparts;
+    if (part == nullptr) {
+      const PoisTerm t = pois_term(i, S, N, P, n_views, view_off, workspace);
+      V = t.V, nb = t.nb;
+      if (pois) {
+        if (int rc = pois_loglik_launch(true, F[i], Y[i], log_offset ? log_offset[i] : nullptr, S[i], N[i], P[i], t.vr,
+                                        V, nb, wi, gloss, skip, dF[i], t.slot, st))
+          return rc;
+      } else {
+        const auto kernel = ni ? loglik_skip_kernel<true> : loglik_w_kernel<true>;
+        kernel<<<dim3(nb, V), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], t.vr, wi, gloss, dF[i],
+                                            t.slot);
+      }
+      part = t.slot;
+    }
+    // the first term's finishing launch also zero-fills the noise gradient and writes dkl
+    if (pois)
+      pois_bwd_finish_kernel<<<1, 256, 0, st>>>(dnoise[i], gloss, i == 0 ? dkl : nullptr, n_kl, kl_scale,
+                                                i == 0 ? dnoise_all : nullptr, n_noise);
+    else
+      loglik_views_bwd_finish_kernel<<<1, 256, 0, st>>>(part, V, nb, wi, ni, noise_u[i], S[i], dnoise[i], gloss,
+                                                        i == 0 ? dkl : nullptr, n_kl, kl_scale,
+                                                        i == 0 ? dnoise_all : nullptr, n_noise);
+  }
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace gpsa
 
 extern "C" {
+
+int gpsa_elbo_loss_pois_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const int* kind, const double* const* lgam,
+                            const float* const* log_offset, int skip, const double* kl, int n_kl, double kl_scale,
+                            float* loss, double* ll_out, void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!loss || !ll_out) return GPSA_EINVAL;
+  if (int rc = pois_args_check(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, lgam, skip,
+                               workspace_bytes))
+    return rc;
+  return pois_fwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, lgam, log_offset,
+                       skip, kl, n_kl, kl_scale, loss, ll_out, workspace, stream);
+}
+
+int gpsa_elbo_loss_pois_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                            const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                            const int* n_views, const long long* const* view_off, const double* const* w,
+                            const double* const* nobs, const int* kind, const double* const* lgam,
+                            const float* const* log_offset, int skip, const float* gloss, int n_kl, double kl_scale,
+                            float* const* dF, float* const* dnoise, float* dnoise_all, int n_noise, double* dkl,
+                            void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!gloss || !dF || !dnoise) return GPSA_EINVAL;
+  if (int rc = pois_args_check(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, lgam, skip,
+                               workspace_bytes))
+    return rc;
+  for (int i = 0; i < n_ll; ++i)
+    if (!dnoise[i] || (!(zpart && zpart[i]) && !dF[i])) return GPSA_EINVAL;
+  return pois_bwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, log_offset, skip,
+                       gloss, n_kl, kl_scale, dF, dnoise, dnoise_all, n_noise, dkl, workspace, stream);
+}
 
 int gpsa_elbo_loss_weighted_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
                                 const int* S, const long long* N, const int* P, const int* n_views,

@@ -380,6 +380,20 @@ __global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT)) panel_elbo_skip
 GPSA_ELBO_SHAPES(GPSA_ELBO_SKIP_EXTERN)
 extern template __global__ void panel_elbo_skip_kernel<13, 2, 2, true, true>(ElboArgs);
 extern template __global__ void panel_elbo_skip_kernel<13, 2, 4, true, true>(ElboArgs);
+// ... and with the Poisson term in the closing (qf_elbo_pois.hip; gpsa_quadform_elbo_pois_f32): log_offset [N] or nullptr,
+// skip != 0 leaves the NaN entries of Y out; ``part`` then sums y eta - exp(eta) and noise_u is not read
+template <int MB, int NCT, int RL, bool FULLT = false, bool PAIRB = false>
+__global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT))
+panel_elbo_pois_kernel(ElboArgs a, const float* __restrict__ log_offset, int skip);
+#define GPSA_ELBO_POIS_EXTERN(MB, NCT)                                                              \
+  extern template __global__ void panel_elbo_pois_kernel<MB, NCT, 2>(ElboArgs, const float*, int); \
+  extern template __global__ void panel_elbo_pois_kernel<MB, NCT, 4>(ElboArgs, const float*, int);
+#define GPSA_ELBO_POIS_DEFINE(MB, NCT)                                                       \
+  template __global__ void panel_elbo_pois_kernel<MB, NCT, 2>(ElboArgs, const float*, int); \
+  template __global__ void panel_elbo_pois_kernel<MB, NCT, 4>(ElboArgs, const float*, int);
+GPSA_ELBO_SHAPES(GPSA_ELBO_POIS_EXTERN)
+extern template __global__ void panel_elbo_pois_kernel<13, 2, 2, true, true>(ElboArgs, const float*, int);
+extern template __global__ void panel_elbo_pois_kernel<13, 2, 4, true, true>(ElboArgs, const float*, int);
 
 // the same pass with the contraction on the bf16 matrix instructions in three pieces (qf_x3.hip; gpsa_step_desc.contraction
 // = 1): Ppk is then pack_x3_kernel's three-plane bf16 image of Omega

@@ -7,6 +7,8 @@ namespace gpsa {
 template <int MB, int NCT, int RL, bool FULLT, bool PAIRB>
 __global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT)) panel_elbo_kernel(ElboArgs a) {
   constexpr bool SKIP = false;
+  constexpr int LIK = GPSA_LIK_GAUSSIAN;
+  constexpr const float* log_offset = nullptr;  // (the Poisson kernel's argument)
 #include "qf_elbo_body.hpp"
 }
 

@@ -1,6 +1,7 @@
-// The body that panel_elbo_kernel (qf_elbo.hip) and panel_elbo_skip_kernel (qf_elbo_skip.hip) share.  It is a FRAGMENT:
-// each kernel includes it between its braces, after ``constexpr bool SKIP = ...``, with the template parameters MB, NCT,
-// RL, FULLT, PAIRB and the argument ``ElboArgs a`` in scope.  Textual inclusion, not a device function: the default
+// The body that panel_elbo_kernel (qf_elbo.hip), panel_elbo_skip_kernel (qf_elbo_skip.hip) and panel_elbo_pois_kernel
+// (qf_elbo_pois.hip) share.  It is a FRAGMENT: each kernel includes it between its braces, after ``constexpr bool SKIP =
+// ...``, the likelihood selector ``constexpr int LIK = GPSA_LIK_...`` and ``log_offset`` (the Gaussian kernels: a constexpr
+// nullptr), with the template parameters MB, NCT, RL, FULLT, PAIRB and the argument ``ElboArgs a`` in scope.  Textual inclusion, not a device function: the default
 // kernel's code then is what it was before the skip variant existed, instruction for instruction (an inlined
 // function taking the arguments moved its register allocation), and the two kernels differ by the one compare and
 // select in the closing.
@@ -28,6 +29,11 @@
 // SKIP (panel_elbo_skip_kernel; model.skip_missing): Y[n, l] != Y[n, l] marks a missing observation, which is left
 // out of the likelihood - z = 0, dF = 0 and g = 0 exactly, nothing joins abar or the sum of z^2 (the count of the
 // observed entries that the loss needs instead of S N L is gpsa_count_observed's).
+// LIK == GPSA_LIK_POISSON (panel_elbo_pois_kernel; model.likelihood): the draw is a log rate.  The closing replaces the
+// residual by eta = F + log_offset[n], dLoss/dF = (exp(eta) - y) / S and the summed term by y eta - exp(eta) (the exact
+// expf: one per (l, column)); everything from g on is shared.  The offset is per COLUMN, not per output: it is loaded
+// with resid / okc, once per column tile - not in the closing (a compiler-visible load there waits for vmcnt(0)) and not
+// as a fourth gather kind.  SKIP is a kernel argument there, not a constant.
   constexpr int MP = MB * 16;
   constexpr int WGCOLS = 64 * NCT;
   constexpr int CHUNK = MP * 16;
@@ -108,9 +114,10 @@
   static_assert(NPW <= 4, "a wave's pieces of a stage must lie within the 4 KiB an immediate offset reaches");
 
   // likelihood constants (elementwise.hip: loglik_*_kernel)
-  const double sN = exp((double)a.noise_u[0]) + 1e-5;
+  const double sN = LIK == GPSA_LIK_POISSON ? 1.0 : exp((double)a.noise_u[0]) + 1e-5;
   const float inv = (float)(1.0 / sN);
-  const float coef = (float)(-1.0 / (sN * sN * (double)a.S));  // dLoss/dF = coef (Y - F) at upstream gradient 1
+  // dLoss/dF = coef (Y - F) at upstream gradient 1;  Poisson: coef (exp(eta) - Y)
+  const float coef = LIK == GPSA_LIK_POISSON ? (float)(1.0 / (double)a.S) : (float)(-1.0 / (sN * sN * (double)a.S));
   const double var0 = exp((double)a.var_u[0]);
   double z2 = 0.0;
 
@@ -137,6 +144,7 @@
     ord.get(step, tile, l_lo, l_hi);
     const long long cw = tile * WGCOLS + (long long)w * (16 * NCT);
     float resid[NCT];
+    float offc[NCT];  // (Poisson) the columns' log offsets
     bool okc[NCT];
     load_alpha_slab<MB, NCT, true, FULLT>(X, M, C, cw, j, kq, xb, okc);
     if (RL < 4) load_alpha_last<MB, NCT, 4>(X, M, C, cw, j, kq, RL, xl);
@@ -146,6 +154,8 @@
       // sigma^2 - q formed in fp64 before rounding (data_sample_fwd_kernel)
       const double qc = a.q[okc[ct] ? c : C - 1];
       resid[ct] = okc[ct] ? (float)(var0 - qc) : 1.f;
+      if constexpr (LIK == GPSA_LIK_POISSON)
+        offc[ct] = log_offset != nullptr ? log_offset[(okc[ct] ? c : C - 1) % a.N] : 0.f;
     }
     // gather addresses of this lane for output l_lo: operation o moves element (o*64 + lane) of the wave's
     // [(ct*3 + kind)*16 + j] table; kind 0: mean[l][c] (next output: + C), 1: eps[c][l] (+ 1), 2: Y[c % N][l] (+ 1)
@@ -270,16 +280,29 @@
         const float sd = sqrtf(var);
         const float Fd = mean + sd * e;  // the draw (data_sample_fwd_kernel's expression)
         // SKIP: a NaN observation is a missing one - residual exactly 0, so dF, g, z and its share of abar are too
-        const float rres = SKIP ? ((y == y) ? y - Fd : 0.f) : y - Fd;
-        const float dF = coef * rres;
+        float rres = 0.f, dF, pterm = 0.f;
+        if constexpr (LIK == GPSA_LIK_POISSON) {
+          const float eta = Fd + offc[ct];
+          const float ex = expf(eta);
+          const bool obs = !SKIP || y == y;
+          dF = obs ? coef * (ex - y) : 0.f;
+          pterm = obs ? fmaf(y, eta, -ex) : 0.f;
+        } else {
+          rres = SKIP ? ((y == y) ? y - Fd : 0.f) : y - Fd;
+          dF = coef * rres;
+        }
         const float gv = okc[ct] ? dF * e * 0.5f / sd : 0.f;
         if (okc[ct] && kq == 0) {
           const long long o = (long long)l * C + cw + ct * 16 + j;
           a.g[o] = gv;
           a.dmeanT[o] = dF;
           if (a.FT != nullptr) a.FT[o] = Fd;  // (uniform)
-          const float z = rres * inv;
-          z2l += z * z;
+          if constexpr (LIK == GPSA_LIK_POISSON) {
+            z2l += pterm;
+          } else {
+            const float z = rres * inv;
+            z2l += z * z;
+          }
         }
         // Register files (round 4): this unit is built with -amdgpu-mfma-vgpr-form (__graft_entry__.build), so the FIRST
         // accumulator set (the product being formed) and the alpha slab live in arch VGPRs - the dot product above

@@ -754,14 +754,24 @@ static inline int gram_nl(int MB, int L, long long C) {
   return (can && C >= 8192) ? 2 : 1;
 }
 
-// panel_elbo_kernel (skip: panel_elbo_skip_kernel, the NaN entries of Y left out) for one shape of GPSA_ELBO_SHAPES
+// panel_elbo_kernel (skip: panel_elbo_skip_kernel, the NaN entries of Y left out; lik == GPSA_LIK_POISSON:
+// panel_elbo_pois_kernel, which takes the offsets and the skip flag as arguments) for one shape of GPSA_ELBO_SHAPES
 template <int MB, int NCT>
-static void elbo_shape(const ElboArgs& a, unsigned grid, hipStream_t st, bool skip) {
+static void elbo_shape(const ElboArgs& a, unsigned grid, hipStream_t st, bool skip, int lik, const float* log_offset) {
   // the 13-tile shape with every row tile but the last inside the matrix (the headline configuration): the
   // instantiation without row clamps and with one barrier per two K chunks
   constexpr bool HEAD = MB == 13 && NCT == 2;
   const bool rl2 = last_tile_rl(a.M, MB) == 2;
-  if (skip) {
+  if (lik == GPSA_LIK_POISSON) {
+    const int sk = skip ? 1 : 0;
+    if (HEAD && a.M > 16 * (MB - 1)) {
+      if (rl2) panel_elbo_pois_kernel<MB, NCT, 2, HEAD, HEAD><<<grid, 256, 0, st>>>(a, log_offset, sk);
+      else panel_elbo_pois_kernel<MB, NCT, 4, HEAD, HEAD><<<grid, 256, 0, st>>>(a, log_offset, sk);
+    } else {
+      if (rl2) panel_elbo_pois_kernel<MB, NCT, 2><<<grid, 256, 0, st>>>(a, log_offset, sk);
+      else panel_elbo_pois_kernel<MB, NCT, 4><<<grid, 256, 0, st>>>(a, log_offset, sk);
+    }
+  } else if (skip) {
     if (HEAD && a.M > 16 * (MB - 1)) {
       if (rl2) panel_elbo_skip_kernel<MB, NCT, 2, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
       else panel_elbo_skip_kernel<MB, NCT, 4, HEAD, HEAD><<<grid, 256, 0, st>>>(a);
@@ -1214,14 +1224,17 @@ int gpsa_quadform_elbo_takes_delta(int M) { return M >= 1 && elbo_delta_ok(M) ? 
 
 // x3: the contraction on the bf16 matrix instructions in three pieces (pack_x3_kernel's image of Omega, panel_elbo_x3_kernel)
 // skip (fp32 contraction only): panel_elbo_skip_kernel - a NaN in Y is a missing observation
+// lik == GPSA_LIK_POISSON (fp32 contraction only): panel_elbo_pois_kernel with log_offset (nullable); noise_u is not read
 static int elbo_launch(bool x3, bool skip, int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
                        const float* meanT, const float* delta, const double* q, const float* var_u, const float* eps,
                        const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
-                       double* part, float* FT, void* workspace, long long workspace_bytes, void* stream) {
+                       double* part, float* FT, void* workspace, long long workspace_bytes, void* stream,
+                       int lik = GPSA_LIK_GAUSSIAN, const float* log_offset = nullptr) {
   using namespace gpsa;
   if (M < 1 || C < 1 || L < 1 || N < 1 || S < 1 || !alpha || !Omega || (!meanT && !delta) || !q || !var_u || !eps || !Y ||
-      !noise_u || !g || !dmeanT || !abar || !part)
+      (!noise_u && lik != GPSA_LIK_POISSON) || !g || !dmeanT || !abar || !part)
     return GPSA_EINVAL;
+  if (lik == GPSA_LIK_POISSON && x3) return GPSA_EINVAL;
   if (x3 && omega_dtype != GPSA_F32 && omega_dtype != GPSA_F64) return GPSA_EINVAL;
   if (delta != nullptr && !elbo_delta_ok(M)) return GPSA_EUNSUPPORTED;
   if (!elbo_path(M) || C > GPSA_PANEL_MAX_C) return GPSA_EUNSUPPORTED;
@@ -1248,7 +1261,7 @@ static int elbo_launch(bool x3, bool skip, int omega_dtype, const float* alpha, 
   const long long ntiles = cdiv(C, 64 * nct);
   const long long grid = persistent_grid(x3 ? 1 : elbo_wgs_per_cu(MB, nct), ntiles * L);
 #define GPSA_ELBO_CASE(MBV, NCTV) \
-  case MBV: elbo_shape<MBV, NCTV>(a, (unsigned)grid, st, skip); break;
+  case MBV: elbo_shape<MBV, NCTV>(a, (unsigned)grid, st, skip, lik, log_offset); break;
 #define GPSA_ELBO_X3_CASE(MBV, NCTV) \
   case MBV: panel_elbo_x3_kernel<MBV, NCTV><<<(unsigned)grid, 256, 0, st>>>(a); break;
   if (x3) {
@@ -1304,6 +1317,26 @@ int gpsa_quadform_elbo_delta_skip_f32(int omega_dtype, const float* alpha, const
   if (!delta) return GPSA_EINVAL;
   return elbo_launch(false, true, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u, g,
                      dmeanT, abar, part, FT, workspace, workspace_bytes, stream);
+}
+
+int gpsa_quadform_elbo_pois_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                                long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
+                                double* part, float* FT, const float* log_offset, int skip, void* workspace,
+                                long long workspace_bytes, void* stream) {
+  if (!meanT) return GPSA_EINVAL;
+  return elbo_launch(false, skip != 0, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u,
+                     g, dmeanT, abar, part, FT, workspace, workspace_bytes, stream, GPSA_LIK_POISSON, log_offset);
+}
+
+int gpsa_quadform_elbo_delta_pois_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                      const float* delta, const double* q, const float* var_u, const float* eps,
+                                      const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                      float* abar, double* part, float* FT, const float* log_offset, int skip,
+                                      void* workspace, long long workspace_bytes, void* stream) {
+  if (!delta) return GPSA_EINVAL;
+  return elbo_launch(false, skip != 0, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u,
+                     g, dmeanT, abar, part, FT, workspace, workspace_bytes, stream, GPSA_LIK_POISSON, log_offset);
 }
 
 int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,

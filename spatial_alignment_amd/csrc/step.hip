@@ -602,6 +602,9 @@ struct Plan {
   // roofline figures): slot = step index modulo the ring, 2 events per kernel
   std::vector<hipEvent_t> tev;
   bool skip_seen = false;  // the last fused ELBO launch left the NaN entries of Y out (gpsa_step_io.skip_missing)
+  // gpsa_step_likelihood: the likelihood of modality m's fused ELBO pass and, for a Poisson one, its rows' log offsets
+  int lik[GPSA_MAX_MODS] = {};
+  const float* log_offset[GPSA_MAX_MODS] = {};
   int tslots = 0, tfwd = 0, tbwd = 0;
   void tick(int kernel, int edge, bool fwd, hipStream_t st) {
     if (tslots == 0) return;
@@ -1353,7 +1356,10 @@ static int data_pass_fwd(Ctx& c, const Pass& ps) {
     float* abar = dmeanT + (long long)L * C;
     // io.skip_missing: the fp32 skip kernels (panel_elbo_skip_kernel), also in a bf16x3 plan - there is no x3 skip closing
     // (gpsa_step_contraction then reports the pass as fp32); such a plan's scratch holds the larger of the two workspaces
-    const bool skip = c.io.skip_missing != 0, x3 = ps.x3 && !skip;
+    // P.lik[m] == GPSA_LIK_POISSON (gpsa_step_likelihood): the fp32 Poisson kernels (panel_elbo_pois_kernel), with the same
+    // rule for a bf16x3 plan
+    const bool pois = P.lik[m] == GPSA_LIK_POISSON;
+    const bool skip = c.io.skip_missing != 0, x3 = ps.x3 && !skip && !pois;
     const long long ws32 = gpsa_quadform_elbo_f32_workspace(Mg, C, L);
     const long long wsx3 = ps.x3 ? gpsa_quadform_elbo_x3_f32_workspace(Mg, C, L) : 0;
     const long long wsb = x3 ? wsx3 : ws32;
@@ -1361,7 +1367,17 @@ static int data_pass_fwd(Ctx& c, const Pass& ps) {
     const bool timed = !dry && !c.quiet && &ps == &P.passes[0];
     if (timed) P.tick(0, 0, true, c.st);
     if (!dry) P.skip_seen = skip;
-    if (skip && mean_in_product)
+    if (pois && mean_in_product)
+      GPSA_RUN(gpsa_quadform_elbo_delta_pois_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
+                                                 c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
+                                                 c.io.ll_part[m], c.io.F_fused_T[m], P.log_offset[m], skip ? 1 : 0, ws,
+                                                 wsb, c.stv()));
+    else if (pois)
+      GPSA_RUN(gpsa_quadform_elbo_pois_f32(GPSA_F64, alpha, Om, Mg, C, L, meanT, q, c.prm.data_var, eps, c.io.Y[m],
+                                           (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
+                                           c.io.ll_part[m], c.io.F_fused_T[m], P.log_offset[m], skip ? 1 : 0, ws, wsb,
+                                           c.stv()));
+    else if (skip && mean_in_product)
       GPSA_RUN(gpsa_quadform_elbo_delta_skip_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
                                                  c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
                                                  c.io.ll_part[m], c.io.F_fused_T[m], ws, wsb, c.stv()));
@@ -2150,6 +2166,8 @@ static bool graph_usable(Plan& P, hipStream_t st) {
     P.g_enabled = (e && e[0] == '1') ? 1 : 0;
   }
   if (!P.g_enabled || P.tslots != 0 || P.g_idle_captures > 8) return false;
+  for (int m = 0; m < P.nm; ++m)  // (gpsa_step_likelihood's state is not part of the key: such a plan runs eagerly)
+    if (P.lik[m] != GPSA_LIK_GAUSSIAN) return false;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;
   return true;
@@ -2347,8 +2365,19 @@ int gpsa_step_fused(const void* plan, int m) {
 int gpsa_step_contraction(const void* plan, int m) {
   if (!plan) return 0;
   for (const gpsa::Pass& q : reinterpret_cast<const gpsa::Plan*>(plan)->passes)
-    if (q.m == m && !q.test)  // (skip_seen: the plan's last fused pass took the fp32 skip kernel, gpsa_step_io.skip_missing)
-      return ((q.o_fuse >= 0 && q.x3 && !reinterpret_cast<const gpsa::Plan*>(plan)->skip_seen) ? 1 : 0) | (q.gx3 ? 2 : 0);
+    if (q.m == m && !q.test) {  // (skip_seen: the plan's last fused pass took the fp32 skip kernel, gpsa_step_io.skip_missing;
+      const gpsa::Plan* p = reinterpret_cast<const gpsa::Plan*>(plan);  //  a Poisson modality's takes the fp32 Poisson kernel)
+      return ((q.o_fuse >= 0 && q.x3 && !p->skip_seen && p->lik[m] != GPSA_LIK_POISSON) ? 1 : 0) | (q.gx3 ? 2 : 0);
+    }
+  return 0;
+}
+int gpsa_step_likelihood(void* plan, int m, int kind, const float* log_offset) {
+  if (!plan) return GPSA_EINVAL;
+  gpsa::Plan* p = reinterpret_cast<gpsa::Plan*>(plan);
+  if (m < 0 || m >= p->nm || (kind != GPSA_LIK_GAUSSIAN && kind != GPSA_LIK_POISSON)) return GPSA_EINVAL;
+  if (kind == GPSA_LIK_GAUSSIAN && log_offset != nullptr) return GPSA_EINVAL;
+  p->lik[m] = kind;
+  p->log_offset[m] = log_offset;
   return 0;
 }
 long long gpsa_step_bwd_acc_bytes(const void* plan) { return plan ? reinterpret_cast<const gpsa::Plan*>(plan)->bwd_acc_bytes : -1; }

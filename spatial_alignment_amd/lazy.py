@@ -222,6 +222,17 @@ def run_fused(rec, idx, Ys, parts):
     plan, io, prm, saved, tensors, ins = (live[k] for k in ("plan", "io", "prm", "saved", "tensors", "ins"))
     mask = 0
     io.skip_missing = 1 if rec.get("skip") else 0  # (gpsa_step_io: the fused pass leaves the NaN entries of Y out)
+    # count outputs (model.likelihood): the plan is told each enqueued modality's likelihood and, for a Poisson one, its
+    # rows' log offsets (rec keeps them alive until the backward has run); a model that never had a Poisson modality makes
+    # no such call, one that had tells the plan when a modality is Gaussian again
+    lik = rec.get("lik")
+    if lik is not None or getattr(plan, "lik_set", False):
+        offs = rec.get("log_offset") or [None] * len(plan.mods)
+        for i in idx:
+            kind = int(lik[i]) if lik is not None else 0
+            o = offs[i] if kind == 1 else None
+            _lib.check(plan.lib.gpsa_step_likelihood(plan.handle, int(i), kind, None if o is None else o.data_ptr()),
+                       "gpsa_step_likelihood")
     for i, Y in zip(idx, Ys):
         io.Y[i] = Y.data_ptr()
         rec["Y"][i] = Y  # (alive until the backward has run: the io struct points into it)
@@ -238,6 +249,8 @@ def run_fused(rec, idx, Ys, parts):
     # answer (gpsa_step_contraction) when the flag is on and once more after it went off (a model that never sets the
     # flag makes no such call)
     skip = bool(rec.get("skip"))
-    if skip or getattr(plan, "skip_ran", False):
+    pois = lik is not None  # (the same for a Poisson modality's fp32 kernel)
+    if skip or getattr(plan, "skip_ran", False) or pois or getattr(plan, "lik_set", False):
         plan.skip_ran = skip
+        plan.lik_set = pois
         plan.contraction = {m: int(plan.lib.gpsa_step_contraction(plan.handle, j)) for j, m in enumerate(plan.mods)}

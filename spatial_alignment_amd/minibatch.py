@@ -9,7 +9,8 @@ B-row problem.
 buffers that persist across steps, and advances its step counter there too: nothing is read back by the host, so the
 draw can sit inside a captured step (``train.GraphedTrainStep(..., sampler=...)``) and every replay trains on the next
 batch.  The batch's ``data_dict`` carries ``view_weights`` = N_v / B_v, which ``loss_fn`` applies through
-``gpsa_elbo_loss_weighted_fwd`` / ``_bwd``.
+``gpsa_elbo_loss_weighted_fwd`` / ``_bwd``.  A Poisson modality's ``log_offset`` (per-row log size factors) is gathered
+with the rows by a second call of the same op.
 
 The index rule (standard drop-last epochs): K = N div B batches per epoch; step t is slot k = t mod K of epoch
 e = t div K, and row j of the batch of (modality m, view v) is  pi_{seed,m,v,e}(k B + j),  pi a keyed bijection of
@@ -162,11 +163,31 @@ class RowSampler:
         self._rows = [torch.zeros(tot[m], dtype=torch.int64, device=dev) for m in mods]
         self._Xb = [torch.zeros(tot[m], x.shape[1], dtype=torch.float32, device=dev) for m, x in zip(mods, self._X)]
         self._Yb = [torch.zeros(tot[m], y.shape[1], dtype=torch.float32, device=dev) for m, y in zip(mods, self._Y)]
+        # per-row log offsets (count outputs: model.likelihood): gathered as one more "output" column by a second call of
+        # the op on a step counter of its own, which moves in lockstep with the first (same seed, same step, same rows)
+        self._O = self._Ob = self._counter_o = None
+        if any(data_dict[m].get("log_offset") is not None for m in mods):
+            self._O, self._Ob = [], []
+            for m, x in zip(mods, self._X):
+                o = data_dict[m].get("log_offset")
+                if o is None:
+                    o = torch.zeros(x.shape[0], dtype=torch.float32, device=dev)
+                elif (not torch.is_tensor(o) or o.dtype != torch.float32 or tuple(o.shape) != (x.shape[0],)
+                      or o.device != dev):
+                    raise ValueError(f"RowSampler: data_dict[{m!r}]['log_offset'] must be a float32 tensor of shape "
+                                     f"({x.shape[0]},) on {dev}")
+                self._O.append(o.contiguous().view(-1, 1))
+                self._Ob.append(torch.zeros(tot[m], 1, dtype=torch.float32, device=dev))
+            self._counter_o = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._rows_o = [torch.zeros_like(r) for r in self._rows]
+            self._Xb_o = [torch.zeros_like(x) for x in self._Xb]
         dd = {}
         for i, m in enumerate(mods):
             w = torch.tensor([n / b for n, b in zip(views[m], self.batch_size[m])], dtype=torch.float64, device=dev)
             dd[m] = {"spatial_coords": self._Xb[i], "outputs": self._Yb[i], "n_samples_list": list(self.batch_size[m]),
                      "view_weights": w}
+            if self._O is not None and data_dict[m].get("log_offset") is not None:
+                dd[m]["log_offset"] = self._Ob[i].view(-1)
         view_idx, Ns, _, _ = model.create_view_idx_dict(dd)
         self.batch = Batch(dd, {m: dd[m]["spatial_coords"] for m in mods}, view_idx, Ns,
                            {m: r for m, r in zip(mods, self._rows)})
@@ -178,11 +199,16 @@ class RowSampler:
         nv, nr, bs = self._args
         torch.ops.gpsa.row_sample_gather(self._X, self._Y, nv, nr, bs, self.seed, self.counter, self._rows, self._Xb,
                                          self._Yb)
+        if self._O is not None:
+            torch.ops.gpsa.row_sample_gather(self._X, self._O, nv, nr, bs, self.seed, self._counter_o, self._rows_o,
+                                             self._Xb_o, self._Ob)
         return self.batch
 
     def set_step(self, t):
         """the next ``next()`` draws step t's batch"""
         self.counter.fill_(int(t))
+        if self._counter_o is not None:
+            self._counter_o.fill_(int(t))
 
     def host_rows(self, t):
         """{mod: int64 rows} of step t's batch from the host restatement (tests, documentation)"""

@@ -152,6 +152,13 @@ class VariationalGPSA(GPSA):
         # the ELBO of the observed entries - every loss path takes its skip kernels (gpsa_elbo_loss_skip_fwd / _bwd,
         # gpsa_quadform_elbo_skip_f32, gpsa_lmc_loglik_fused_skip_f32); False: the default kernels, a NaN propagates.
         self.skip_missing = False
+        # count outputs (opt-in): "gaussian" (the reference's likelihood, the default), "poisson", or {modality: kind} with
+        # the unnamed modalities Gaussian.  A Poisson modality's draws are log rates: loss_fn evaluates
+        # sum (y eta - exp(eta)) / S - sum lgamma(y + 1) with eta = F_obs + data_dict[m]["log_offset"][n] (optional per-row
+        # log size factors) on every loss path through its Poisson kernels (gpsa_elbo_loss_pois_fwd / _bwd,
+        # gpsa_quadform_elbo_pois_f32, gpsa_lmc_loglik_fused_pois_f32); its noise_variance entry does not enter (gradient 0).
+        # With every modality Gaussian nothing of this runs.
+        self.likelihood = "gaussian"
         self._noise = None  # injected Gaussian noise (tests / reproducibility), see inject_noise()
         self._cache = None
 
@@ -232,13 +239,99 @@ class VariationalGPSA(GPSA):
             raise TypeError(f"skip_missing must be True or False, got {value!r}")
         self.__dict__["_skip_missing"] = value
 
+    @property
+    def likelihood(self):
+        return self.__dict__.get("_likelihood", "gaussian")
+
+    @likelihood.setter
+    def likelihood(self, value):
+        kinds = ("gaussian", "poisson")
+        if isinstance(value, str):
+            if value not in kinds:
+                raise ValueError(f"likelihood must be one of {kinds} or a dict {{modality: kind}}, got {value!r}")
+        elif isinstance(value, dict):
+            for m, k in value.items():
+                if m not in self.modality_names:
+                    raise ValueError(f"likelihood names the modality {m!r}; the model has {list(self.modality_names)}")
+                if not isinstance(k, str) or k not in kinds:
+                    raise ValueError(f"likelihood of modality {m!r} must be one of {kinds}, got {k!r}")
+            value = dict(value)
+        else:
+            raise ValueError(f"likelihood must be one of {kinds} or a dict {{modality: kind}}, got {value!r}")
+        self.__dict__["_likelihood"] = value
+
+    def likelihood_of(self, m):
+        """the likelihood of modality ``m``: ``"gaussian"`` or ``"poisson"``"""
+        lik = self.likelihood
+        return lik if isinstance(lik, str) else lik.get(m, "gaussian")
+
+    def _lik_kinds(self):
+        """per modality its GPSA_LIK_* kind, or None when every modality is Gaussian (nothing new runs then)"""
+        lik = self.likelihood
+        if lik == "gaussian" or (isinstance(lik, dict) and all(k == "gaussian" for k in lik.values())):
+            return None
+        return [1 if self.likelihood_of(m) == "poisson" else 0 for m in self.modality_names]
+
+    def _close_pois(self, aux, weighted, skip):
+        """the tables of a loss with Poisson terms (aux["kinds"]): every term gets views (the weighted loss's, else one view
+        of weight 1: a Gaussian term from its draws is then closed by the weighted closing's arithmetic), the Poisson
+        terms their lgamma constants (cached like the observed counts: for the caller's own tensors only, recomputed on
+        a minibatch's gathered rows), the Gaussian terms their counts - the observed entries under ``skip``, N P for a
+        term that arrives as partial sums of z^2 otherwise"""
+        kinds = aux["kinds"]
+        n = len(kinds)
+        dev = self.Xtilde.device
+        Ysrc = aux["Y"]
+        Yc = aux["Y"] = [SE._f32c(y) for y in Ysrc]
+        own = all(c is y for c, y in zip(Yc, Ysrc))
+        if weighted is None:
+            ones = self.__dict__.setdefault("_unit_weights", {})
+            w1 = ones.get((1, dev))
+            if w1 is None:
+                w1 = ones[(1, dev)] = torch.ones(1, dtype=torch.float64, device=dev)
+            aux["n_views"], aux["weights"] = [1] * n, [w1] * n
+            aux["view_off"] = [x for y in Yc for x in (0, int(y.shape[0]))]
+        starts, at = [], 0
+        for v in aux["n_views"]:
+            starts.append(at)
+            at += int(v) + 1
+
+        def sub(idx):  # the view tables of the terms ``idx``
+            return dict(n_views=[aux["n_views"][i] for i in idx],
+                        view_off=[x for i in idx for x in aux["view_off"][starts[i]:starts[i] + aux["n_views"][i] + 1]])
+
+        cacheable = weighted is None and own
+        pidx = [i for i in range(n) if kinds[i] == 1]
+        lg = SE.lgamma_sums(self, [Yc[i] for i in pidx], sub(pidx), skip, cacheable)
+        aux["lgam"] = [None] * n
+        for i, t in zip(pidx, lg):
+            aux["lgam"][i] = t
+        aux["skip"] = bool(skip)
+        gidx = [i for i in range(n) if kinds[i] == 0]
+        nobs = [None] * n
+        if skip and gidx:
+            for i, t in zip(gidx, SE.observed_counts(self, [Yc[i] for i in gidx], sub(gidx), cacheable)):
+                nobs[i] = t
+        elif gidx and aux.get("fuse_mods") is not None:
+            consts = self.__dict__.setdefault("_entry_counts", {})
+            for i in gidx:
+                if aux["fuse_mods"][i]:
+                    key = (int(Yc[i].numel()), dev)
+                    if key not in consts:
+                        consts[key] = torch.full([1], float(key[0]), dtype=torch.float64, device=dev)
+                    nobs[i] = consts[key]
+        aux["nobs"] = nobs if any(t is not None for t in nobs) else None
+
     def _close_loss(self, aux, kl, Fs, Ws, weighted, skip):
         """loss_fn's closing through the one loss node: the view tables of ``weighted`` (or None) join ``aux``; under
         ``skip`` so do the observed counts of every term (cached for observations that stay - not for a minibatch's
-        gathered rows nor for a converted copy, counted at every step); the loss comes back in the model's dtype"""
+        gathered rows nor for a converted copy, counted at every step); with a Poisson modality (aux["kinds"]) the tables
+        are _close_pois's; the loss comes back in the model's dtype"""
         if weighted is not None:
             aux.update(weighted)
-        if skip:
+        if aux.get("kinds") is not None:
+            self._close_pois(aux, weighted, skip)
+        elif skip:
             Ysrc = aux["Y"]
             Yc = aux["Y"] = [SE._f32c(y) for y in Ysrc]
             own = all(c is y for c, y in zip(Yc, Ysrc))  # (a copy made here dies with the step: its address says nothing)
@@ -971,10 +1064,30 @@ class VariationalGPSA(GPSA):
         return dict(n_views=n_views, view_off=view_off, weights=weights)
 
     def _loss_aux(self, data_dict):
-        """the loss nodes' ``aux``: observations, the modalities' entries of ``noise_variance`` (quirk 5), the KL scale"""
+        """the loss nodes' ``aux``: observations, the modalities' entries of ``noise_variance`` (quirk 5), the KL scale;
+        with a Poisson modality also the terms' kinds and the Poisson terms' per-row log offsets
+        (``data_dict[m]["log_offset"]``: optional, fp32 [N] on the model's device; refused for a Gaussian modality)"""
         nn_ = self.noise_variance.numel()
-        return dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
-                    noise_idx=[nn_ - self.n_modalities + i for i in range(self.n_modalities)], kl_scale=self.kl_scale)
+        aux = dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
+                   noise_idx=[nn_ - self.n_modalities + i for i in range(self.n_modalities)], kl_scale=self.kl_scale)
+        kinds = self._lik_kinds()
+        offs = []
+        for i, m in enumerate(self.modality_names):
+            o = data_dict[m].get("log_offset")
+            if o is not None and (kinds is None or kinds[i] == 0):
+                raise ValueError(f"loss_fn: data_dict[{m!r}] carries 'log_offset', but modality {m!r} has a Gaussian "
+                                 "likelihood (offsets belong to a Poisson modality: model.likelihood)")
+            if o is not None:
+                N = int(data_dict[m]["outputs"].shape[0])
+                if (not torch.is_tensor(o) or o.dtype != torch.float32 or tuple(o.shape) != (N,)
+                        or o.device != self.Xtilde.device):
+                    raise ValueError(f"loss_fn: data_dict[{m!r}]['log_offset'] must be a float32 tensor of shape ({N},) on "
+                                     f"{self.Xtilde.device}")
+                o = o if o.is_contiguous() else o.contiguous()
+            offs.append(o)
+        if kinds is not None:
+            aux["kinds"], aux["log_offset"] = kinds, offs
+        return aux
 
     # ------------------------------------------------------------------------------------------
     def loss_fn(self, data_dict, F_samples):
@@ -1000,6 +1113,8 @@ class VariationalGPSA(GPSA):
             fuse = getattr(cache, "fuse", None)
             if fuse is not None:
                 fuse["skip"] = skip  # (run_fused: gpsa_step_io.skip_missing)
+                # (run_fused: gpsa_step_likelihood for the modalities it enqueues)
+                fuse["lik"], fuse["log_offset"] = aux.get("kinds"), aux.get("log_offset")
             Fs, eff, run_i, run_Y, run_parts = [], [], [], [], []
             lmc_terms, Ws, shapes = {}, [], [None] * self.n_modalities
             for i, m in enumerate(self.modality_names):
@@ -1051,6 +1166,8 @@ class VariationalGPSA(GPSA):
             return self._close_loss(aux, kl, Fs, Ws, None, skip)
         f64 = torch.float64
         kl = None
+        aux0 = self._loss_aux(data_dict)  # (also refuses a log_offset on a Gaussian modality)
+        pois = aux0.get("kinds") is not None
         grouped = cache.batch is not None
         if grouped:  # every KL term of the step (all views, all outputs) in one launch each way
             kl = self._kl_grouped(cache)
@@ -1082,14 +1199,14 @@ class VariationalGPSA(GPSA):
                                              cache.Omega_F_fac[m]), l_first, 1).sum()
                 l_first += int(self.n_latent_outputs[m])
                 kl = term if kl is None else kl + term
-            if weighted is not None or skip:
+            if weighted is not None or skip or pois:
                 continue
             noise_u = self.noise_variance[-self.n_modalities + i]  # quirk 5 (used as a std)
             Y = data_dict[m]["outputs"]
             lls.append(E.LogLikFn.apply(F_samples[m], Y, noise_u))
-        if weighted is not None or skip:
+        if weighted is not None or skip or pois:
             Fs = [F_samples[m] for m in self.modality_names]
-            return self._close_loss(self._loss_aux(data_dict), kl, Fs, (), weighted, skip)
+            return self._close_loss(aux0, kl, Fs, (), weighted, skip)
         ll = lls[0] if len(lls) == 1 else torch.stack(lls)
         # -LL + kl_scale * KL in one launch (kl: the per-term vector of the grouped path, or a scalar)
         return E.ElboFn.apply(ll, kl, self.kl_scale).to(self.Xtilde.dtype)

@@ -42,6 +42,8 @@ def shard_data_dict(data_dict, rank, world):
             "outputs": d["outputs"][idx].contiguous(),
             "n_samples_list": new_ns,
         }
+        if d.get("log_offset") is not None:  # a Poisson modality's per-row log offsets travel with the rows
+            out[mod]["log_offset"] = d["log_offset"][idx].contiguous()
     return out
 
 
@@ -55,6 +57,8 @@ def shard_outputs(data_dict, rank, world):
             "outputs": d["outputs"][:, lo:hi].contiguous(),
             "n_samples_list": list(d["n_samples_list"]),
         }
+        if d.get("log_offset") is not None:  # (per row: every output shard keeps all of them)
+            out[mod]["log_offset"] = d["log_offset"]
     return out
 
 

@@ -96,6 +96,8 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
         the data GP is then evaluated THERE and not on the rows of ``X_spatial``, which may be omitted (given, it still
         yields ``G_mean`` / ``G_scale``).
     Y {mod: [N, P]} (at ``G_test``'s rows when that is given): adds ``lpd`` [N] fp64 and ``lpd_sum``.
+        Refused (ValueError) when a modality has a Poisson likelihood (``model.likelihood``): its ``F_mean`` / ``F_var`` are
+        the moments of the log rate, and the Gaussian closed form of ``lpd`` does not apply to counts.
     eps_G: the warp draws, a list over the non-fixed, non-empty views in order, each [S, n_v, D] (``inject_noise``'s
         layout); otherwise they come from ``generator`` or the device's default generator.
     rows_per_chunk / workspace_gb: the data stage's chunk, directly or as a budget (default DEFAULT_WORKSPACE_GB).
@@ -113,6 +115,12 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
     if warp == "mean" and eps_G is not None:
         raise ValueError("eps_G was given with warp='mean', which draws nothing")
     S = 1 if warp == "mean" else int(S)
+    if Y is not None:
+        for m in model.modality_names:
+            if getattr(model, "likelihood_of", lambda _m: "gaussian")(m) == "poisson":
+                raise ValueError(f"predict: Y was given, but modality {m!r} has a Poisson likelihood: lpd is the Gaussian "
+                                 "closed form and does not apply to counts (F_mean / F_var are the moments of its log "
+                                 "rate; call predict without Y)")
     o = E.ops()
     dev = model.Xtilde.device
     mods = model.modality_names

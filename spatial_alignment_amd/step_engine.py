@@ -798,7 +798,11 @@ class ElboLossFn(torch.autograd.Function):
           aux["n_views"] per term and aux["view_off"], every term's n_views + 1 row offsets concatenated)
           gpsa_elbo_loss_weighted_fwd / _bwd: loss = -(sum_i sum_v w_iv LL_iv) + kl_scale * sum(kl), every term from
           its materialised draws;
-      at least one term as partial sums  gpsa_elbo_loss_fused_fwd / _bwd;  none  gpsa_elbo_loss_fwd / _bwd."""
+      at least one term as partial sums  gpsa_elbo_loss_fused_fwd / _bwd;  none  gpsa_elbo_loss_fwd / _bwd.
+    aux["kinds"] (model.likelihood with a Poisson modality: per term its GPSA_LIK_* kind, with aux["lgam"] - the Poisson
+    terms' lgamma tables, lgamma_sums - and aux["log_offset"], per term a tensor or None) comes first: gpsa_elbo_loss_pois_fwd
+    / _bwd, which take all of the tables above (aux["skip"]: the NaN select; a Poisson LMC term:
+    gpsa_lmc_loglik_fused_pois_f32; a fused Poisson term's partial sums are those of y eta - exp(eta))."""
 
     @staticmethod
     def forward(ctx, aux, noise, kl, *ins):
@@ -811,7 +815,9 @@ class ElboLossFn(torch.autograd.Function):
         dev = Fs[0].device
         Fc, Yc, nz, klc = _loss_inputs(Fs, aux["Y"], noise, kl, fused)
         idx = [int(j) for j in aux["noise_idx"]]
-        lmc_op = torch.ops.gpsa.lmc_loglik_fused if nobs is None else torch.ops.gpsa.lmc_loglik_fused_skip
+        kinds = aux.get("kinds")
+        skip = bool(aux["skip"]) if kinds is not None else nobs is not None  # (the Gaussian closings: counts = skip)
+        lmc_op = torch.ops.gpsa.lmc_loglik_fused if not skip else torch.ops.gpsa.lmc_loglik_fused_skip
         lmc_saved = {}
         for i, wpos in lmc.items():
             Fl, W = Fc[i], Ws[wpos].detach()
@@ -821,7 +827,10 @@ class ElboLossFn(torch.autograd.Function):
             dFl, dW = torch.empty_like(Fl), torch.empty_like(W)
             wsl = _ops_mod.get_ops()._ws(int(_lib.load().gpsa_lmc_loglik_workspace(S_ * N_, L_, int(W.shape[1]), nparts)),
                                          Fl)
-            lmc_op(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
+            if kinds is not None and kinds[i] == _lib.LIK_KINDS["poisson"]:
+                torch.ops.gpsa.lmc_loglik_fused_pois(Fl, W, Yc[i], aux["log_offset"][i], int(skip), zpart, dFl, dW, wsl)
+            else:
+                lmc_op(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
             lmc_saved[i] = (dFl, dW, wpos)
             Fc[i] = zpart
         loss, ll, ws = _loss_outputs(n, dev)  # (after the LMC terms: they grow the same per-stream scratch)
@@ -831,7 +840,12 @@ class ElboLossFn(torch.autograd.Function):
             for i in range(n):
                 shapes += list(aux["term_shapes"][i]) if fused[i] else [int(d) for d in Fc[i].shape]
             tabs = (shapes, [int(z) for z in fused])
-        if nobs is not None:
+        if kinds is not None:
+            views = (list(aux["n_views"]), list(aux["view_off"]), list(aux["weights"])) if "weights" in aux else ([], [], [])
+            name = "elbo_loss_pois"
+            tabs = (tabs or ([], [])) + views + (list(nobs) if nobs is not None else [], [int(k) for k in kinds],
+                                                 list(aux["lgam"]), list(aux["log_offset"]), int(skip))
+        elif nobs is not None:
             views = (list(aux["n_views"]), list(aux["view_off"]), list(aux["weights"])) if "weights" in aux else ([], [], [])
             name, tabs = "elbo_loss_skip", (tabs or ([], [])) + views + (list(nobs),)
         elif "weights" in aux:
@@ -898,3 +912,28 @@ def observed_counts(model, Yc, views, cacheable):
             cache.clear()
         cache[key] = ([weakref.ref(y) for y in Yc], nobs)
     return nobs
+
+
+def lgamma_sums(model, Yc, views, skip, cacheable):
+    """-> per Y of ``Yc`` (the Poisson terms' observations) the device fp64 sums of lgamma(y + 1), one per view (``views``:
+    {"n_views", "view_off"} of THESE terms, or None = one view each; ``skip``: NaN entries left out); gpsa_lgamma_sum, no
+    host read.  The term's constant depends on no parameter: with ``cacheable`` it is kept on the model the way
+    observed_counts keeps its counts - keyed by data pointer, version and shape, a hit for the very tensors only."""
+    dev = Yc[0].device
+    nv = list(views["n_views"]) if views is not None else []
+    off = list(views["view_off"]) if views is not None else []
+    key = None
+    if cacheable and not torch.cuda.is_current_stream_capturing():
+        cache = model.__dict__.setdefault("_lgam_cache", {})
+        key = tuple((y.data_ptr(), y._version, tuple(y.shape)) for y in Yc) + (tuple(nv), tuple(off), bool(skip))
+        hit = cache.get(key)
+        if hit is not None and all(r() is y for r, y in zip(hit[0], Yc)):
+            return hit[1]
+    out = [torch.empty(nv[i] if nv else 1, dtype=torch.float64, device=dev) for i in range(len(Yc))]
+    ws = _ops_mod.get_ops()._ws(TO.lgamma_workspace_bytes(), out[0])
+    torch.ops.gpsa.lgamma_sum(Yc, nv, off, int(bool(skip)), out, ws)
+    if key is not None:
+        if len(cache) >= _NOBS_CACHE_MAX:
+            cache.clear()
+        cache[key] = ([weakref.ref(y) for y in Yc], out)
+    return out

@@ -25,8 +25,10 @@ each with
                                             gpsa::elbo_loss_weighted_fwd / _bwd        (csrc/loss_views.hip)
    partly observed outputs (opt-in)         gpsa::count_observed, gpsa::elbo_loss_skip_fwd / _bwd (csrc/loss_views.hip),
                                             gpsa::lmc_loglik_fused_skip                (model.skip_missing)
+   count outputs (opt-in)                   gpsa::lgamma_sum, gpsa::elbo_loss_pois_fwd / _bwd (csrc/poisson.hip,
+                                            csrc/loss_views.hip), gpsa::lmc_loglik_fused_pois  (model.likelihood)
 
-The six elbo_loss ops share their table builders (``_ll_arrays``, ``_grad_arrays``, ``_view_tables``) and are what the
+The eight elbo_loss ops share their table builders (``_ll_arrays``, ``_grad_arrays``, ``_view_tables``) and are what the
 one loss node, ``step_engine.ElboLossFn``, chooses among.
 
 The step-engine ops are the ones ``VariationalGPSA.forward`` / ``loss_fn`` / ``FusedAdam`` go through
@@ -588,3 +590,86 @@ def _lmc_loglik_fused_skip(F, W, Y, noise, noise_idx, zpart, dF, dW, ws):
 
 _engine_op("lmc_loglik_fused_skip(Tensor F, Tensor W, Tensor Y, Tensor noise, int noise_idx, Tensor(a!) zpart, "
            "Tensor(b!) dF, Tensor(c!) dW, Tensor(d!) ws) -> ()", _lmc_loglik_fused_skip)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# count outputs (model.likelihood; csrc/poisson.hip, csrc/loss_views.hip): the Poisson likelihood term
+# ---------------------------------------------------------------------------------------------------------
+def lgamma_workspace_bytes():
+    return int(_lib.load().gpsa_lgamma_sum_workspace()) + 64
+
+
+def _opt_ptrs(n, ts):
+    """host array of n device pointers, NULL for None; an absent table (empty list) is NULL"""
+    return (C.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in ts]) if ts else None
+
+
+def _lgamma_sum(Ys, n_views, view_off, skip, out, ws):
+    """gpsa_lgamma_sum: out[i][v] = sum of lgamma(Ys[i] + 1) over view v's rows (empty n_views: one view per term; skip:
+    NaN entries left out), device doubles written without a host read"""
+    n = len(Ys)
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    nv, offp, _, _, _keep = _view_tables(n, n_views, view_off)
+    _lib.check(_lib.load().gpsa_lgamma_sum(n, arr(Ys), (C.c_longlong * n)(*[int(y.shape[0]) for y in Ys]),
+                                           (C.c_int * n)(*[int(y.shape[1]) for y in Ys]), nv, offp, int(skip), arr(out),
+                                           ws.data_ptr(), ws.numel(), _raw_stream(ws.device.index)), "gpsa_lgamma_sum")
+
+
+_engine_op("lgamma_sum(Tensor[] Ys, int[] n_views, int[] view_off, int skip, Tensor(a!)[] out, Tensor(b!) ws) -> ()",
+           _lgamma_sum)
+
+
+def _pois_tables(n, n_views, view_off, weights, nobs, kinds, lgam, offsets):
+    nv, offp, Wp, _, keep = _view_tables(n, n_views, view_off, weights)
+    return (nv, offp, Wp, _opt_ptrs(n, nobs), (C.c_int * n)(*[int(k) for k in kinds]), _opt_ptrs(n, lgam),
+            _opt_ptrs(n, offsets)), keep
+
+
+def _elbo_loss_pois_fwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, kinds, lgam, offsets,
+                        skip, kl, kl_scale, loss, ll, ws):
+    """gpsa_elbo_loss_pois_fwd: the ELBO loss of a model with Poisson terms (kinds: GPSA_LIK_* per term; lgam / offsets /
+    nobs: per term a tensor or None; the other tables as elbo_loss_skip_fwd)"""
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
+    tabs, _keep = _pois_tables(n, n_views, view_off, weights, nobs, kinds, lgam, offsets)
+    _lib.check(_lib.load().gpsa_elbo_loss_pois_fwd(n, *terms, Zp, nparts, *tabs, int(skip), *_kl_args(kl), float(kl_scale),
+                                                   loss.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   _raw_stream(loss.device.index)), "gpsa_elbo_loss_pois_fwd")
+
+
+_engine_op("elbo_loss_pois_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
+           "int[] n_views, int[] view_off, Tensor[] weights, Tensor?[] nobs, int[] kinds, Tensor?[] lgam, "
+           "Tensor?[] offsets, int skip, Tensor? kl, float kl_scale, Tensor(a!) loss, Tensor(b!) ll, Tensor(c!) ws) -> ()",
+           _elbo_loss_pois_fwd)
+
+
+def _elbo_loss_pois_bwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, kinds, lgam, offsets,
+                        skip, gloss, n_kl, kl_scale, dFs, dnoise, dkl, ws):
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
+    tabs, _keep = _pois_tables(n, n_views, view_off, weights, nobs, kinds, lgam, offsets)
+    grads = _grad_arrays(dFs, dnoise, noise_idx, fused or None)
+    _lib.check(_lib.load().gpsa_elbo_loss_pois_bwd(n, *terms, Zp, nparts, *tabs, int(skip), gloss.data_ptr(), int(n_kl),
+                                                   float(kl_scale), *grads, 0 if dkl is None else dkl.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), _raw_stream(gloss.device.index)),
+               "gpsa_elbo_loss_pois_bwd")
+
+
+_engine_op("elbo_loss_pois_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
+           "int[] n_views, int[] view_off, Tensor[] weights, Tensor?[] nobs, int[] kinds, Tensor?[] lgam, "
+           "Tensor?[] offsets, int skip, Tensor gloss, int n_kl, float kl_scale, Tensor(a!)[] dFs, Tensor(b!) dnoise, "
+           "Tensor(c!)? dkl, Tensor(d!) ws) -> ()", _elbo_loss_pois_bwd)
+
+
+def _lmc_loglik_fused_pois(F, W, Y, offset, skip, zpart, dF, dW, ws):
+    """gpsa_lmc_loglik_fused_pois_f32: lmc_loglik_fused for a Poisson modality - F W is the log rate, zpart sums
+    y eta - exp(eta), eta = F W + offset[row] (offset: [N] or None)"""
+    S, N, L = (int(d) for d in F.shape)
+    _lib.check(_lib.load().gpsa_lmc_loglik_fused_pois_f32(F.data_ptr(), W.data_ptr(), Y.data_ptr(),
+                                                          0 if offset is None else offset.data_ptr(), int(skip), S, N, L,
+                                                          int(W.shape[1]), zpart.data_ptr(), zpart.numel(),
+                                                          dF.data_ptr(), dW.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                          _raw_stream(F.device.index)),
+               "gpsa_lmc_loglik_fused_pois_f32")
+
+
+_engine_op("lmc_loglik_fused_pois(Tensor F, Tensor W, Tensor Y, Tensor? offset, int skip, Tensor(a!) zpart, "
+           "Tensor(b!) dF, Tensor(c!) dW, Tensor(d!) ws) -> ()", _lmc_loglik_fused_pois)
