@@ -5,7 +5,9 @@ are log rates: every spot n gets a size factor exp(o[n]) and its counts are y[n,
 With ``model.likelihood = "poisson"`` and ``data_dict[m]["log_offset"] = o`` the fit runs on the counts themselves - no
 log transform, no Gaussian noise model - and ``predict`` returns the moments of the log rate, printed as an RMSE against
 the simulated f.  Next to it, the usual route: the same model with the Gaussian likelihood on log1p of the
-size-normalised counts.
+size-normalised counts.  It ends with the held-out score: a second draw of counts at the same spots, scored by
+``predict(..., Y=counts, scale="response", log_offset=o)`` - the Poisson-lognormal log predictive density ``lpd_sum`` and
+the expected counts ``Y_mean``.
 usage: python examples/poisson_counts.py [steps]"""
 import os
 import sys
@@ -56,3 +58,12 @@ dd_g = simulate.as_data_dict(X, torch.log1p(Y / torch.exp(o)[:, None]), [n, n])
 model_g = make_model(dd_g, m=25, device=dev)
 fit(model_g, on_device(dd_g), steps, lr=1e-2, S=3, sync_every=100)
 print(f"Gaussian likelihood on log1p(counts / size factor): RMSE against the log rate {log_rate_rmse(model_g):.4f}")
+
+# held-out counts at the same spots: the score of the Poisson fit on the scale of the observations
+Y_new = torch.poisson(torch.exp(Fl + o[:, None]), generator=gen)
+view_idx = {mod: [torch.arange(n), torch.arange(n, 2 * n)]}
+out = predict(model, {mod: X.to(dev)}, view_idx, {mod: 2 * n}, S=10, Y={mod: Y_new}, scale="response",
+              log_offset={mod: o.to(dev)}, generator=torch.Generator(device=dev).manual_seed(3))[mod]
+rmse = float((out.Y_mean.cpu() - Y_new).pow(2).mean().sqrt())
+print(f"held-out counts: lpd_sum {float(out.lpd_sum):.1f} ({float(out.lpd_sum) / Y_new.numel():.4f} per count), "
+      f"RMSE of Y_mean {rmse:.3f} (the counts' own sd {float(Y_new.std()):.3f})")

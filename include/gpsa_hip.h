@@ -944,6 +944,25 @@ int gpsa_predict_moments_f32(const float* meanT, const float* v, const double* q
                              const float* Y, float* F_mean, float* F_var, float* Fl_mean, float* Fl_var, double* lpd,
                              void* stream);
 
+/* ---- prediction of counts: the same layer closed under a Poisson likelihood (csrc/predict_counts.hip) -----------------
+ * Inputs, layout and the per-sample m_s, u_s exactly as gpsa_predict_moments_f32 forms them (mix with W per sample,
+ * + 2e-5, never tau).  The log rate of row r, output p under sample s is eta ~ Normal(mu, u), mu = m_s[r,p] +
+ * log_offset[r] (log_offset [c] fp32 or NULL = 0), u = u_s[r,p]; with lam_s = exp(mu + u/2)
+ *   Y_mean[r,p] = mean_s lam_s,   Y_var[r,p] = Y_mean + mean_s[lam_s^2 expm1(u)] + var_s(lam_s)
+ * (fp64, the between-sample term from sums centred on the first sample).  Y [c,P] fp32 (may be NULL, then lpd must be
+ * NULL too, and neither a mode nor a quadrature is computed):
+ *   lpd[r] = sum_p log( mean_s Int Poisson(Y[r,p]; e^eta) Normal(eta; mu, u) d eta )   in fp64, NaN entries skipped,
+ * each integral by 20-node Gauss-Hermite quadrature centred on the mode of y eta - e^eta - (eta - mu)^2 / (2u) (8 Newton
+ * iterations from min(mu + u y, max(mu, log y))), the samples mixed through a running maximum.  Y is not validated: the
+ * formula is taken as written for any real y > -1 (lgamma(y + 1) by Stirling's series for a positive argument; y <= -1
+ * gives NaN, where the library's lgamma would give its value at a non-positive argument).  Accuracy of one integral against brute force: 1.9e-10 (u <= 0.5), 2.0e-8
+ * (u <= 1), 1.8e-6 (u <= 2), 4.6e-5 (u <= 4) as |error| / max(1, |log density|); nothing is measured beyond u = 4.
+ * Y_mean / Y_var [c,P] fp32 are required.  No workspace.  Any c, S, L, P >= 1; with W: L <= 64 (GPSA_EUNSUPPORTED beyond),
+ * GPSA_EINVAL on W == NULL with P != L, a missing array, or Y and lpd not both given / both NULL. */
+int gpsa_predict_counts_f32(const float* meanT, const float* v, const double* q, const float* var_u, long long c, int S,
+                            int L, int P, const float* W, const float* log_offset, const float* Y, float* Y_mean,
+                            float* Y_var, double* lpd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

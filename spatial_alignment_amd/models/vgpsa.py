@@ -778,7 +778,9 @@ class VariationalGPSA(GPSA):
     def predict(self, X_spatial=None, view_idx=None, Ns=None, **kwargs):
         """Closed-form posterior moments and the held-out log predictive density (``predict.predict``): ``G_mean`` /
         ``G_scale`` of the warp, ``F_mean`` / ``F_var`` of the outputs over S warp samples, ``lpd`` with observations -
-        in row chunks, without draws of the data GP and without touching the training state."""
+        in row chunks, without draws of the data GP and without touching the training state.  ``scale="response"``
+        (with ``log_offset``) adds ``Y_mean`` / ``Y_var`` on the scale of the observations and scores counts of a Poisson
+        modality."""
         from ..predict import predict as _predict
 
         return _predict(self, X_spatial, view_idx, Ns, **kwargs)

@@ -506,6 +506,43 @@ class HipOps:
         _lib.check(rc, "gpsa_predict_moments_f32")
         return Fm, Fv, Lm, Lv, lpd
 
+    def predict_counts(self, meanT, v, q, var_u, S, W=None, log_offset=None, Y=None, out=None):
+        """gpsa_predict_counts_f32: the same layer closed under a Poisson likelihood (log link).  meanT, v, q, var_u, S, W
+        as ``predict_moments`` takes them; log_offset [c] fp32 or None (= 0), Y [c,P] counts (NaN = missing) or None.
+        -> (Y_mean, Y_var [c,P] fp32, lpd [c] fp64 or None); ``out``: the same three, preallocated."""
+        meanT, v, q = self._c(meanT), self._c(v), self._c(q.double())
+        L, SC = meanT.shape
+        S = int(S)
+        if S < 1 or SC % S != 0 or tuple(v.shape) != (L, SC) or q.numel() != SC:
+            raise ValueError(f"predict_counts: meanT {tuple(meanT.shape)}, v {tuple(v.shape)}, q {tuple(q.shape)} do not "
+                             f"hold S = {S} samples of the same rows")
+        c = SC // S
+        var_u = self._f32(var_u).reshape(-1)
+        W = None if W is None else self._f32(W)
+        if W is not None and W.shape[0] != L:
+            raise ValueError(f"predict_counts: W has {W.shape[0]} rows, the data GP {L} latent outputs")
+        P = L if W is None else int(W.shape[1])
+        log_offset = None if log_offset is None else self._f32(log_offset)
+        if log_offset is not None and tuple(log_offset.shape) != (c,):
+            raise ValueError(f"predict_counts: log_offset has shape {tuple(log_offset.shape)}, the chunk needs ({c},)")
+        Y = None if Y is None else self._f32(Y)
+        if Y is not None and tuple(Y.shape) != (c, P):
+            raise ValueError(f"predict_counts: Y has shape {tuple(Y.shape)}, the chunk needs ({c}, {P})")
+        dev, f32 = meanT.device, torch.float32
+        if out is None:
+            out = (torch.empty(c, P, dtype=f32, device=dev), torch.empty(c, P, dtype=f32, device=dev),
+                   torch.empty(c, dtype=torch.float64, device=dev) if Y is not None else None)
+        Ym, Yv, lpd = out
+        for t, sh, dt in ((Ym, (c, P), f32), (Yv, (c, P), f32), (lpd, (c,), torch.float64)):
+            assert t is None or (tuple(t.shape) == sh and t.dtype == dt and t.is_contiguous()), (sh, dt)
+        rc = self.lib.gpsa_predict_counts_f32(_p(meanT), _p(v), _p(q), _p(var_u), c, S, L, P, _p(W), _p(log_offset),
+                                              _p(Y), _p(Ym), _p(Yv), _p(lpd), self._stream(meanT))
+        if rc == _lib.GPSA_EUNSUPPORTED:
+            raise _lib.GpsaHipError(f"gpsa_predict_counts_f32: an LMC mix of {L} latent outputs (more than 64, the "
+                                    "limit the LDS-resident W shares with the training kernels)")
+        _lib.check(rc, "gpsa_predict_counts_f32")
+        return Ym, Yv, lpd
+
     @staticmethod
     def _f32(t):
         t = t if t.dtype == torch.float32 else t.float()

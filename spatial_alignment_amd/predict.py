@@ -18,6 +18,22 @@ module closes the same layers as MOMENTS, row chunk by row chunk:
   and, with observations ``Y``, ``lpd[n] = sum_p log mean_s Normal(Y[n,p]; m_s[n,p], u_s[n,p] + tau^2)`` (always with the
   noise; NaN entries of ``Y`` contribute 0).
 
+Count outputs (``model.likelihood``: a Poisson modality's draws are log rates): the fields above stay on the log-rate
+scale.  ``scale="response"`` adds the prediction on the scale of the observations, ``Y_mean`` / ``Y_var``, under each
+modality's own likelihood, and makes ``lpd`` that likelihood's held-out log density:
+
+* Gaussian modality: ``Y_mean = F_mean``, ``Y_var = F_var`` with the noise ``tau^2`` in it whatever ``include_noise``
+  says, ``lpd`` the closed form above.
+* Poisson modality, per sample ``eta ~ Normal(mu, u)`` with ``mu = m_s + log_offset[n]``, ``u = u_s`` (never ``tau``):
+  ``lam_s = exp(mu + u/2)``, ``Y_mean = mean_s lam_s``, ``Y_var = Y_mean + mean_s[lam_s^2 expm1(u)] + var_s(lam_s)`` and
+  ``lpd[n] = sum_p log mean_s Int Poisson(y; e^eta) Normal(eta; mu, u) d eta`` (``gpsa_predict_counts_f32``).  The integral
+  has no closed form: it is taken by ``len(GH_NODES)``-node Gauss-Hermite quadrature centred on the integrand's mode
+  (``NEWTON_ITERATIONS`` Newton iterations).  Against a brute-force integral its error, as ``|error| / max(1, |value|)``,
+  is 1.9e-10 for u <= 0.5, 2.0e-8 for u <= 1, 1.8e-6 for u <= 2 and 4.6e-5 for u <= 4 (tests/test_predict_counts.py);
+  BEYOND u = 4 NOTHING IS MEASURED.  ``y`` is not validated (the formula is taken as written for any real y > -1, as
+  in training; y <= -1 gives NaN);
+  ``include_noise`` has no meaning for the ``Y_*`` of a Poisson modality.
+
 Memory: the data stage handles ``c`` rows at a time - sample locations, covariance panel, projection, the two
 contractions and ``gpsa_predict_moments_f32`` straight into the rows' slice of the results - so the peak beyond the
 results is about ``S c (4 M + 8 L + 8 D)`` bytes plus a fixed fp64 covariance block (PROJECT_BLOCK columns) and the
@@ -35,10 +51,38 @@ DEFAULT_WORKSPACE_GB = 0.5
 
 TWO_JITTER = 2e-5  # diagonal_offset added twice by the reference's conditional (quirk 3)
 
+# The Gauss-Hermite rule of the Poisson-lognormal integral (scale="response"): (x_k, log w_k + x_k^2), Q = 20 nodes, and the
+# number of Newton iterations for the integrand's mode.  The kernel (csrc/predict_counts.hip) carries the same literals;
+# tests/test_predict_counts.py restates the rule in numpy from THESE and holds it against a brute-force integral.
+GH_NODES = (
+    (-5.387480890011233, -0.10692622802020324),
+    (-4.603682449550744, -0.35050407841539055),
+    (-3.944764040115625, -0.4743672219775181),
+    (-3.3478545673832163, -0.5529289199616052),
+    (-2.7888060584281305, -0.6072415536850873),
+    (-2.2549740020892757, -0.6461102649118216),
+    (-1.7385377121165861, -0.6739741099862373),
+    (-1.234076215395323, -0.6933054504113765),
+    (-0.7374737285453944, -0.7055368459223146),
+    (-0.24534070830090124, -0.7114710404116901),
+    (0.24534070830090124, -0.7114710404116901),
+    (0.7374737285453944, -0.7055368459223146),
+    (1.234076215395323, -0.6933054504113765),
+    (1.7385377121165861, -0.6739741099862373),
+    (2.2549740020892757, -0.6461102649118216),
+    (2.7888060584281305, -0.6072415536850873),
+    (3.3478545673832163, -0.5529289199616052),
+    (3.944764040115625, -0.4743672219775181),
+    (4.603682449550744, -0.35050407841539055),
+    (5.387480890011233, -0.10692622802020324),
+)
+NEWTON_ITERATIONS = 8
+
 
 class Prediction(dict):
     """one modality's result: a dict whose entries also read as attributes (``G_mean``, ``G_scale``, ``F_mean``, ``F_var``,
-    ``F_latent_mean``, ``F_latent_var``, ``lpd``, ``lpd_sum``; None where not asked for)"""
+    ``F_latent_mean``, ``F_latent_var``, ``lpd``, ``lpd_sum``; None where not asked for; with ``scale="response"`` also
+    ``Y_mean``, ``Y_var``)"""
 
     def __getattr__(self, name):
         try:
@@ -88,7 +132,8 @@ def _project_blocks(model, o, fac, Z, Gf, ls_u, var_u):
 
 @torch.no_grad()
 def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample", G_test=None, Y=None,
-            include_noise=False, latent=False, eps_G=None, generator=None, rows_per_chunk=None, workspace_gb=None):
+            include_noise=False, latent=False, eps_G=None, generator=None, rows_per_chunk=None, workspace_gb=None,
+            scale="link", log_offset=None):
     """Posterior moments of ``model`` (a VariationalGPSA) at its own rows or at ``G_test``; see the module docstring.
 
     X_spatial {mod: [N, D]}, view_idx, Ns: as ``forward`` takes them (view_idx / Ns default to the model's own).
@@ -96,8 +141,15 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
         the data GP is then evaluated THERE and not on the rows of ``X_spatial``, which may be omitted (given, it still
         yields ``G_mean`` / ``G_scale``).
     Y {mod: [N, P]} (at ``G_test``'s rows when that is given): adds ``lpd`` [N] fp64 and ``lpd_sum``.
-        Refused (ValueError) when a modality has a Poisson likelihood (``model.likelihood``): its ``F_mean`` / ``F_var`` are
-        the moments of the log rate, and the Gaussian closed form of ``lpd`` does not apply to counts.
+        With ``scale="link"`` refused (ValueError) when a modality has a Poisson likelihood (``model.likelihood``): its
+        ``F_mean`` / ``F_var`` are the moments of the log rate, and the Gaussian closed form of ``lpd`` does not apply to
+        counts; ``scale="response"`` scores them.
+    scale: ``"link"`` (default): the fields above and nothing else.  ``"response"``: every Prediction also carries
+        ``Y_mean`` / ``Y_var`` [N, P] fp32, the prediction on the scale of the observations under the modality's own
+        likelihood, and ``lpd`` is that likelihood's (module docstring; a Poisson modality's integral is measured for
+        u <= 4 only).  ``F_*`` and ``G_*`` do not change.
+    log_offset {mod: [N] fp32} (at ``G_test``'s rows when that is given; only with ``scale="response"``): per-row offsets of
+        a Poisson modality's log rate, as ``loss_fn`` takes them in ``data_dict[m]["log_offset"]``.  Absent: 0.
     eps_G: the warp draws, a list over the non-fixed, non-empty views in order, each [S, n_v, D] (``inject_noise``'s
         layout); otherwise they come from ``generator`` or the device's default generator.
     rows_per_chunk / workspace_gb: the data stage's chunk, directly or as a budget (default DEFAULT_WORKSPACE_GB).
@@ -114,13 +166,28 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
         raise ValueError("predict needs X_spatial (rows to align and predict) or G_test (aligned locations)")
     if warp == "mean" and eps_G is not None:
         raise ValueError("eps_G was given with warp='mean', which draws nothing")
+    if scale not in ("link", "response"):
+        raise ValueError(f"scale must be 'link' or 'response', not {scale!r}")
     S = 1 if warp == "mean" else int(S)
-    if Y is not None:
+    response = scale == "response"
+    pois = {m: getattr(model, "likelihood_of", lambda _m: "gaussian")(m) == "poisson" for m in model.modality_names}
+    if Y is not None and not response:
         for m in model.modality_names:
-            if getattr(model, "likelihood_of", lambda _m: "gaussian")(m) == "poisson":
+            if pois[m]:
                 raise ValueError(f"predict: Y was given, but modality {m!r} has a Poisson likelihood: lpd is the Gaussian "
                                  "closed form and does not apply to counts (F_mean / F_var are the moments of its log "
-                                 "rate; call predict without Y)")
+                                 "rate; call predict without Y, or with scale=\"response\" for the counts' own moments "
+                                 "and log density)")
+    if log_offset is not None:
+        if not response:
+            raise ValueError("predict: log_offset was given with scale='link'; offsets act on the counts' scale only "
+                             "(scale=\"response\")")
+        for m in log_offset:
+            if m not in pois:
+                raise ValueError(f"predict: log_offset names the modality {m!r}; the model has {list(pois)}")
+            if log_offset[m] is not None and not pois[m]:
+                raise ValueError(f"predict: log_offset[{m!r}] was given, but modality {m!r} has a Gaussian likelihood "
+                                 "(offsets belong to a Poisson modality: model.likelihood)")
     o = E.ops()
     dev = model.Xtilde.device
     mods = model.modality_names
@@ -154,6 +221,10 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
     if Y is not None:
         for m in mods:
             _check_rows("Y", m, Y[m], (n_out[m], P[m]))
+    if log_offset is not None:
+        for m, t in log_offset.items():
+            if t is not None:
+                _check_rows("log_offset", m, t, (n_out[m],))
     free = [v for v in range(V) if not model._is_fixed(v)]
     nonempty = [v for v in free if rows_of is not None and sum(rows_of[v][m][1] for m in mods) > 0]
     sampled = warp == "sample" and Gt is None
@@ -269,6 +340,10 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
         Flm, Flv = (new(n, L), new(n, L)) if latent else (None, None)
         lpd = new(n, dt=f64) if Y is not None else None
         Ym = None if Y is None else Y[m].to(device=dev, dtype=f32).contiguous()
+        counts = response and pois[m]  # the Gaussian closing then leaves lpd alone: the counts' closing writes it
+        Cm, Cv = (new(n, P[m]), new(n, P[m])) if counts else (None, None)
+        off = None if not counts or log_offset is None or log_offset.get(m) is None else \
+            log_offset[m].to(device=dev, dtype=f32).contiguous()
         for a in range(0, n, c):
             b = min(n, a + c)
             if Gt is not None:
@@ -283,12 +358,21 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
             vq = o.quadform_fwd(alpha, Om_F)
             cut = lambda t: None if t is None else t[a:b]
             o.predict_moments(meanT, vq, q, var32, S_m, W=W, noise_u=noise_u, include_noise=include_noise,
-                              Y=cut(Ym), latent=latent, out=(Fm[a:b], Fv[a:b], cut(Flm), cut(Flv), cut(lpd)))
+                              Y=None if counts else cut(Ym), latent=latent,
+                              out=(Fm[a:b], Fv[a:b], cut(Flm), cut(Flv), None if counts else cut(lpd)))
+            if counts:
+                o.predict_counts(meanT, vq, q, var32, S_m, W=W, log_offset=cut(off), Y=cut(Ym),
+                                 out=(Cm[a:b], Cv[a:b], cut(lpd)))
             del alpha, meanT, vq, q
         del Om_F
+        if response and not counts:  # Gaussian: the observation's moments are the field's, with the noise
+            tau = torch.exp(noise_u.double()) + 1e-5  # vgpsa.py:217; a standard deviation (quirk 5)
+            Cm, Cv = Fm.clone(), Fv.clone() if include_noise else (Fv.double() + tau * tau).to(f32)  # (no aliases)
         res[m] = Prediction(
             G_mean=None if G_mean64 is None else G_mean64[m].to(f32),
             G_scale=None if G_scale64 is None else G_scale64[m].to(f32),
             F_mean=Fm, F_var=Fv, F_latent_mean=Flm, F_latent_var=Flv, lpd=lpd,
             lpd_sum=None if lpd is None else lpd.sum())
+        if response:
+            res[m]["Y_mean"], res[m]["Y_var"] = Cm, Cv
     return res

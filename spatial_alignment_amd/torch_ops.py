@@ -17,6 +17,7 @@ each with
                                             gpsa::quadform_bwd_omega
    (4) reparameterised draws                gpsa::gauss_sample_F (+ _bwd)              (vgpsa.py:423-426)
        ... closed as moments (prediction)   gpsa::predict_moments                      (predict.py)
+       ... closed as counts (prediction)    gpsa::predict_counts                       (predict.py, scale="response")
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
@@ -244,6 +245,27 @@ def _(meanT, v, q, var_u, S, W=None, noise_u=None, include_noise=False, Y=None, 
     P = L if W is None else W.shape[1]
     lat = (c, L) if latent else (0,)
     return (meanT.new_empty(c, P), meanT.new_empty(c, P), meanT.new_empty(lat), meanT.new_empty(lat),
+            meanT.new_empty(c if Y is not None else 0, dtype=torch.float64))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# (4c) the same layer closed under a Poisson likelihood: moments of the counts and the Poisson-lognormal log density
+# ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("gpsa::predict_counts", mutates_args=(), device_types="cuda")
+def predict_counts(meanT: torch.Tensor, v: torch.Tensor, q: torch.Tensor, var_u: torch.Tensor, S: int,
+                   W: Optional[torch.Tensor] = None, log_offset: Optional[torch.Tensor] = None,
+                   Y: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """meanT, v [L, S*c]; q [S*c]; log_offset [c] -> (Y_mean, Y_var [c, P], lpd [c] fp64); lpd is an empty tensor without
+    Y (predict.py with scale="response"; csrc/predict_counts.hip)"""
+    Ym, Yv, lpd = _o().predict_counts(meanT, v, q, var_u, S, W, log_offset, Y)
+    return Ym, Yv, meanT.new_empty(0, dtype=torch.float64) if lpd is None else lpd
+
+
+@predict_counts.register_fake
+def _(meanT, v, q, var_u, S, W=None, log_offset=None, Y=None):
+    L, c = meanT.shape[0], meanT.shape[1] // S
+    P = L if W is None else W.shape[1]
+    return (meanT.new_empty(c, P), meanT.new_empty(c, P),
             meanT.new_empty(c if Y is not None else 0, dtype=torch.float64))
 
 

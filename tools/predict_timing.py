@@ -9,6 +9,11 @@ route A's S-draw average carries against F_mean with the same warp draws (RMS ov
   python tools/predict_timing.py                      # BASELINE config 2's size: 2 x 10 000 spots, 50 outputs, M = 200
   python tools/predict_timing.py --side 316           # config 5's row count (2 x 99 856), 50 outputs
   python tools/predict_timing.py --once               # one predict() call, for rocprofv3 --kernel-trace --stats
+  python tools/predict_timing.py --counts             # the counts leg: scale="response" on a Poisson model, see below
+--counts times three calls in alternating blocks: the Gaussian call with Y (route B), predict(scale="response",
+log_offset=...) of the same model with likelihood "poisson" with Y (counts/Y: B + the quadrature of
+gpsa_predict_counts_f32), and the same without Y (counts: B + the counts' moments alone).  Like the other legs it only
+appends its line to --out; the README row and docs/LAB_NOTES.md are brought up to date from that line by hand.
 Appends one JSON line per run to --out (default profiles/predict_timing.jsonl).
 """
 import argparse
@@ -56,6 +61,7 @@ def main():
     ap.add_argument("--chunks", default="2000,5000", help="rows_per_chunk values next to the default")
     ap.add_argument("--skip-a", action="store_true", help="do not run route A (its two [S, N, L] tensors do not fit)")
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--counts", action="store_true", help="time the counts leg (scale='response') next to route B")
     ap.add_argument("--out", default=os.path.join("profiles", "predict_timing.jsonl"))
     args = ap.parse_args()
 
@@ -73,6 +79,36 @@ def main():
 
     def route_b(c=None):
         return model.predict(X, view_idx, Ns, S=S, eps_G=eps_G, Y=Y, rows_per_chunk=c)
+
+    if args.counts:
+        Yc = {mod: torch.floor(torch.exp(torch.clamp(Y[mod], max=3.0)))}
+        off = {mod: 0.25 * torch.sin(torch.arange(N, dtype=torch.float32, device=dev))}
+
+        def counts(with_y):
+            model.likelihood = "poisson"
+            try:
+                return model.predict(X, view_idx, Ns, S=S, eps_G=eps_G, Y=Yc if with_y else None, scale="response",
+                                     log_offset=off)
+            finally:
+                model.likelihood = "gaussian"
+
+        routes = {"B": route_b, "counts/Y": lambda: counts(True), "counts": lambda: counts(False)}
+        for fn in routes.values():
+            fn()
+            fn()
+        times = {k: [] for k in routes}
+        for _ in range(args.blocks):
+            for k, fn in routes.items():
+                times[k].append(timed(fn, args.calls))
+        rec = dict(tool="predict_timing", leg="counts", side=args.side, N=N, outputs=L, M=args.m, S=S, blocks=args.blocks,
+                   calls_per_block=args.calls, exponentials_per_call=(9 + 40 + 3) * S * N * L,
+                   ms={k: dict(median=statistics.median(v), min=min(v), max=max(v)) for k, v in times.items()})
+        line = json.dumps(rec)
+        print(line)
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(line + "\n")
+        return
 
     if args.once:
         route_b()
