@@ -923,6 +923,94 @@ int gpsa_lmc_loglik_fused_pois_f32(const float* F, const float* W, const float* 
  * set.  GPSA_LIK_GAUSSIAN (a new plan's state; log_offset must be NULL) goes back.  Set it before enqueuing m's pass. */
 int gpsa_step_likelihood(void* plan, int m, int kind, const float* log_offset);
 
+/* ---- count outputs: the negative binomial likelihood with a dispersion per output (csrc/negbin.hip,
+ * csrc/loss_views.hip; opt-in: model.likelihood = "negative_binomial") -------------------------------------------------------------
+ * For a term of kind GPSA_LIK_NEGBIN the draws are log means.  log_disp [P] fp32 is rho, r_p = exp(rho_p) the "size";
+ * with eta[s,n,p] = F[s,n,p] + log_offset[n] and a = eta - rho_p,
+ *   log NB(y; mu, r) = [lgamma(y + r) - lgamma(r) - lgamma(y + 1)] + y a - (y + r) softplus(a),
+ *   softplus(a) = max(a, 0) + log1p(exp(-|a|)),  sigma(a) = 1 / (1 + exp(-a)),
+ *   LL = sum_v w[v] ( sum_{s, (n,p) in v} t / S + sum_{(n,p) in v} c ),  t = y a - (y + r) softplus(a),
+ *                                                                      c = lgamma(y + r) - lgamma(r) - lgamma(y + 1),
+ *   dLoss/dF = gloss w[v] ((y + r) sigma(a) - y) / S,
+ *   dLL/drho_p = sum_v w[v] ( sum_{s,n} u / S + sum_n r (psi(y + r) - psi(r)) ),  u = -r softplus(a) + (y + r) sigma(a) - y.
+ * No exp(eta) appears: the term stays finite where the Poisson term overflows (eta = 136 gives t = -136, dF = 1 in fp32).
+ * expf / log1pf are the exact ones; the per-element terms are fp32, every sum is fp64 in a fixed order (no atomics).  Y is
+ * NOT validated; skip != 0: a NaN in Y is a missing observation (dF exactly 0, nothing added to any sum, rho's included);
+ * skip == 0: a NaN propagates.  The term's noise_u entry does not enter; its gradient is written as exactly 0.
+ * gpsa_nb_const: the draw-independent pieces, once per step (they depend on rho), in fp64 per term:
+ *   csum[i][v]   = sum over the rows of view v of lgamma(y + r) - lgamma(r)      (unweighted, like gpsa_lgamma_sum's table)
+ *   dconst[i][p] = sum_v w_i[v] sum_{n in v} r_p (psi(y + r_p) - psi(r_p))       (w NULL or w[i] NULL: weights of 1)
+ * psi: the recurrence up to x >= 8, then the asymptotic series through x^-14; y + r <= 0 gives NaN there.  A column
+ * reduction over Y [N, P]: threads along p, row blocks into fp64 partials, a fixed-order finish.  The lgamma(y + 1) table
+ * stays gpsa_lgamma_sum's.  workspace >= the largest gpsa_nb_const_workspace(N_i, P_i, n_views_i) bytes of the call. */
+#define GPSA_LIK_NEGBIN 2
+long long gpsa_nb_const_workspace(long long N, int P, int n_views);
+int gpsa_nb_const(int n_ll, const float* const* Y, const long long* N, const int* P, const float* const* log_disp,
+                  const int* n_views, const long long* const* view_off, const double* const* w, int skip,
+                  double* const* csum, double* const* dconst, void* workspace, long long workspace_bytes, void* stream);
+/* The ELBO loss closing for a model with at least one negative binomial term: the tables of gpsa_elbo_loss_pois_fwd /
+ * _bwd plus, per term, log_disp[i] ([P_i] fp32; NB terms), csum[i] / dconst[i] (gpsa_nb_const with the same views, weights
+ * and skip flag) and lgam[i] (gpsa_lgamma_sum; Poisson AND NB terms).  _bwd writes ddisp[i] ([P_i] fp32; NB terms): the
+ * gradient of the loss with respect to rho, gloss included.  An NB term from its draws runs loglik_nb_kernel; one that
+ * arrives as nparts partial sums of t (zpart[i]; one view) brings usum[i], the [P_i] fp64 per-output sums of u over (s, n).
+ * Gaussian and Poisson terms in the same call are closed exactly as gpsa_elbo_loss_pois_* closes them.  Every check runs
+ * before the first launch.  workspace >= gpsa_elbo_loss_nb_workspace(n_ll, S, N, P, n_views, kind) bytes (n_views NULL:
+ * one view per term; kind: the call's table - only its NB terms have column partials - or NULL: every term counted as NB). */
+/* gpsa_quadform_elbo_pois_f32 / _delta_pois_f32 with the negative binomial term in the closing (panel_elbo_nb_kernel): per
+ * (l, c), c = s N + n, a = F + log_offset[n] - log_disp[l];  dmeanT = dLoss/dF = ((y + r) sigma(a) - y) / S;  g as there;
+ * part[] sums t.  u_elems [L, C] fp32 receives u per element at the index of g and dmeanT (exact 0 for a missing entry;
+ * columns the kernel does not own are not written: C is covered exactly), and usum [L] fp64 its per-output sums over C
+ * from a fixed-order row reduction - gpsa_elbo_loss_nb_bwd's usum[i].  noise_u is not read (may be NULL); log_offset [N] or
+ * NULL; skip as above.  fp32 contraction only; same sizes, workspace query (gpsa_quadform_elbo_f32_workspace) and
+ * GPSA_EUNSUPPORTED cases. */
+int gpsa_quadform_elbo_nb_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                              const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                              long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
+                              float* FT, const float* log_offset, const float* log_disp, float* u_elems, double* usum,
+                              int skip, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_quadform_elbo_delta_nb_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                    const float* delta, const double* q, const float* var_u, const float* eps,
+                                    const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                    float* abar, double* part, float* FT, const float* log_offset, const float* log_disp,
+                                    float* u_elems, double* usum, int skip, void* workspace, long long workspace_bytes,
+                                    void* stream);
+/* The step engine's setter for a negative binomial modality m: stage 2 of gpsa_step_forward then runs
+ * gpsa_quadform_elbo_nb_f32 / _delta_nb_f32 for m with log_disp [L_m], u_elems [L_m, S N_m] fp32, usum [L_m] fp64 and
+ * log_offset ([N_m] or NULL), all of which must stay valid while the plan may run; gpsa_step_io.skip_missing is the skip
+ * flag and ll_part[m] goes to gpsa_elbo_loss_nb_fwd / _bwd with usum as usum[i].  It is the ONLY way to that kind:
+ * gpsa_step_likelihood keeps refusing every kind but GPSA_LIK_GAUSSIAN and GPSA_LIK_POISSON, and either of those goes back
+ * (and forgets the tensors).  A NULL log_disp, u_elems or usum is GPSA_EINVAL; a pass enqueued for a modality of this kind
+ * without them is GPSA_EINVAL before any launch.  In a bf16x3 plan the pass runs the fp32 NB kernel (there is no x3 NB
+ * closing; the Gram stays on x3) and gpsa_step_contraction reports it for as long as the kind is set. */
+int gpsa_step_dispersion(void* plan, int m, const float* log_disp, float* u_elems, double* usum, const float* log_offset);
+/* gpsa_lmc_loglik_fused_pois_f32 for a negative binomial LMC modality (lmc_mfma_nb_kernel): F_obs = F W is the log mean,
+ * dF_obs = ((y + r) sigma(a) - y) / S in front of the unchanged dF_latent and dW products, zpart sums t, and usum [P] fp64
+ * receives the per-output sums of u over (s, n) - per-workgroup [P] partials next to the dW partials, reduced in a fixed
+ * order - which gpsa_elbo_loss_nb_bwd takes as usum[i].  Matrix-core kernel only (L <= 64, else GPSA_EUNSUPPORTED);
+ * workspace >= gpsa_lmc_loglik_nb_workspace (gpsa_lmc_loglik_workspace plus the new partials). */
+long long gpsa_lmc_loglik_nb_workspace(long long C, int L, int P, int nparts);
+int gpsa_lmc_loglik_fused_nb_f32(const float* F, const float* W, const float* Y, const float* log_offset,
+                                 const float* log_disp, int skip, int S, long long N, int L, int P, double* zpart,
+                                 int nparts, float* dF, float* dW, double* usum, void* workspace,
+                                 long long workspace_bytes, void* stream);
+long long gpsa_elbo_loss_nb_workspace(int n_ll, const int* S, const long long* N, const int* P, const int* n_views,
+                                      const int* kind);
+int gpsa_elbo_loss_nb_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                          const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                          const int* n_views, const long long* const* view_off, const double* const* w,
+                          const double* const* nobs, const int* kind, const double* const* lgam,
+                          const float* const* log_offset, const float* const* log_disp, const double* const* csum,
+                          int skip, const double* kl, int n_kl, double kl_scale, float* loss, double* ll_out,
+                          void* workspace, long long workspace_bytes, void* stream);
+int gpsa_elbo_loss_nb_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                          const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                          const int* n_views, const long long* const* view_off, const double* const* w,
+                          const double* const* nobs, const int* kind, const double* const* lgam,
+                          const float* const* log_offset, const float* const* log_disp, const double* const* dconst,
+                          const double* const* usum, int skip, const float* gloss, int n_kl, double kl_scale,
+                          float* const* dF, float* const* dnoise, float* dnoise_all, int n_noise, double* dkl,
+                          float* const* ddisp, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- prediction: closed-form moments of the data GP (csrc/predict.hip) ----------------------------------------------
  * The counterpart of gpsa_data_sample_fwd: from a chunk of c rows evaluated at S warp samples - meanT, v [L, S*c] fp32
  * (column s*c + r), q [S*c] fp64, var_u as there - it forms per sample the conditional of vgpsa.py:174-204,

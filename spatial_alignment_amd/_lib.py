@@ -238,9 +238,34 @@ SIGNATURES.update({
                                                _vp, _vp, _vp, _vp, _i, _vp, _ll, _vp]),
     "gpsa_lmc_loglik_fused_pois_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _ll, _i, _i, _vp, _i, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_step_likelihood": (_i, [_vp, _i, _i, _vp]),
+    # count outputs (model.likelihood): the negative binomial term, a dispersion per output
+    "gpsa_nb_const_workspace": (_ll, [_ll, _i, _i]),
+    "gpsa_nb_const": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), _pp, C.POINTER(_i), _pp, _pp, _i, _pp, _pp, _vp, _ll,
+                           _vp]),
+    "gpsa_quadform_elbo_nb_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _ll, _vp]),
+    "gpsa_quadform_elbo_delta_nb_f32": (_i, [_i, _vp, _vp, _i, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _ll, _vp]),
+    "gpsa_step_dispersion": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "gpsa_lmc_loglik_nb_workspace": (_ll, [_ll, _i, _i, _i]),
+    "gpsa_lmc_loglik_fused_nb_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _ll, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _ll,
+                                          _vp]),
+    "gpsa_elbo_loss_nb_workspace": (_ll, [_i, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i),
+                                          C.POINTER(_i)]),
+    "gpsa_elbo_loss_nb_fwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i), _pp, _i,
+                                   C.POINTER(_i), _pp, _pp, _pp, C.POINTER(_i), _pp, _pp, _pp, _pp, _i, _vp, _i, _d, _vp,
+                                   _vp, _vp, _ll, _vp]),
+    "gpsa_elbo_loss_nb_bwd": (_i, [_i, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_ll), C.POINTER(_i), _pp, _i,
+                                   C.POINTER(_i), _pp, _pp, _pp, C.POINTER(_i), _pp, _pp, _pp, _pp, _pp, _i, _vp, _i, _d,
+                                   _pp, _pp, _vp, _i, _vp, _pp, _vp, _ll, _vp]),
 })
 
-LIK_KINDS = {"gaussian": 0, "poisson": 1}  # GPSA_LIK_GAUSSIAN / GPSA_LIK_POISSON
+LIK_KINDS = {"gaussian": 0, "poisson": 1}  # GPSA_LIK_GAUSSIAN / GPSA_LIK_POISSON: the kinds gpsa_step_likelihood takes
+# (a negative binomial modality reaches the step engine through gpsa_step_dispersion)
+LIK_NEGBIN = 2  # GPSA_LIK_NEGBIN
+# every value of model.likelihood -> its GPSA_LIK_* kind (LIK_KINDS stays the two-entry table it was: what reads it, the
+# step engine's setter among them, knows no third kind)
+LIK_KIND_OF = dict(LIK_KINDS, negative_binomial=LIK_NEGBIN)
 
 _lib = None
 

@@ -80,6 +80,29 @@ int lmc_mfma_pois_launch(const float* F, const float* W, const float* Y, const f
                          long long N, int L, int P, double* zpart, int nparts, float* dF, float* dWpart, int G,
                          hipStream_t st);
 
+// lmc.hip: lmc_mfma_launch for a negative binomial modality (lmc_mfma_nb_kernel): upart [G][P] fp64, the workgroups'
+// per-output sums of u
+int lmc_mfma_nb_launch(const float* F, const float* W, const float* Y, const float* log_offset, const float* log_disp,
+                       int skip, int S, long long N, int L, int P, double* zpart, int nparts, float* dF, float* dWpart,
+                       double* upart, int G, hipStream_t st);
+
+// negbin.hip: the negative binomial term's per-element kernel (loglik_nb_kernel<bwd>) as a column reduction: threads
+// along p, the S * rows_v rows of view v in g.nrb row blocks, grid (g.gx, g.nrb, V).  forward: part[v * g.nb() + block]
+// = the block's sum of t; backward: dF = gloss w_v ((y + r) sigma(a) - y) / S and upart[(v * g.nrb + row block) * P + p]
+// = the row block's sum of u in column p.  nb_grid sizes both (at most 4096 block partials per term).
+struct NbGrid {
+  int gx, nrb, cw;  // column blocks, row blocks per view, columns per pass of a block (a power of two <= 64)
+  int nb() const { return gx * nrb; }
+};
+NbGrid nb_grid(long long rows, int V, int P);
+int nb_loglik_launch(bool bwd, const float* F, const float* Y, const float* log_offset, const float* log_disp, int S,
+                     long long N, int P, const ViewRows& vr, int V, const NbGrid& g, const double* w, const float* gloss,
+                     int skip, float* dF, double* part, double* upart, hipStream_t st);
+// ddisp[p] = -gloss ( sum_v w_v sum_b upart[(v nrb + b) P + p] / S + dconst[p] )  (w == nullptr: weights of 1; a term
+// that came as partial sums: V = nrb = 1, upart = its [P] sums of u)
+int nb_ddisp_launch(const double* upart, int V, int nrb, int P, const double* w, int S, const double* dconst,
+                    const float* gloss, float* ddisp, hipStream_t st);
+
 // proj64.hip: alpha = Kinv X (fp64 matrix cores) as a persistent output-stationary kernel over pack_whiten_kernel's
 // packed inverse(s); proj64_ok says which shapes it takes; q is closed by atomic adds onto
 // zero: q_zeroed says an earlier launch on the stream has cleared it (else a memset node goes in front)

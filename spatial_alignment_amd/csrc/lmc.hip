@@ -38,6 +38,8 @@ lmc_mfma_kernel(const float* __restrict__ F, const float* __restrict__ W, const 
   constexpr bool SKIP = false;
   constexpr int LIK = GPSA_LIK_GAUSSIAN;
   constexpr const float* log_offset = nullptr;  // (the Poisson kernel's argument)
+  constexpr const float* log_disp = nullptr;    // (the NB kernel's arguments)
+  constexpr double* upart = nullptr;
 #include "lmc_body.hpp"
 }
 template <int NLT, int NPT>
@@ -48,6 +50,8 @@ lmc_mfma_skip_kernel(const float* __restrict__ F, const float* __restrict__ W, c
   constexpr bool SKIP = true;
   constexpr int LIK = GPSA_LIK_GAUSSIAN;
   constexpr const float* log_offset = nullptr;  // (the Poisson kernel's argument)
+  constexpr const float* log_disp = nullptr;    // (the NB kernel's arguments)
+  constexpr double* upart = nullptr;
 #include "lmc_body.hpp"
 }
 
@@ -59,6 +63,22 @@ lmc_mfma_pois_kernel(const float* __restrict__ F, const float* __restrict__ W, c
                      const float* __restrict__ log_offset, int skip, int S, long long N, int L, int P,
                      double* __restrict__ zpart, int nparts, float* __restrict__ dF, float* __restrict__ dWpart) {
   constexpr int LIK = GPSA_LIK_POISSON;
+  constexpr const float* noise_u = nullptr;  // (not read)
+  const bool SKIP = skip != 0;
+  constexpr const float* log_disp = nullptr;  // (the NB kernel's arguments)
+  constexpr double* upart = nullptr;
+#include "lmc_body.hpp"
+}
+
+// LIK = GPSA_LIK_NEGBIN (lmc_mfma_nb_kernel; gpsa_lmc_loglik_fused_nb_f32): F W is the log mean of count outputs with a
+// dispersion per output (log_disp [P]); the closing also sums u per output into upart [G][P] (lmc_body.hpp)
+template <int NLT, int NPT>
+__global__ void __launch_bounds__(256, 2)
+lmc_mfma_nb_kernel(const float* __restrict__ F, const float* __restrict__ W, const float* __restrict__ Y,
+                   const float* __restrict__ log_offset, const float* __restrict__ log_disp, int skip, int S, long long N,
+                   int L, int P, double* __restrict__ zpart, int nparts, float* __restrict__ dF,
+                   float* __restrict__ dWpart, double* __restrict__ upart) {
+  constexpr int LIK = GPSA_LIK_NEGBIN;
   constexpr const float* noise_u = nullptr;  // (not read)
   const bool SKIP = skip != 0;
 #include "lmc_body.hpp"
@@ -124,6 +144,36 @@ static int lmc_mfma_pois_launch_t(const float* F, const float* W, const float* Y
                                                              dWpart);
   GPSA_LAUNCH_CHECK();
   return 0;
+}
+template <int NLT, int NPT>
+static int lmc_mfma_nb_launch_t(const float* F, const float* W, const float* Y, const float* log_offset,
+                                const float* log_disp, int skip, int S, long long N, int L, int P, double* zpart,
+                                int nparts, float* dF, float* dWpart, double* upart, int G, hipStream_t st) {
+  const int sm = (int)lmc_mfma_smem(NLT, NPT);
+  static per_device_flag attr_flag;
+  bool& attr_set = attr_flag.here();
+  if (!attr_set && sm > 65536) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lmc_mfma_nb_kernel<NLT, NPT>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, sm) != hipSuccess)
+      return GPSA_EUNSUPPORTED;
+    attr_set = true;
+  }
+  lmc_mfma_nb_kernel<NLT, NPT><<<G, 256, (size_t)sm, st>>>(F, W, Y, log_offset, log_disp, skip, S, N, L, P, zpart, nparts,
+                                                           dF, dWpart, upart);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+// ... for a negative binomial modality (gpsa_lmc_loglik_fused_nb_f32)
+int lmc_mfma_nb_launch(const float* F, const float* W, const float* Y, const float* log_offset, const float* log_disp,
+                       int skip, int S, long long N, int L, int P, double* zpart, int nparts, float* dF, float* dWpart,
+                       double* upart, int G, hipStream_t st) {
+  if (L <= 16)
+    return lmc_mfma_nb_launch_t<1, 4>(F, W, Y, log_offset, log_disp, skip, S, N, L, P, zpart, nparts, dF, dWpart, upart, G, st);
+  if (L <= 32)
+    return lmc_mfma_nb_launch_t<2, 2>(F, W, Y, log_offset, log_disp, skip, S, N, L, P, zpart, nparts, dF, dWpart, upart, G, st);
+  if (L <= 64)
+    return lmc_mfma_nb_launch_t<4, 1>(F, W, Y, log_offset, log_disp, skip, S, N, L, P, zpart, nparts, dF, dWpart, upart, G, st);
+  return GPSA_EUNSUPPORTED;
 }
 // ... for a Poisson modality (gpsa_lmc_loglik_fused_pois_f32)
 int lmc_mfma_pois_launch(const float* F, const float* W, const float* Y, const float* log_offset, int skip, int S,

@@ -8,6 +8,11 @@
 // and the two kernels differ by the one compare in the residual's select.
 // LIK == GPSA_LIK_POISSON: fo[r] is the log rate, eta = fo + log_offset[row] (a per-row load next to Yr),
 // dfo = (exp(eta) - y) / S with the exact expf, the summed term y eta - exp(eta); the dW and dF chains are unchanged.
+// LIK == GPSA_LIK_NEGBIN (lmc_mfma_nb_kernel; the other kernels define log_disp and upart as constexpr nullptrs): fo[r] is
+// the log mean, a = fo + log_offset[row] - rho_p with rho_p = log_disp[p] loaded once per chunk of outputs (the thread's
+// columns), dfo = ((y + r) sigma(a) - y) / S, the summed term t = y a - (y + r) softplus(a), and u = -r softplus(a) +
+// (y + r) sigma(a) - y summed per output in fp64 registers: a wave owns its outputs of the chunk, so the four row groups
+// of a lane column meet by two lane exchanges and upart[workgroup][p] is written once per chunk, next to dWpart.
   constexpr int LT = 16 * NLT, KB = 4 * NLT, PC = 64 * NPT, WS = PC + 4, FS = LT + 1;
   extern __shared__ __attribute__((aligned(16))) float lm_smem[];
   float* sW = lm_smem;                   // [LT][WS]   W[l][p0 + pp], zero padded
@@ -17,9 +22,9 @@
   __shared__ double red[4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, kq = lane >> 4;
-  const double sN = LIK == GPSA_LIK_POISSON ? 1.0 : exp((double)noise_u[0]) + 1e-5;  // "variance" used as std
+  const double sN = LIK != GPSA_LIK_GAUSSIAN ? 1.0 : exp((double)noise_u[0]) + 1e-5;  // "variance" used as std
   const float inv = (float)(1.0 / sN);
-  const float coef = LIK == GPSA_LIK_POISSON ? (float)(1.0 / (double)S) : (float)(-1.0 / (sN * sN * (double)S));
+  const float coef = LIK != GPSA_LIK_GAUSSIAN ? (float)(1.0 / (double)S) : (float)(-1.0 / (sN * sN * (double)S));
   const long long ntiles = (N + 15) / 16;
   double z2 = 0.0;
   float* sTw = sT + w * 16 * 17;
@@ -45,6 +50,16 @@
     bool pok[NPT];
 #pragma unroll
     for (int i = 0; i < NPT; ++i) pok[i] = p0 + pw + 16 * i + li < P;
+    float rh[NPT], rsz[NPT];  // (NB) rho and r = exp(rho) of this thread's outputs
+    double uacc[NPT];         // (NB) their sums of u over this workgroup's tiles
+    if constexpr (LIK == GPSA_LIK_NEGBIN) {
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        rh[i] = log_disp[pok[i] ? p0 + pw + 16 * i + li : P - 1];
+        rsz[i] = expf(rh[i]);
+        uacc[i] = 0.0;
+      }
+    }
 
     for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
       const long long n0 = t * 16;
@@ -55,7 +70,7 @@
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         rok[r] = n0 + 4 * kq + r < N;
-        if constexpr (LIK == GPSA_LIK_POISSON)
+        if constexpr (LIK != GPSA_LIK_GAUSSIAN)
           Or[r] = log_offset != nullptr ? log_offset[rok[r] ? n0 + 4 * kq + r : N - 1] : 0.f;
       }
 #pragma unroll
@@ -90,9 +105,21 @@
 #pragma unroll
           for (int ks = 0; ks < KB; ++ks) fo = __builtin_amdgcn_mfma_f32_16x16x4f32(aF[ks], Wf[i][ks], fo, 0, 0, 0);
           float dfo[4];
+          float ul = 0.f;  // (NB) this output's u over the four rows
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            if constexpr (LIK == GPSA_LIK_POISSON) {
+            if constexpr (LIK == GPSA_LIK_NEGBIN) {
+              const float a = fo[r] + Or[r] - rh[i];
+              const float e = expf(-fabsf(a));                    // in (0, 1]: nothing overflows
+              const float sp = fmaxf(a, 0.f) + log1pf(e);         // softplus(a)
+              const float sg = (a >= 0.f ? 1.f : e) / (1.f + e);  // sigma(a)
+              const float y = Yr[i][r], yr = y + rsz[i];
+              const bool obs = rok[r] && pok[i] && (!SKIP || y == y);
+              const float d = fmaf(yr, sg, -y);
+              z2l += obs ? fmaf(y, a, -yr * sp) : 0.f;
+              ul += obs ? fmaf(-rsz[i], sp, d) : 0.f;
+              dfo[r] = obs ? coef * d : 0.f;
+            } else if constexpr (LIK == GPSA_LIK_POISSON) {
               const float eta = fo[r] + Or[r];
               const float ex = expf(eta);
               const bool obs = rok[r] && pok[i] && (!SKIP || Yr[i][r] == Yr[i][r]);
@@ -105,6 +132,7 @@
               dfo[r] = coef * rr;
             }
           }
+          if constexpr (LIK == GPSA_LIK_NEGBIN) uacc[i] += (double)ul;
           // dW[l, p] += sum_c F[c, l] dfo[c, p]: K step r contracts the spots 4 kq + r
 #pragma unroll
           for (int r = 0; r < 4; ++r)
@@ -155,6 +183,17 @@
           const int l = 16 * lt + 4 * kq + r, p = p0 + pw + 16 * i + li;
           if (l < L && p < P) dWpart[((long long)blockIdx.x * L + l) * P + p] = dWacc[i][lt][r];
         }
+    if constexpr (LIK == GPSA_LIK_NEGBIN) {
+      // this workgroup's sums of u for the chunk: the row groups kq of a column in the fixed order (0 + 1) + (2 + 3)
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        double v = uacc[i];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        const int p = p0 + pw + 16 * i + li;
+        if (kq == 0 && p < P) upart[(long long)blockIdx.x * P + p] = v;
+      }
+    }
   }
   z2 = block_sum(z2, red);
   if (tid == 0) zpart[blockIdx.x] = z2;

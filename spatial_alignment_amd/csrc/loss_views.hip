@@ -8,6 +8,8 @@
 //   gpsa_elbo_loss_pois_fwd / _bwd       model.likelihood: the same tables plus a likelihood kind per term; a Poisson
 //                                        term (count outputs, poisson.hip) sums y eta - exp(eta) and has the lgamma table
 //                                        as its constant, a Gaussian term in the same call is closed as below
+//   gpsa_elbo_loss_nb_fwd / _bwd         the same plus negative binomial terms (negbin.hip): rho per output, the tables of
+//                                        gpsa_nb_const, and the gradient of rho from per-output sums
 // The first two pairs are argument checks around one views_fwd_impl / views_bwd_impl: the weighted pair passes no counts and no
 // fused terms.  The per-element kernels differ in their arithmetic and stay two (loglik_w_kernel counts per chunk and
 // sums z^2 - 1 in the backward; loglik_skip_kernel leaves the counts to the closing).
@@ -481,9 +483,275 @@ static int pois_bwd_impl(int n_ll, const float* const* F, const float* const* Y,
   return 0;
 }
 
+// ---- the closing with negative binomial terms (gpsa_elbo_loss_nb_fwd / _bwd; the per-element kernels are negbin.hip's) ---
+// Gaussian and Poisson terms in such a call go through the very launches of the Poisson closing above; an NB term's
+// partials sum t = y a - (y + r) softplus(a), its constants are gpsa_nb_const's table minus the lgamma table, and its
+// backward also closes the per-output sums of u into the gradient of rho (nb_ddisp_launch).
+struct NbFinishArgs {
+  PoisFinishArgs p;
+  const double* csum[GPSA_MAX_MODS];   // [V] sum of lgamma(y + r) - lgamma(r) per view (NB terms)
+};
+// elbo_pois_finish_kernel with  ll[i] = sum_v w_v (t_v / S_i + csum_v - lgam_v)  for an NB term
+__global__ void __launch_bounds__(256) elbo_nb_finish_kernel(NbFinishArgs n) {
+  __shared__ double red[4];
+  const ViewFinishArgs& a = n.p.g;
+  double lsum = 0.0;
+  for (int i = 0; i < a.n_ll; ++i) {
+    const int kind = n.p.kind[i];
+    if (kind != GPSA_LIK_GAUSSIAN) {
+      double tot = 0.0;
+      for (int v = 0; v < a.V[i]; ++v) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < a.nb[i]; b += blockDim.x) s += a.part[i][(long long)v * a.nb[i] + b];
+        s = block_sum(s, red);
+        if (threadIdx.x == 0) {
+          const double wv = a.w[i] != nullptr ? a.w[i][v] : 1.0;
+          if (kind == GPSA_LIK_NEGBIN)
+            tot += wv * (s / (double)a.S[i] + (n.csum[i][v] - n.p.lgam[i][v]));
+          else
+            tot += wv * (s / (double)a.S[i] - n.p.lgam[i][v]);
+        }
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) {
+        a.ll[i] = tot;
+        lsum += tot;
+      }
+      continue;
+    }
+    double B = 0.0;
+    if (a.nobs[i] != nullptr) {
+      const double sd = exp((double)a.noise_u[i][0]) + 1e-5;
+      B = -log(sd) - 0.9189385332046727;
+    }
+    const double s = view_total(a.part[i], a.V[i], a.nb[i], a.w[i], a.nobs[i], a.S[i], -0.5, B, red);
+    if (threadIdx.x == 0) {
+      const double v = s / (double)a.S[i];
+      a.ll[i] = v;
+      lsum += v;
+    }
+  }
+  double k = 0.0;
+  for (int t = threadIdx.x; t < a.n_kl; t += 256) k += a.kl[t];
+  k = block_sum(k, red);
+  if (threadIdx.x == 0) a.loss[0] = (float)(a.kl_scale * k - lsum);
+}
+
+// doubles of term i's [V][nrb][P] column partials of u, sized for views of up to N rows (the launch's nrb is no larger)
+static long long nb_upart_doubles(int S, long long N, int P, int V) {
+  return (long long)V * nb_grid((long long)S * N, V, P).nrb * P;
+}
+// (kind == nullptr: every term counted as negative binomial; otherwise only the NB terms have column partials)
+static long long nb_loss_workspace(int n_ll, const int* S, const long long* N, const int* P, const int* n_views,
+                                   const int* kind) {
+  long long d = LL_SLOT_DOUBLES * n_ll;
+  for (int i = 0; i < n_ll; ++i)
+    if (!kind || kind[i] == GPSA_LIK_NEGBIN) d += nb_upart_doubles(S[i], N[i], P[i], n_views ? n_views[i] : 1);
+  return 8 * d;
+}
+
+// the pair's tables, checked before any launch: pois_args_check's rules for the Gaussian and Poisson terms, and for an NB
+// term its lgamma table, rho and the table of gpsa_nb_const that the direction reads (csum / dconst)
+static int nb_args_check(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                         const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                         const int* n_views, const long long* const* view_off, const double* const* w,
+                         const double* const* nobs, const int* kind, const double* const* lgam,
+                         const float* const* log_disp, const double* const* nbc, int skip, long long workspace_bytes) {
+  if (!kind || !lgam || !log_disp || !nbc) return GPSA_EINVAL;
+  if ((n_views == nullptr) != (view_off == nullptr) || (w != nullptr && n_views == nullptr)) return GPSA_EINVAL;
+  if (int rc = elbo_loss_args_check(n_ll, F, Y, noise_u, S, N, P, workspace_bytes)) return rc;
+  for (int i = 0; i < n_ll; ++i) {
+    const bool fused = zpart && zpart[i];
+    if (fused && (nparts < 1 || (n_views && n_views[i] != 1))) return GPSA_EINVAL;
+    if (!fused && (!F[i] || !Y[i])) return GPSA_EINVAL;
+    if (n_views && !views_ok(n_views[i], view_off[i], N[i])) return GPSA_EINVAL;
+    if (kind[i] == GPSA_LIK_NEGBIN) {
+      if (!lgam[i] || !log_disp[i] || !nbc[i]) return GPSA_EINVAL;
+    } else if (kind[i] == GPSA_LIK_POISSON) {
+      if (!lgam[i]) return GPSA_EINVAL;
+    } else if (kind[i] == GPSA_LIK_GAUSSIAN) {
+      if (!noise_u[i]) return GPSA_EINVAL;
+      if (nobs && nobs[i]) {  // the skip closing's arithmetic
+        if (!fused && !skip) return GPSA_EINVAL;
+      } else {  // the weighted closing's
+        if (fused || skip || !n_views || !w || !w[i]) return GPSA_EINVAL;
+      }
+    } else {
+      return GPSA_EINVAL;
+    }
+  }
+  if (workspace_bytes < nb_loss_workspace(n_ll, S, N, P, n_views, kind)) return GPSA_EWORKSPACE;
+  return 0;
+}
+
+// an NB term's grid: the column reduction over its largest view's S * rows
+static NbGrid nb_term_grid(int S, const ViewRows& vr, int V, int P) {
+  long long most = 0;
+  for (int v = 0; v < V; ++v)
+    if (vr.off[v + 1] - vr.off[v] > most) most = vr.off[v + 1] - vr.off[v];
+  return nb_grid(most * S, V, P);
+}
+
+static int nb_fwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u, const int* S,
+                       const long long* N, const int* P, const double* const* zpart, int nparts, const int* n_views,
+                       const long long* const* view_off, const double* const* w, const double* const* nobs,
+                       const int* kind, const double* const* lgam, const float* const* log_offset,
+                       const float* const* log_disp, const double* const* csum, int skip, const double* kl, int n_kl,
+                       double kl_scale, float* loss, double* ll_out, void* workspace, void* stream) {
+  hipStream_t st = as_stream(stream);
+  NbFinishArgs n = {};
+  ViewFinishArgs& a = n.p.g;
+  a.n_ll = n_ll;
+  a.n_kl = kl ? n_kl : 0;
+  a.kl = kl;
+  a.kl_scale = kl_scale;
+  a.ll = ll_out;
+  a.loss = loss;
+  for (int i = 0; i < n_ll; ++i) {
+    const bool gauss = kind[i] == GPSA_LIK_GAUSSIAN;
+    n.p.kind[i] = kind[i];
+    n.p.lgam[i] = lgam[i];
+    n.csum[i] = csum[i];
+    a.w[i] = w ? w[i] : nullptr;
+    a.nobs[i] = (gauss && nobs) ? nobs[i] : nullptr;
+    a.noise_u[i] = noise_u[i];
+    a.S[i] = S[i];
+    if (zpart && zpart[i]) {
+      a.part[i] = zpart[i];
+      a.V[i] = 1;
+      a.nb[i] = nparts;
+      continue;
+    }
+    const PoisTerm t = pois_term(i, S, N, P, n_views, view_off, workspace);
+    const float* off = log_offset ? log_offset[i] : nullptr;
+    a.part[i] = t.slot;
+    a.V[i] = t.V;
+    a.nb[i] = t.nb;
+    if (kind[i] == GPSA_LIK_NEGBIN) {
+      const NbGrid g = nb_term_grid(S[i], t.vr, t.V, P[i]);
+      if (int rc = nb_loglik_launch(false, F[i], Y[i], off, log_disp[i], S[i], N[i], P[i], t.vr, t.V, g, a.w[i], nullptr,
+                                    skip, nullptr, t.slot, nullptr, st))
+        return rc;
+      a.nb[i] = g.nb();
+    } else if (kind[i] == GPSA_LIK_POISSON) {
+      if (int rc = pois_loglik_launch(false, F[i], Y[i], off, S[i], N[i], P[i], t.vr, t.V, t.nb, a.w[i], nullptr, skip,
+                                      nullptr, t.slot, st))
+        return rc;
+    } else {
+      const auto kernel = a.nobs[i] ? loglik_skip_kernel<false> : loglik_w_kernel<false>;
+      kernel<<<dim3(t.nb, t.V), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], t.vr, a.w[i], nullptr,
+                                              nullptr, t.slot);
+    }
+  }
+  elbo_nb_finish_kernel<<<1, 256, 0, st>>>(n);
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
+static int nb_bwd_impl(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u, const int* S,
+                       const long long* N, const int* P, const double* const* zpart, int nparts, const int* n_views,
+                       const long long* const* view_off, const double* const* w, const double* const* nobs,
+                       const int* kind, const float* const* log_offset, const float* const* log_disp,
+                       const double* const* dconst, const double* const* usum, int skip, const float* gloss, int n_kl,
+                       double kl_scale, float* const* dF, float* const* dnoise, float* dnoise_all, int n_noise,
+                       double* dkl, float* const* ddisp, void* workspace, void* stream) {
+  hipStream_t st = as_stream(stream);
+  double* up = reinterpret_cast<double*>(workspace) + LL_SLOT_DOUBLES * n_ll;  // the terms' column partials of u, in order
+  for (int i = 0; i < n_ll; ++i) {
+    const bool gauss = kind[i] == GPSA_LIK_GAUSSIAN;
+    const double* wi = w ? w[i] : nullptr;
+    const double* ni = (gauss && nobs) ? nobs[i] : nullptr;
+    const double* part = zpart ? zpart[i] : nullptr;
+    const float* off = log_offset ? log_offset[i] : nullptr;
+    double* upart = up;
+    if (kind[i] == GPSA_LIK_NEGBIN) up += nb_upart_doubles(S[i], N[i], P[i], n_views ? n_views[i] : 1);
+    int V = 1, nb = nparts;
+    if (part == nullptr) {
+      const PoisTerm t = pois_term(i, S, N, P, n_views, view_off, workspace);
+      V = t.V, nb = t.nb;
+      if (kind[i] == GPSA_LIK_NEGBIN) {
+        const NbGrid g = nb_term_grid(S[i], t.vr, V, P[i]);
+        if (int rc = nb_loglik_launch(true, F[i], Y[i], off, log_disp[i], S[i], N[i], P[i], t.vr, V, g, wi, gloss, skip,
+                                      dF[i], nullptr, upart, st))
+          return rc;
+        if (int rc = nb_ddisp_launch(upart, V, g.nrb, P[i], wi, S[i], dconst[i], gloss, ddisp[i], st)) return rc;
+      } else if (kind[i] == GPSA_LIK_POISSON) {
+        if (int rc = pois_loglik_launch(true, F[i], Y[i], off, S[i], N[i], P[i], t.vr, V, nb, wi, gloss, skip, dF[i],
+                                        t.slot, st))
+          return rc;
+      } else {
+        const auto kernel = ni ? loglik_skip_kernel<true> : loglik_w_kernel<true>;
+        kernel<<<dim3(nb, V), 256, 0, st>>>(F[i], Y[i], noise_u[i], S[i], N[i] * P[i], P[i], t.vr, wi, gloss, dF[i],
+                                            t.slot);
+      }
+      part = t.slot;
+    } else if (kind[i] == GPSA_LIK_NEGBIN) {
+      if (int rc = nb_ddisp_launch(usum[i], 1, 1, P[i], wi, S[i], dconst[i], gloss, ddisp[i], st)) return rc;
+    }
+    // the first term's finishing launch also zero-fills the noise gradient and writes dkl
+    if (!gauss)
+      pois_bwd_finish_kernel<<<1, 256, 0, st>>>(dnoise[i], gloss, i == 0 ? dkl : nullptr, n_kl, kl_scale,
+                                                i == 0 ? dnoise_all : nullptr, n_noise);
+    else
+      loglik_views_bwd_finish_kernel<<<1, 256, 0, st>>>(part, V, nb, wi, ni, noise_u[i], S[i], dnoise[i], gloss,
+                                                        i == 0 ? dkl : nullptr, n_kl, kl_scale,
+                                                        i == 0 ? dnoise_all : nullptr, n_noise);
+  }
+  GPSA_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace gpsa
 
 extern "C" {
+
+long long gpsa_elbo_loss_nb_workspace(int n_ll, const int* S, const long long* N, const int* P, const int* n_views,
+                                      const int* kind) {
+  using namespace gpsa;
+  if (n_ll < 1 || n_ll > GPSA_MAX_MODS || !S || !N || !P) return 0;
+  for (int i = 0; i < n_ll; ++i)
+    if (S[i] < 1 || N[i] < 1 || P[i] < 1 || (n_views && (n_views[i] < 1 || n_views[i] > LOSS_MAX_VIEWS))) return 0;
+  return nb_loss_workspace(n_ll, S, N, P, n_views, kind);
+}
+
+int gpsa_elbo_loss_nb_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                          const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                          const int* n_views, const long long* const* view_off, const double* const* w,
+                          const double* const* nobs, const int* kind, const double* const* lgam,
+                          const float* const* log_offset, const float* const* log_disp, const double* const* csum,
+                          int skip, const double* kl, int n_kl, double kl_scale, float* loss, double* ll_out,
+                          void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!loss || !ll_out || !workspace) return GPSA_EINVAL;
+  if (int rc = nb_args_check(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, lgam, log_disp,
+                             csum, skip, workspace_bytes))
+    return rc;
+  return nb_fwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, lgam, log_offset,
+                     log_disp, csum, skip, kl, n_kl, kl_scale, loss, ll_out, workspace, stream);
+}
+
+int gpsa_elbo_loss_nb_bwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
+                          const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,
+                          const int* n_views, const long long* const* view_off, const double* const* w,
+                          const double* const* nobs, const int* kind, const double* const* lgam,
+                          const float* const* log_offset, const float* const* log_disp, const double* const* dconst,
+                          const double* const* usum, int skip, const float* gloss, int n_kl, double kl_scale,
+                          float* const* dF, float* const* dnoise, float* dnoise_all, int n_noise, double* dkl,
+                          float* const* ddisp, void* workspace, long long workspace_bytes, void* stream) {
+  using namespace gpsa;
+  if (!gloss || !dF || !dnoise || !ddisp || !workspace) return GPSA_EINVAL;
+  if (int rc = nb_args_check(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, lgam, log_disp,
+                             dconst, skip, workspace_bytes))
+    return rc;
+  for (int i = 0; i < n_ll; ++i) {
+    const bool fused = zpart && zpart[i];
+    if (!dnoise[i] || (!fused && !dF[i])) return GPSA_EINVAL;
+    if (kind[i] == GPSA_LIK_NEGBIN && (!ddisp[i] || (fused && (!usum || !usum[i])))) return GPSA_EINVAL;
+  }
+  return nb_bwd_impl(n_ll, F, Y, noise_u, S, N, P, zpart, nparts, n_views, view_off, w, nobs, kind, log_offset, log_disp,
+                     dconst, usum, skip, gloss, n_kl, kl_scale, dF, dnoise, dnoise_all, n_noise, dkl, ddisp, workspace,
+                     stream);
+}
 
 int gpsa_elbo_loss_pois_fwd(int n_ll, const float* const* F, const float* const* Y, const float* const* noise_u,
                             const int* S, const long long* N, const int* P, const double* const* zpart, int nparts,

@@ -394,6 +394,21 @@ panel_elbo_pois_kernel(ElboArgs a, const float* __restrict__ log_offset, int ski
 GPSA_ELBO_SHAPES(GPSA_ELBO_POIS_EXTERN)
 extern template __global__ void panel_elbo_pois_kernel<13, 2, 2, true, true>(ElboArgs, const float*, int);
 extern template __global__ void panel_elbo_pois_kernel<13, 2, 4, true, true>(ElboArgs, const float*, int);
+// ... and with the negative binomial term (qf_elbo_nb.hip; gpsa_quadform_elbo_nb_f32): log_disp [L], u_elems [L, C] receives
+// u per element; ``part`` then sums t = y a - (y + r) softplus(a)
+template <int MB, int NCT, int RL, bool FULLT = false, bool PAIRB = false>
+__global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT))
+panel_elbo_nb_kernel(ElboArgs a, const float* __restrict__ log_offset, int skip, const float* __restrict__ log_disp,
+                     float* __restrict__ u_elems);
+#define GPSA_ELBO_NB_EXTERN(MB, NCT)                                                                                    \
+  extern template __global__ void panel_elbo_nb_kernel<MB, NCT, 2>(ElboArgs, const float*, int, const float*, float*); \
+  extern template __global__ void panel_elbo_nb_kernel<MB, NCT, 4>(ElboArgs, const float*, int, const float*, float*);
+#define GPSA_ELBO_NB_DEFINE(MB, NCT)                                                                             \
+  template __global__ void panel_elbo_nb_kernel<MB, NCT, 2>(ElboArgs, const float*, int, const float*, float*); \
+  template __global__ void panel_elbo_nb_kernel<MB, NCT, 4>(ElboArgs, const float*, int, const float*, float*);
+GPSA_ELBO_SHAPES(GPSA_ELBO_NB_EXTERN)
+extern template __global__ void panel_elbo_nb_kernel<13, 2, 2, true, true>(ElboArgs, const float*, int, const float*, float*);
+extern template __global__ void panel_elbo_nb_kernel<13, 2, 4, true, true>(ElboArgs, const float*, int, const float*, float*);
 
 // the same pass with the contraction on the bf16 matrix instructions in three pieces (qf_x3.hip; gpsa_step_desc.contraction
 // = 1): Ppk is then pack_x3_kernel's three-plane bf16 image of Omega

@@ -9,6 +9,8 @@ __global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT)) panel_elbo_kern
   constexpr bool SKIP = false;
   constexpr int LIK = GPSA_LIK_GAUSSIAN;
   constexpr const float* log_offset = nullptr;  // (the Poisson kernel's argument)
+  constexpr const float* log_disp = nullptr;    // (the NB kernel's arguments)
+  constexpr float* u_elems = nullptr;
 #include "qf_elbo_body.hpp"
 }
 

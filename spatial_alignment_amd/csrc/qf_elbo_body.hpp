@@ -34,6 +34,13 @@
 // expf: one per (l, column)); everything from g on is shared.  The offset is per COLUMN, not per output: it is loaded
 // with resid / okc, once per column tile - not in the closing (a compiler-visible load there waits for vmcnt(0)) and not
 // as a fourth gather kind.  SKIP is a kernel argument there, not a constant.
+// LIK == GPSA_LIK_NEGBIN (panel_elbo_nb_kernel; the other kernels define log_disp and u_elems as constexpr nullptrs): the
+// draw is a log mean, a = F + log_offset[n] - rho_l with rho_l = log_disp[l] - per OUTPUT and wave-uniform, so one scalar
+// load at the top of the output's chunks (scalar loads count on lgkmcnt, which the chunk loop drains anyway; the vector
+// loads' vmcnt, which covers the ring stages in flight, is not touched).  dLoss/dF = ((y + r) sigma(a) - y) / S, the summed
+// term t = y a - (y + r) softplus(a); u = -r softplus(a) + (y + r) sigma(a) - y goes to u_elems [L, C] at the index of g
+// and dmeanT (exact 0 for a missing entry): a workgroup walks tiles with the outputs as the inner loop, so part[] cannot
+// carry a per-output sum - a row reduction over C (the entry's) gives the [L] table.
   constexpr int MP = MB * 16;
   constexpr int WGCOLS = 64 * NCT;
   constexpr int CHUNK = MP * 16;
@@ -114,10 +121,10 @@
   static_assert(NPW <= 4, "a wave's pieces of a stage must lie within the 4 KiB an immediate offset reaches");
 
   // likelihood constants (elementwise.hip: loglik_*_kernel)
-  const double sN = LIK == GPSA_LIK_POISSON ? 1.0 : exp((double)a.noise_u[0]) + 1e-5;
+  const double sN = LIK != GPSA_LIK_GAUSSIAN ? 1.0 : exp((double)a.noise_u[0]) + 1e-5;
   const float inv = (float)(1.0 / sN);
   // dLoss/dF = coef (Y - F) at upstream gradient 1;  Poisson: coef (exp(eta) - Y)
-  const float coef = LIK == GPSA_LIK_POISSON ? (float)(1.0 / (double)a.S) : (float)(-1.0 / (sN * sN * (double)a.S));
+  const float coef = LIK != GPSA_LIK_GAUSSIAN ? (float)(1.0 / (double)a.S) : (float)(-1.0 / (sN * sN * (double)a.S));
   const double var0 = exp((double)a.var_u[0]);
   double z2 = 0.0;
 
@@ -154,7 +161,7 @@
       // sigma^2 - q formed in fp64 before rounding (data_sample_fwd_kernel)
       const double qc = a.q[okc[ct] ? c : C - 1];
       resid[ct] = okc[ct] ? (float)(var0 - qc) : 1.f;
-      if constexpr (LIK == GPSA_LIK_POISSON)
+      if constexpr (LIK != GPSA_LIK_GAUSSIAN)
         offc[ct] = log_offset != nullptr ? log_offset[(okc[ct] ? c : C - 1) % a.N] : 0.f;
     }
     // gather addresses of this lane for output l_lo: operation o moves element (o*64 + lane) of the wave's
@@ -184,6 +191,8 @@
       }
 
     for (int l = l_lo; l <= l_hi; ++l) {
+      float rho_l = 0.f;  // (NB) this output's log dispersion: wave-uniform, a scalar load
+      if constexpr (LIK == GPSA_LIK_NEGBIN) rho_l = log_disp[l];
 #pragma unroll
       for (int kc = 0; kc < MB; ++kc) {
         float bv[NCT][4];
@@ -280,8 +289,20 @@
         const float sd = sqrtf(var);
         const float Fd = mean + sd * e;  // the draw (data_sample_fwd_kernel's expression)
         // SKIP: a NaN observation is a missing one - residual exactly 0, so dF, g, z and its share of abar are too
-        float rres = 0.f, dF, pterm = 0.f;
-        if constexpr (LIK == GPSA_LIK_POISSON) {
+        float rres = 0.f, dF, pterm = 0.f, uval = 0.f;
+        if constexpr (LIK == GPSA_LIK_NEGBIN) {
+          const float aa = Fd + offc[ct] - rho_l;
+          const float rsz = expf(rho_l);
+          const float ee = expf(-fabsf(aa));                      // in (0, 1]: nothing overflows
+          const float sp = fmaxf(aa, 0.f) + log1pf(ee);           // softplus(a)
+          const float sg = (aa >= 0.f ? 1.f : ee) / (1.f + ee);   // sigma(a)
+          const float yr = y + rsz;
+          const bool obs = !SKIP || y == y;
+          const float dd = fmaf(yr, sg, -y);
+          dF = obs ? coef * dd : 0.f;
+          pterm = obs ? fmaf(y, aa, -yr * sp) : 0.f;
+          uval = obs ? fmaf(-rsz, sp, dd) : 0.f;
+        } else if constexpr (LIK == GPSA_LIK_POISSON) {
           const float eta = Fd + offc[ct];
           const float ex = expf(eta);
           const bool obs = !SKIP || y == y;
@@ -297,7 +318,8 @@
           a.g[o] = gv;
           a.dmeanT[o] = dF;
           if (a.FT != nullptr) a.FT[o] = Fd;  // (uniform)
-          if constexpr (LIK == GPSA_LIK_POISSON) {
+          if constexpr (LIK == GPSA_LIK_NEGBIN) u_elems[o] = uval;
+          if constexpr (LIK != GPSA_LIK_GAUSSIAN) {
             z2l += pterm;
           } else {
             const float z = rres * inv;

@@ -11,6 +11,8 @@ __global__ void __launch_bounds__(256, elbo_wgs_per_cu(MB, NCT))
 panel_elbo_pois_kernel(ElboArgs a, const float* __restrict__ log_offset, int skip) {
   constexpr int LIK = GPSA_LIK_POISSON;
   const bool SKIP = skip != 0;
+  constexpr const float* log_disp = nullptr;  // (the NB kernel's arguments)
+  constexpr float* u_elems = nullptr;
 #include "qf_elbo_body.hpp"
 }
 

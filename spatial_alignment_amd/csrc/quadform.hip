@@ -754,15 +754,35 @@ static inline int gram_nl(int MB, int L, long long C) {
   return (can && C >= 8192) ? 2 : 1;
 }
 
+// out[l] = sum_c x[l, c] in fp64: thread t takes columns t, t + 256, ..., then the block's fixed-order sum; grid L
+__global__ void __launch_bounds__(256) row_sum_f64_kernel(const float* __restrict__ x, long long C, double* __restrict__ out) {
+  __shared__ double red[4];
+  const float* row = x + (long long)blockIdx.x * C;
+  double s = 0.0;
+  for (long long c = threadIdx.x; c < C; c += 256) s += (double)row[c];
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
 // panel_elbo_kernel (skip: panel_elbo_skip_kernel, the NaN entries of Y left out; lik == GPSA_LIK_POISSON:
 // panel_elbo_pois_kernel, which takes the offsets and the skip flag as arguments) for one shape of GPSA_ELBO_SHAPES
 template <int MB, int NCT>
-static void elbo_shape(const ElboArgs& a, unsigned grid, hipStream_t st, bool skip, int lik, const float* log_offset) {
+static void elbo_shape(const ElboArgs& a, unsigned grid, hipStream_t st, bool skip, int lik, const float* log_offset,
+                       const float* log_disp, float* u_elems) {
   // the 13-tile shape with every row tile but the last inside the matrix (the headline configuration): the
   // instantiation without row clamps and with one barrier per two K chunks
   constexpr bool HEAD = MB == 13 && NCT == 2;
   const bool rl2 = last_tile_rl(a.M, MB) == 2;
-  if (lik == GPSA_LIK_POISSON) {
+  if (lik == GPSA_LIK_NEGBIN) {  // panel_elbo_nb_kernel: also rho per output and the per-element u
+    const int sk = skip ? 1 : 0;
+    if (HEAD && a.M > 16 * (MB - 1)) {
+      if (rl2) panel_elbo_nb_kernel<MB, NCT, 2, HEAD, HEAD><<<grid, 256, 0, st>>>(a, log_offset, sk, log_disp, u_elems);
+      else panel_elbo_nb_kernel<MB, NCT, 4, HEAD, HEAD><<<grid, 256, 0, st>>>(a, log_offset, sk, log_disp, u_elems);
+    } else {
+      if (rl2) panel_elbo_nb_kernel<MB, NCT, 2><<<grid, 256, 0, st>>>(a, log_offset, sk, log_disp, u_elems);
+      else panel_elbo_nb_kernel<MB, NCT, 4><<<grid, 256, 0, st>>>(a, log_offset, sk, log_disp, u_elems);
+    }
+  } else if (lik == GPSA_LIK_POISSON) {
     const int sk = skip ? 1 : 0;
     if (HEAD && a.M > 16 * (MB - 1)) {
       if (rl2) panel_elbo_pois_kernel<MB, NCT, 2, HEAD, HEAD><<<grid, 256, 0, st>>>(a, log_offset, sk);
@@ -1229,12 +1249,14 @@ static int elbo_launch(bool x3, bool skip, int omega_dtype, const float* alpha, 
                        const float* meanT, const float* delta, const double* q, const float* var_u, const float* eps,
                        const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar,
                        double* part, float* FT, void* workspace, long long workspace_bytes, void* stream,
-                       int lik = GPSA_LIK_GAUSSIAN, const float* log_offset = nullptr) {
+                       int lik = GPSA_LIK_GAUSSIAN, const float* log_offset = nullptr, const float* log_disp = nullptr,
+                       float* u_elems = nullptr, double* usum = nullptr) {
   using namespace gpsa;
   if (M < 1 || C < 1 || L < 1 || N < 1 || S < 1 || !alpha || !Omega || (!meanT && !delta) || !q || !var_u || !eps || !Y ||
-      (!noise_u && lik != GPSA_LIK_POISSON) || !g || !dmeanT || !abar || !part)
+      (!noise_u && lik == GPSA_LIK_GAUSSIAN) || !g || !dmeanT || !abar || !part)
     return GPSA_EINVAL;
-  if (lik == GPSA_LIK_POISSON && x3) return GPSA_EINVAL;
+  if (lik == GPSA_LIK_NEGBIN && (!log_disp || !u_elems || !usum)) return GPSA_EINVAL;
+  if (lik != GPSA_LIK_GAUSSIAN && x3) return GPSA_EINVAL;
   if (x3 && omega_dtype != GPSA_F32 && omega_dtype != GPSA_F64) return GPSA_EINVAL;
   if (delta != nullptr && !elbo_delta_ok(M)) return GPSA_EUNSUPPORTED;
   if (!elbo_path(M) || C > GPSA_PANEL_MAX_C) return GPSA_EUNSUPPORTED;
@@ -1261,7 +1283,7 @@ static int elbo_launch(bool x3, bool skip, int omega_dtype, const float* alpha, 
   const long long ntiles = cdiv(C, 64 * nct);
   const long long grid = persistent_grid(x3 ? 1 : elbo_wgs_per_cu(MB, nct), ntiles * L);
 #define GPSA_ELBO_CASE(MBV, NCTV) \
-  case MBV: elbo_shape<MBV, NCTV>(a, (unsigned)grid, st, skip, lik, log_offset); break;
+  case MBV: elbo_shape<MBV, NCTV>(a, (unsigned)grid, st, skip, lik, log_offset, log_disp, u_elems); break;
 #define GPSA_ELBO_X3_CASE(MBV, NCTV) \
   case MBV: panel_elbo_x3_kernel<MBV, NCTV><<<(unsigned)grid, 256, 0, st>>>(a); break;
   if (x3) {
@@ -1278,6 +1300,10 @@ static int elbo_launch(bool x3, bool skip, int omega_dtype, const float* alpha, 
 #undef GPSA_ELBO_CASE
 #undef GPSA_ELBO_X3_CASE
   GPSA_LAUNCH_CHECK();
+  if (lik == GPSA_LIK_NEGBIN) {  // the per-output sums of u: one block per output, fp64, a fixed order
+    row_sum_f64_kernel<<<(unsigned)L, 256, 0, st>>>(u_elems, C, usum);
+    GPSA_LAUNCH_CHECK();
+  }
   return slab_reduce_launch(slab, M, MB, nct, C, L, ntiles, grid, abar, st);
 }
 
@@ -1337,6 +1363,29 @@ int gpsa_quadform_elbo_delta_pois_f32(int omega_dtype, const float* alpha, const
   if (!delta) return GPSA_EINVAL;
   return elbo_launch(false, skip != 0, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u,
                      g, dmeanT, abar, part, FT, workspace, workspace_bytes, stream, GPSA_LIK_POISSON, log_offset);
+}
+
+int gpsa_quadform_elbo_nb_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                              const float* meanT, const double* q, const float* var_u, const float* eps, const float* Y,
+                              long long N, int S, const float* noise_u, float* g, float* dmeanT, float* abar, double* part,
+                              float* FT, const float* log_offset, const float* log_disp, float* u_elems, double* usum,
+                              int skip, void* workspace, long long workspace_bytes, void* stream) {
+  if (!meanT) return GPSA_EINVAL;
+  return elbo_launch(false, skip != 0, omega_dtype, alpha, Omega, M, C, L, meanT, nullptr, q, var_u, eps, Y, N, S, noise_u,
+                     g, dmeanT, abar, part, FT, workspace, workspace_bytes, stream, GPSA_LIK_NEGBIN, log_offset, log_disp,
+                     u_elems, usum);
+}
+
+int gpsa_quadform_elbo_delta_nb_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,
+                                    const float* delta, const double* q, const float* var_u, const float* eps,
+                                    const float* Y, long long N, int S, const float* noise_u, float* g, float* dmeanT,
+                                    float* abar, double* part, float* FT, const float* log_offset, const float* log_disp,
+                                    float* u_elems, double* usum, int skip, void* workspace, long long workspace_bytes,
+                                    void* stream) {
+  if (!delta) return GPSA_EINVAL;
+  return elbo_launch(false, skip != 0, omega_dtype, alpha, Omega, M, C, L, nullptr, delta, q, var_u, eps, Y, N, S, noise_u,
+                     g, dmeanT, abar, part, FT, workspace, workspace_bytes, stream, GPSA_LIK_NEGBIN, log_offset, log_disp,
+                     u_elems, usum);
 }
 
 int gpsa_quadform_elbo_x3_f32(int omega_dtype, const float* alpha, const void* Omega, int M, long long C, int L,

@@ -605,6 +605,10 @@ struct Plan {
   // gpsa_step_likelihood: the likelihood of modality m's fused ELBO pass and, for a Poisson one, its rows' log offsets
   int lik[GPSA_MAX_MODS] = {};
   const float* log_offset[GPSA_MAX_MODS] = {};
+  // gpsa_step_dispersion: a negative binomial modality's rho [L], its per-element u [L, C] and their per-output sums [L]
+  const float* log_disp[GPSA_MAX_MODS] = {};
+  float* u_elems[GPSA_MAX_MODS] = {};
+  double* usum[GPSA_MAX_MODS] = {};
   int tslots = 0, tfwd = 0, tbwd = 0;
   void tick(int kernel, int edge, bool fwd, hipStream_t st) {
     if (tslots == 0) return;
@@ -1358,8 +1362,11 @@ static int data_pass_fwd(Ctx& c, const Pass& ps) {
     // (gpsa_step_contraction then reports the pass as fp32); such a plan's scratch holds the larger of the two workspaces
     // P.lik[m] == GPSA_LIK_POISSON (gpsa_step_likelihood): the fp32 Poisson kernels (panel_elbo_pois_kernel), with the same
     // rule for a bf16x3 plan
-    const bool pois = P.lik[m] == GPSA_LIK_POISSON;
-    const bool skip = c.io.skip_missing != 0, x3 = ps.x3 && !skip && !pois;
+    // P.lik[m] == GPSA_LIK_NEGBIN (gpsa_step_dispersion): the fp32 NB kernels (panel_elbo_nb_kernel), the same rule again;
+    // the kind without its tensors is refused here, before any launch of the pass
+    const bool pois = P.lik[m] == GPSA_LIK_POISSON, nb = P.lik[m] == GPSA_LIK_NEGBIN;
+    if (nb && (P.log_disp[m] == nullptr || P.u_elems[m] == nullptr || P.usum[m] == nullptr)) return GPSA_EINVAL;
+    const bool skip = c.io.skip_missing != 0, x3 = ps.x3 && !skip && !pois && !nb;
     const long long ws32 = gpsa_quadform_elbo_f32_workspace(Mg, C, L);
     const long long wsx3 = ps.x3 ? gpsa_quadform_elbo_x3_f32_workspace(Mg, C, L) : 0;
     const long long wsb = x3 ? wsx3 : ws32;
@@ -1367,7 +1374,17 @@ static int data_pass_fwd(Ctx& c, const Pass& ps) {
     const bool timed = !dry && !c.quiet && &ps == &P.passes[0];
     if (timed) P.tick(0, 0, true, c.st);
     if (!dry) P.skip_seen = skip;
-    if (pois && mean_in_product)
+    if (nb && mean_in_product)
+      GPSA_RUN(gpsa_quadform_elbo_delta_nb_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
+                                               c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
+                                               c.io.ll_part[m], c.io.F_fused_T[m], P.log_offset[m], P.log_disp[m],
+                                               P.u_elems[m], P.usum[m], skip ? 1 : 0, ws, wsb, c.stv()));
+    else if (nb)
+      GPSA_RUN(gpsa_quadform_elbo_nb_f32(GPSA_F64, alpha, Om, Mg, C, L, meanT, q, c.prm.data_var, eps, c.io.Y[m],
+                                         (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar, c.io.ll_part[m],
+                                         c.io.F_fused_T[m], P.log_offset[m], P.log_disp[m], P.u_elems[m], P.usum[m],
+                                         skip ? 1 : 0, ws, wsb, c.stv()));
+    else if (pois && mean_in_product)
       GPSA_RUN(gpsa_quadform_elbo_delta_pois_f32(GPSA_F64, alpha, Om, Mg, C, L, c.prm.delta_F[m], q, c.prm.data_var, eps,
                                                  c.io.Y[m], (long long)(C / P.S), P.S, c.io.noise_u[m], g_ext, dmeanT, abar,
                                                  c.io.ll_part[m], c.io.F_fused_T[m], P.log_offset[m], skip ? 1 : 0, ws,
@@ -2367,7 +2384,7 @@ int gpsa_step_contraction(const void* plan, int m) {
   for (const gpsa::Pass& q : reinterpret_cast<const gpsa::Plan*>(plan)->passes)
     if (q.m == m && !q.test) {  // (skip_seen: the plan's last fused pass took the fp32 skip kernel, gpsa_step_io.skip_missing;
       const gpsa::Plan* p = reinterpret_cast<const gpsa::Plan*>(plan);  //  a Poisson modality's takes the fp32 Poisson kernel)
-      return ((q.o_fuse >= 0 && q.x3 && !p->skip_seen && p->lik[m] != GPSA_LIK_POISSON) ? 1 : 0) | (q.gx3 ? 2 : 0);
+      return ((q.o_fuse >= 0 && q.x3 && !p->skip_seen && p->lik[m] == GPSA_LIK_GAUSSIAN) ? 1 : 0) | (q.gx3 ? 2 : 0);
     }
   return 0;
 }
@@ -2378,6 +2395,20 @@ int gpsa_step_likelihood(void* plan, int m, int kind, const float* log_offset) {
   if (kind == GPSA_LIK_GAUSSIAN && log_offset != nullptr) return GPSA_EINVAL;
   p->lik[m] = kind;
   p->log_offset[m] = log_offset;
+  p->log_disp[m] = nullptr;  // (a modality that was negative binomial is so no longer)
+  p->u_elems[m] = nullptr;
+  p->usum[m] = nullptr;
+  return 0;
+}
+int gpsa_step_dispersion(void* plan, int m, const float* log_disp, float* u_elems, double* usum, const float* log_offset) {
+  if (!plan) return GPSA_EINVAL;
+  gpsa::Plan* p = reinterpret_cast<gpsa::Plan*>(plan);
+  if (m < 0 || m >= p->nm || !log_disp || !u_elems || !usum) return GPSA_EINVAL;
+  p->lik[m] = GPSA_LIK_NEGBIN;
+  p->log_offset[m] = log_offset;
+  p->log_disp[m] = log_disp;
+  p->u_elems[m] = u_elems;
+  p->usum[m] = usum;
   return 0;
 }
 long long gpsa_step_bwd_acc_bytes(const void* plan) { return plan ? reinterpret_cast<const gpsa::Plan*>(plan)->bwd_acc_bytes : -1; }

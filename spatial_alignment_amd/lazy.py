@@ -230,6 +230,19 @@ def run_fused(rec, idx, Ys, parts):
         offs = rec.get("log_offset") or [None] * len(plan.mods)
         for i in idx:
             kind = int(lik[i]) if lik is not None else 0
+            if kind == _lib.LIK_NEGBIN:
+                # a negative binomial modality: the plan is told its rho, where the pass writes u per element and where
+                # their per-output sums go (rec keeps all three alive; the loss node reads the sums in its backward)
+                S_, N_, L_ = (int(d) for d in rec["shapes"][i])
+                rho = rec["log_disp"][i]
+                u = torch.empty(L_, S_ * N_, dtype=torch.float32, device=rho.device)
+                us = torch.empty(L_, dtype=torch.float64, device=rho.device)
+                rec.setdefault("nb_u", {})[i] = u
+                rec.setdefault("nb_usum", {})[i] = us
+                o = offs[i]
+                _lib.check(plan.lib.gpsa_step_dispersion(plan.handle, int(i), rho.data_ptr(), u.data_ptr(), us.data_ptr(),
+                                                         None if o is None else o.data_ptr()), "gpsa_step_dispersion")
+                continue
             o = offs[i] if kind == 1 else None
             _lib.check(plan.lib.gpsa_step_likelihood(plan.handle, int(i), kind, None if o is None else o.data_ptr()),
                        "gpsa_step_likelihood")

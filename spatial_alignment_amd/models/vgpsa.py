@@ -16,6 +16,7 @@ import os
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from .. import engine as E
 from .. import step_engine as SE
 from ..lazy import LazyDraws, LazyProduct
@@ -157,7 +158,15 @@ class VariationalGPSA(GPSA):
         # sum (y eta - exp(eta)) / S - sum lgamma(y + 1) with eta = F_obs + data_dict[m]["log_offset"][n] (optional per-row
         # log size factors) on every loss path through its Poisson kernels (gpsa_elbo_loss_pois_fwd / _bwd,
         # gpsa_quadform_elbo_pois_f32, gpsa_lmc_loglik_fused_pois_f32); its noise_variance entry does not enter (gradient 0).
+        # "negative_binomial": the negative binomial with a trainable dispersion per output - the draws are log means, and
+        # model.log_dispersion[m] (an nn.Parameter of P_m zeros, rho: size r_p = exp(rho_p), so r = 1 at the start) exists
+        # for exactly the NB modalities: setting the likelihood creates it, setting the modality back removes it.  Set the
+        # likelihood BEFORE building the optimizer, which would otherwise not see the parameter.  Its loss runs through
+        # gpsa_nb_const and gpsa_elbo_loss_nb_fwd / _bwd on every loss path: the fused ELBO pass (gpsa_quadform_elbo_nb_f32,
+        # told to the step engine by gpsa_step_dispersion), the fused LMC pass (gpsa_lmc_loglik_fused_nb_f32), materialised
+        # draws.
         # With every modality Gaussian nothing of this runs.
+        self.log_dispersion = nn.ParameterDict()
         self.likelihood = "gaussian"
         self._noise = None  # injected Gaussian noise (tests / reproducibility), see inject_noise()
         self._cache = None
@@ -245,7 +254,7 @@ class VariationalGPSA(GPSA):
 
     @likelihood.setter
     def likelihood(self, value):
-        kinds = ("gaussian", "poisson")
+        kinds = tuple(_lib.LIK_KIND_OF)
         if isinstance(value, str):
             if value not in kinds:
                 raise ValueError(f"likelihood must be one of {kinds} or a dict {{modality: kind}}, got {value!r}")
@@ -259,9 +268,19 @@ class VariationalGPSA(GPSA):
         else:
             raise ValueError(f"likelihood must be one of {kinds} or a dict {{modality: kind}}, got {value!r}")
         self.__dict__["_likelihood"] = value
+        # the NB modalities' rho: created at zero (r = 1) where the modality became NB, kept where it stays NB, removed
+        # where it is NB no longer - parameters() / state_dict() carry it for the NB modalities only
+        for m in self.modality_names:
+            if self.likelihood_of(m) == "negative_binomial":
+                if m not in self.log_dispersion:
+                    like = self.noise_variance
+                    rho = torch.zeros(int(self.Ps[m]), dtype=like.dtype, device=like.device)
+                    self.log_dispersion[m] = nn.Parameter(rho)
+            elif m in self.log_dispersion:
+                del self.log_dispersion[m]
 
     def likelihood_of(self, m):
-        """the likelihood of modality ``m``: ``"gaussian"`` or ``"poisson"``"""
+        """the likelihood of modality ``m``: ``"gaussian"``, ``"poisson"`` or ``"negative_binomial"``"""
         lik = self.likelihood
         return lik if isinstance(lik, str) else lik.get(m, "gaussian")
 
@@ -270,10 +289,11 @@ class VariationalGPSA(GPSA):
         lik = self.likelihood
         if lik == "gaussian" or (isinstance(lik, dict) and all(k == "gaussian" for k in lik.values())):
             return None
-        return [1 if self.likelihood_of(m) == "poisson" else 0 for m in self.modality_names]
+        return [_lib.LIK_KIND_OF[self.likelihood_of(m)] for m in self.modality_names]
 
     def _close_pois(self, aux, weighted, skip):
-        """the tables of a loss with Poisson terms (aux["kinds"]): every term gets views (the weighted loss's, else one view
+        """the tables of a loss with Poisson or negative binomial terms (aux["kinds"]; an NB term takes the lgamma table
+        too, its constants that depend on rho are the loss node's: gpsa_nb_const): every term gets views (the weighted loss's, else one view
         of weight 1: a Gaussian term from its draws is then closed by the weighted closing's arithmetic), the Poisson
         terms their lgamma constants (cached like the observed counts: for the caller's own tensors only, recomputed on
         a minibatch's gathered rows), the Gaussian terms their counts - the observed entries under ``skip``, N P for a
@@ -301,7 +321,7 @@ class VariationalGPSA(GPSA):
                         view_off=[x for i in idx for x in aux["view_off"][starts[i]:starts[i] + aux["n_views"][i] + 1]])
 
         cacheable = weighted is None and own
-        pidx = [i for i in range(n) if kinds[i] == 1]
+        pidx = [i for i in range(n) if kinds[i] != 0]  # (Poisson and NB terms: lgamma(y + 1) is in both densities)
         lg = SE.lgamma_sums(self, [Yc[i] for i in pidx], sub(pidx), skip, cacheable)
         aux["lgam"] = [None] * n
         for i, t in zip(pidx, lg):
@@ -336,7 +356,16 @@ class VariationalGPSA(GPSA):
             Yc = aux["Y"] = [SE._f32c(y) for y in Ysrc]
             own = all(c is y for c, y in zip(Yc, Ysrc))  # (a copy made here dies with the step: its address says nothing)
             aux["nobs"] = SE.observed_counts(self, Yc, weighted, cacheable=weighted is None and own)
-        return SE.ElboLossFn.apply(aux, self.noise_variance, kl, *Fs, *Ws).to(self.Xtilde.dtype)
+        Ds = ()
+        if aux.get("kinds") is not None and 2 in aux["kinds"]:  # the NB terms' rho: trailing inputs, found through aux
+            nbi = [i for i, k in enumerate(aux["kinds"]) if k == 2]
+            aux["disp"] = {i: j for j, i in enumerate(nbi)}
+            Ds = [self.log_dispersion[self.modality_names[i]] for i in nbi]
+            for i, rho in zip(nbi, Ds):
+                if rho.numel() != int(aux["Y"][i].shape[1]):
+                    raise ValueError(f"loss_fn: log_dispersion[{self.modality_names[i]!r}] has {rho.numel()} entries, the "
+                                     f"modality's outputs have {int(aux['Y'][i].shape[1])} columns")
+        return SE.ElboLossFn.apply(aux, self.noise_variance, kl, *Fs, *Ws, *Ds).to(self.Xtilde.dtype)
 
     def _is_fixed(self, v):
         f = self.fixed_view_idx
@@ -1067,7 +1096,7 @@ class VariationalGPSA(GPSA):
 
     def _loss_aux(self, data_dict):
         """the loss nodes' ``aux``: observations, the modalities' entries of ``noise_variance`` (quirk 5), the KL scale;
-        with a Poisson modality also the terms' kinds and the Poisson terms' per-row log offsets
+        with a Poisson or negative binomial modality also the terms' kinds and those terms' per-row log offsets
         (``data_dict[m]["log_offset"]``: optional, fp32 [N] on the model's device; refused for a Gaussian modality)"""
         nn_ = self.noise_variance.numel()
         aux = dict(Y=[data_dict[m]["outputs"] for m in self.modality_names],
@@ -1078,7 +1107,7 @@ class VariationalGPSA(GPSA):
             o = data_dict[m].get("log_offset")
             if o is not None and (kinds is None or kinds[i] == 0):
                 raise ValueError(f"loss_fn: data_dict[{m!r}] carries 'log_offset', but modality {m!r} has a Gaussian "
-                                 "likelihood (offsets belong to a Poisson modality: model.likelihood)")
+                                 "likelihood (offsets belong to a Poisson or negative binomial modality: model.likelihood)")
             if o is not None:
                 N = int(data_dict[m]["outputs"].shape[0])
                 if (not torch.is_tensor(o) or o.dtype != torch.float32 or tuple(o.shape) != (N,)
@@ -1117,6 +1146,9 @@ class VariationalGPSA(GPSA):
                 fuse["skip"] = skip  # (run_fused: gpsa_step_io.skip_missing)
                 # (run_fused: gpsa_step_likelihood for the modalities it enqueues)
                 fuse["lik"], fuse["log_offset"] = aux.get("kinds"), aux.get("log_offset")
+                if aux.get("kinds") is not None and _lib.LIK_NEGBIN in aux["kinds"]:  # (run_fused: gpsa_step_dispersion)
+                    fuse["log_disp"] = [SE._f32c(self.log_dispersion[m].detach()) if k == _lib.LIK_NEGBIN else None
+                                        for m, k in zip(self.modality_names, aux["kinds"])]
             Fs, eff, run_i, run_Y, run_parts = [], [], [], [], []
             lmc_terms, Ws, shapes = {}, [], [None] * self.n_modalities
             for i, m in enumerate(self.modality_names):

@@ -42,7 +42,7 @@ def shard_data_dict(data_dict, rank, world):
             "outputs": d["outputs"][idx].contiguous(),
             "n_samples_list": new_ns,
         }
-        if d.get("log_offset") is not None:  # a Poisson modality's per-row log offsets travel with the rows
+        if d.get("log_offset") is not None:  # a count modality's per-row log offsets travel with the rows
             out[mod]["log_offset"] = d["log_offset"][idx].contiguous()
     return out
 
@@ -80,7 +80,9 @@ def own_kl_terms(model, rank, world):
     return own if own is not None else (0, n)
 
 
-OUTPUT_LOCAL_PREFIXES = ("Omega_sqt_F_dict.", "delta_F_dict.")
+# (log_dispersion: a negative binomial modality's rho has one entry per output, so an output-sharded rank owns the
+# entries of its own columns like its columns' variational parameters - no other rank has a gradient for them)
+OUTPUT_LOCAL_PREFIXES = ("Omega_sqt_F_dict.", "delta_F_dict.", "log_dispersion.")
 
 
 def shared_parameters(model):

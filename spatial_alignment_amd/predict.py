@@ -141,6 +141,8 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
         the data GP is then evaluated THERE and not on the rows of ``X_spatial``, which may be omitted (given, it still
         yields ``G_mean`` / ``G_scale``).
     Y {mod: [N, P]} (at ``G_test``'s rows when that is given): adds ``lpd`` [N] fp64 and ``lpd_sum``.
+        Refused (ValueError), like ``scale="response"``, when a modality has a negative binomial likelihood: it has no
+        count-scale prediction yet (its ``F_mean`` / ``F_var``, the moments of the log mean, are there).
         With ``scale="link"`` refused (ValueError) when a modality has a Poisson likelihood (``model.likelihood``): its
         ``F_mean`` / ``F_var`` are the moments of the log rate, and the Gaussian closed form of ``lpd`` does not apply to
         counts; ``scale="response"`` scores them.
@@ -171,6 +173,13 @@ def predict(model, X_spatial=None, view_idx=None, Ns=None, *, S=10, warp="sample
     S = 1 if warp == "mean" else int(S)
     response = scale == "response"
     pois = {m: getattr(model, "likelihood_of", lambda _m: "gaussian")(m) == "poisson" for m in model.modality_names}
+    for m in model.modality_names:
+        # a negative binomial modality has no count-scale prediction yet (it would otherwise take the Gaussian branch)
+        if getattr(model, "likelihood_of", lambda _m: "gaussian")(m) == "negative_binomial" and (response or Y is not None):
+            raise ValueError(f"predict: modality {m!r} has a negative binomial likelihood, which has no count-scale "
+                             "prediction yet: scale=\"response\" and Y (lpd) are not available for it; the link-scale "
+                             "fields (F_mean / F_var: the moments of its log mean) are - call predict with "
+                             "scale=\"link\" and without Y")
     if Y is not None and not response:
         for m in model.modality_names:
             if pois[m]:

@@ -802,12 +802,19 @@ class ElboLossFn(torch.autograd.Function):
     aux["kinds"] (model.likelihood with a Poisson modality: per term its GPSA_LIK_* kind, with aux["lgam"] - the Poisson
     terms' lgamma tables, lgamma_sums - and aux["log_offset"], per term a tensor or None) comes first: gpsa_elbo_loss_pois_fwd
     / _bwd, which take all of the tables above (aux["skip"]: the NaN select; a Poisson LMC term:
-    gpsa_lmc_loglik_fused_pois_f32; a fused Poisson term's partial sums are those of y eta - exp(eta))."""
+    gpsa_lmc_loglik_fused_pois_f32; a fused Poisson term's partial sums are those of y eta - exp(eta)).
+    aux["disp"] (a negative binomial modality: {term: index of its rho among the LAST len(aux["disp"]) inputs, behind the
+    W of the LMC terms}): gpsa_nb_const at every step, then gpsa_elbo_loss_nb_fwd / _bwd over the same tables; the
+    gradients of the rho inputs come back behind those of the W (an NB LMC term: gpsa_lmc_loglik_fused_nb_f32, whose
+    per-output sums of u the backward's closing turns into its rho gradient).  Calls without aux["disp"] pass no rho
+    and behave as before."""
 
     @staticmethod
     def forward(ctx, aux, noise, kl, *ins):
         n = len(aux["Y"])
-        Fs, Ws = ins[:n], ins[n:]
+        disp_at = aux.get("disp") or {}  # {NB term: index of its rho among the last len(disp_at) inputs}
+        n_in = len(ins) - len(disp_at)
+        Fs, Ws, Ds = ins[:n], ins[n:n_in], ins[n_in:]
         nobs = aux.get("nobs")
         partial = aux.get("fuse_mods") is not None
         fused = [bool(z) for z in aux["fuse_mods"]] if partial else [False] * n  # partial sums in THIS call
@@ -818,22 +825,28 @@ class ElboLossFn(torch.autograd.Function):
         kinds = aux.get("kinds")
         skip = bool(aux["skip"]) if kinds is not None else nobs is not None  # (the Gaussian closings: counts = skip)
         lmc_op = torch.ops.gpsa.lmc_loglik_fused if not skip else torch.ops.gpsa.lmc_loglik_fused_skip
-        lmc_saved = {}
+        lmc_saved, lmc_usum = {}, {}
         for i, wpos in lmc.items():
             Fl, W = Fc[i], Ws[wpos].detach()
             S_, N_, L_ = (int(d) for d in Fl.shape)
             nparts = int(_lib.load().gpsa_quadform_elbo_parts())
             zpart = torch.empty(nparts, dtype=torch.float64, device=dev)
             dFl, dW = torch.empty_like(Fl), torch.empty_like(W)
-            wsl = _ops_mod.get_ops()._ws(int(_lib.load().gpsa_lmc_loglik_workspace(S_ * N_, L_, int(W.shape[1]), nparts)),
-                                         Fl)
-            if kinds is not None and kinds[i] == _lib.LIK_KINDS["poisson"]:
+            nb = kinds is not None and kinds[i] == _lib.LIK_NEGBIN
+            query = _lib.load().gpsa_lmc_loglik_nb_workspace if nb else _lib.load().gpsa_lmc_loglik_workspace
+            wsl = _ops_mod.get_ops()._ws(int(query(S_ * N_, L_, int(W.shape[1]), nparts)), Fl)
+            if nb:  # (its per-output sums of u go to the closing's backward: the gradient of rho)
+                lmc_usum[i] = torch.empty(int(W.shape[1]), dtype=torch.float64, device=dev)
+                torch.ops.gpsa.lmc_loglik_fused_nb(Fl, W, Yc[i], aux["log_offset"][i], _f32c(Ds[disp_at[i]].detach()),
+                                                   int(skip), zpart, dFl, dW, lmc_usum[i], wsl)
+            elif kinds is not None and kinds[i] == _lib.LIK_KINDS["poisson"]:
                 torch.ops.gpsa.lmc_loglik_fused_pois(Fl, W, Yc[i], aux["log_offset"][i], int(skip), zpart, dFl, dW, wsl)
             else:
                 lmc_op(Fl, W, Yc[i], nz, idx[i], zpart, dFl, dW, wsl)
             lmc_saved[i] = (dFl, dW, wpos)
             Fc[i] = zpart
-        loss, ll, ws = _loss_outputs(n, dev)  # (after the LMC terms: they grow the same per-stream scratch)
+        if not (kinds is not None and disp_at):  # (the NB closing makes its own: another workspace size)
+            loss, ll, ws = _loss_outputs(n, dev)  # (after the LMC terms: they grow the same per-stream scratch)
         tabs = ()
         if any(fused):
             shapes = []
@@ -845,6 +858,9 @@ class ElboLossFn(torch.autograd.Function):
             name = "elbo_loss_pois"
             tabs = (tabs or ([], [])) + views + (list(nobs) if nobs is not None else [], [int(k) for k in kinds],
                                                  list(aux["lgam"]), list(aux["log_offset"]), int(skip))
+            if disp_at:
+                return ElboLossFn._forward_nb(ctx, aux, noise, kl, Ds, disp_at, Fc, Yc, nz, idx, tabs, fused, klc, lmc_saved,
+                                              lmc_usum, len(Ws))
         elif nobs is not None:
             views = (list(aux["n_views"]), list(aux["view_off"]), list(aux["weights"])) if "weights" in aux else ([], [], [])
             name, tabs = "elbo_loss_skip", (tabs or ([], [])) + views + (list(nobs),)
@@ -853,13 +869,58 @@ class ElboLossFn(torch.autograd.Function):
         else:
             name = "elbo_loss_fused" if tabs else "elbo_loss"
         getattr(torch.ops.gpsa, name + "_fwd")(Fc, Yc, nz, idx, *tabs, klc, float(aux["kl_scale"]), loss, ll, ws)
-        ctx.aux, ctx.args = aux, (name, Fc, Yc, nz, idx, tabs, fused)
-        ctx.lmc, ctx.n_w = lmc_saved, len(Ws)
+        ctx.nb = None
+        return ElboLossFn._remember(ctx, aux, (name, Fc, Yc, nz, idx, tabs, fused), lmc_saved, len(Ws), klc, kl, noise, loss)
+
+    @staticmethod
+    def _remember(ctx, aux, args, lmc_saved, n_w, klc, kl, noise, loss):
+        ctx.aux, ctx.args = aux, args
+        ctx.lmc, ctx.n_w = lmc_saved, n_w
         ctx.n_kl = 0 if klc is None else klc.numel()
         # (the kernels see kl flat and fp64; its gradient goes back in kl's own shape and dtype)
         ctx.kl_meta = None if (kl is None or (kl.dim() == 1 and kl.dtype == torch.float64)) else (kl.shape, kl.dtype)
         ctx.noise_meta = (noise.shape, noise.dtype)
         return loss.reshape(())
+
+    @staticmethod
+    def _forward_nb(ctx, aux, noise, kl, Ds, disp_at, Fc, Yc, nz, idx, tabs, fused, klc, lmc_saved, lmc_usum, n_w):
+        """the closing of a model with negative binomial terms (aux["disp"]): gpsa_nb_const for the pieces that depend on
+        rho and not on the draws - every step, rho moves - then gpsa_elbo_loss_nb_fwd over the Poisson closing's tables"""
+        n, dev = len(Yc), Yc[0].device
+        ops = _ops_mod.get_ops()
+        nbi = sorted(disp_at)
+        disp = [None] * n
+        for i in nbi:
+            disp[i] = _f32c(Ds[disp_at[i]].detach())
+        nv_all, off_all, w_all = tabs[2], tabs[3], tabs[4]  # (loss_fn gives every term views and weights; none: one view)
+        starts, at = [], 0
+        for v in nv_all:
+            starts.append(at)
+            at += int(v) + 1
+        csum, dconst = [None] * n, [None] * n
+        for i in nbi:
+            csum[i] = torch.empty(int(nv_all[i]) if nv_all else 1, dtype=torch.float64, device=dev)
+            dconst[i] = torch.empty(disp[i].numel(), dtype=torch.float64, device=dev)
+        sub_nv = [int(nv_all[i]) for i in nbi] if nv_all else []
+        sub_off = [x for i in nbi for x in off_all[starts[i]:starts[i] + int(nv_all[i]) + 1]] if nv_all else []
+        Ynb = [Yc[i] for i in nbi]
+        wsc = ops._ws(TO.nb_const_workspace_bytes(Ynb, sub_nv), Yc[0])
+        torch.ops.gpsa.nb_const(Ynb, [disp[i] for i in nbi], sub_nv, sub_off, [w_all[i] for i in nbi] if w_all else [],
+                                int(tabs[-1]), [csum[i] for i in nbi], [dconst[i] for i in nbi], wsc)
+        shapes = list(tabs[0]) or [int(d) for f in Fc for d in f.shape]
+        ws_bytes = TO.nb_loss_workspace_bytes(shapes, [int(v) for v in nv_all], tabs[6])
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ll = torch.empty(n, dtype=torch.float64, device=dev)
+        torch.ops.gpsa.elbo_loss_nb_fwd(Fc, Yc, nz, idx, *tabs[:-1], disp, csum, tabs[-1], klc, float(aux["kl_scale"]), loss,
+                                        ll, ops._ws(ws_bytes, loss))
+        # a term that arrived as partial sums brings its [P] fp64 sums of u: an LMC term from gpsa_lmc_loglik_fused_nb_f32
+        # above, a term of the step's fused pass from the record (lazy.run_fused: gpsa_step_dispersion's usum)
+        rec_usum = (aux.get("fuse") or {}).get("nb_usum") or {}
+        usum = [lmc_usum.get(i, rec_usum.get(i) if fused[i] else None) if i in disp_at else None for i in range(n)]
+        ctx.nb = (disp, dconst, usum, ws_bytes, [disp_at[i] for i in nbi], nbi,
+                  [(Ds[disp_at[i]].shape, Ds[disp_at[i]].dtype) for i in nbi], len(Ds))
+        return ElboLossFn._remember(ctx, aux, ("elbo_loss_nb", Fc, Yc, nz, idx, tabs, fused), lmc_saved, n_w, klc, kl, noise,
+                                    loss)
 
     @staticmethod
     def backward(ctx, gloss):
@@ -876,12 +937,25 @@ class ElboLossFn(torch.autograd.Function):
             dWs[wpos] = dW * g
         # (mutable-argument list: no expanded tensors in it - a fused term's slot holds g, its dF is not written)
         real = [d if not z else g for d, z in zip(dF, fused)] if any(fused) else dF
-        getattr(torch.ops.gpsa, name + "_bwd")(Fc, Yc, nz, idx, *tabs, g, int(ctx.n_kl), float(aux["kl_scale"]), real,
-                                               dnoise, dkl, ws)
+        dDs = ()
+        if ctx.nb is not None:
+            disp, dconst, usum, ws_bytes, pos, nbi, meta, n_d = ctx.nb
+            # (mutable-argument list: a term without a rho holds a dummy of its own in its slot, which is not written)
+            dummy = g.new_empty(1)
+            ddisp = [dummy if d is None else torch.empty_like(d) for d in disp]
+            torch.ops.gpsa.elbo_loss_nb_bwd(Fc, Yc, nz, idx, *tabs[:-1], disp, dconst, usum, tabs[-1], g, int(ctx.n_kl),
+                                            float(aux["kl_scale"]), real, dnoise, dkl, ddisp,
+                                            _ops_mod.get_ops()._ws(ws_bytes, g))
+            dDs = [None] * n_d
+            for i, k, (shape, dt) in zip(nbi, pos, meta):
+                dDs[k] = ddisp[i].reshape(shape).to(dt)
+        else:
+            getattr(torch.ops.gpsa, name + "_bwd")(Fc, Yc, nz, idx, *tabs, g, int(ctx.n_kl), float(aux["kl_scale"]), real,
+                                                   dnoise, dkl, ws)
         if ctx.kl_meta is not None:
             kshape, kdt = ctx.kl_meta
             dkl = dkl.reshape(kshape).to(kdt)
-        return _loss_grads(ctx, dnoise, dkl, dF, dWs)
+        return _loss_grads(ctx, dnoise, dkl, dF, dWs) + tuple(dDs)
 
 
 _NOBS_CACHE_MAX = 8

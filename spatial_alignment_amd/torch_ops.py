@@ -28,6 +28,8 @@ each with
                                             gpsa::lmc_loglik_fused_skip                (model.skip_missing)
    count outputs (opt-in)                   gpsa::lgamma_sum, gpsa::elbo_loss_pois_fwd / _bwd (csrc/poisson.hip,
                                             csrc/loss_views.hip), gpsa::lmc_loglik_fused_pois  (model.likelihood)
+   overdispersed counts (opt-in)            gpsa::nb_const, gpsa::elbo_loss_nb_fwd / _bwd, gpsa::lmc_loglik_fused_nb
+                                            (csrc/negbin.hip, csrc/loss_views.hip, csrc/lmc.hip; model.likelihood = "negative_binomial")
 
 The eight elbo_loss ops share their table builders (``_ll_arrays``, ``_grad_arrays``, ``_view_tables``) and are what the
 one loss node, ``step_engine.ElboLossFn``, chooses among.
@@ -695,3 +697,93 @@ def _lmc_loglik_fused_pois(F, W, Y, offset, skip, zpart, dF, dW, ws):
 
 _engine_op("lmc_loglik_fused_pois(Tensor F, Tensor W, Tensor Y, Tensor? offset, int skip, Tensor(a!) zpart, "
            "Tensor(b!) dF, Tensor(c!) dW, Tensor(d!) ws) -> ()", _lmc_loglik_fused_pois)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# count outputs (model.likelihood = "negative_binomial"; csrc/negbin.hip, csrc/loss_views.hip): the negative binomial term
+# ---------------------------------------------------------------------------------------------------------
+def nb_const_workspace_bytes(Ys, n_views):
+    lib = _lib.load()
+    return max(int(lib.gpsa_nb_const_workspace(int(y.shape[0]), int(y.shape[1]), int(n_views[i]) if n_views else 1))
+               for i, y in enumerate(Ys)) + 64
+
+
+def nb_loss_workspace_bytes(shapes, n_views, kinds):
+    """gpsa_elbo_loss_nb_workspace for the terms' [S, N, P] (flattened), view counts (empty: one view each) and kinds"""
+    n = len(shapes) // 3
+    nv = (C.c_int * n)(*[int(v) for v in n_views]) if n_views else None
+    return int(_lib.load().gpsa_elbo_loss_nb_workspace(n, (C.c_int * n)(*shapes[0::3]), (C.c_longlong * n)(*shapes[1::3]),
+                                                       (C.c_int * n)(*shapes[2::3]), nv,
+                                                       (C.c_int * n)(*[int(k) for k in kinds]))) + 64
+
+
+def _nb_const(Ys, disp, n_views, view_off, weights, skip, csum, dconst, ws):
+    """gpsa_nb_const: per NB term, csum[i][v] = sum of lgamma(y + r) - lgamma(r) over view v's rows and dconst[i][p] = the
+    view-weighted sum over rows of r (psi(y + r) - psi(r)), r = exp(disp[i]); device doubles, no host read"""
+    n = len(Ys)
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    nv, offp, Wp, _, _keep = _view_tables(n, n_views, view_off, weights)
+    _lib.check(_lib.load().gpsa_nb_const(n, arr(Ys), (C.c_longlong * n)(*[int(y.shape[0]) for y in Ys]),
+                                         (C.c_int * n)(*[int(y.shape[1]) for y in Ys]), arr(disp), nv, offp, Wp, int(skip),
+                                         arr(csum), arr(dconst), ws.data_ptr(), ws.numel(),
+                                         _raw_stream(ws.device.index)), "gpsa_nb_const")
+
+
+_engine_op("nb_const(Tensor[] Ys, Tensor[] disp, int[] n_views, int[] view_off, Tensor[] weights, int skip, "
+           "Tensor(a!)[] csum, Tensor(b!)[] dconst, Tensor(c!) ws) -> ()", _nb_const)
+
+
+def _elbo_loss_nb_fwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, kinds, lgam, offsets,
+                      disp, csum, skip, kl, kl_scale, loss, ll, ws):
+    """gpsa_elbo_loss_nb_fwd: the ELBO loss of a model with negative binomial terms (elbo_loss_pois_fwd's tables; disp /
+    csum: per term a tensor or None - rho and gpsa_nb_const's per-view table)"""
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
+    tabs, _keep = _pois_tables(n, n_views, view_off, weights, nobs, kinds, lgam, offsets)
+    _lib.check(_lib.load().gpsa_elbo_loss_nb_fwd(n, *terms, Zp, nparts, *tabs, _opt_ptrs(n, disp), _opt_ptrs(n, csum),
+                                                 int(skip), *_kl_args(kl), float(kl_scale), loss.data_ptr(), ll.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _raw_stream(loss.device.index)),
+               "gpsa_elbo_loss_nb_fwd")
+
+
+_engine_op("elbo_loss_nb_fwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
+           "int[] n_views, int[] view_off, Tensor[] weights, Tensor?[] nobs, int[] kinds, Tensor?[] lgam, "
+           "Tensor?[] offsets, Tensor?[] disp, Tensor?[] csum, int skip, Tensor? kl, float kl_scale, Tensor(a!) loss, "
+           "Tensor(b!) ll, Tensor(c!) ws) -> ()", _elbo_loss_nb_fwd)
+
+
+def _elbo_loss_nb_bwd(Fs, Ys, noise, noise_idx, shapes, fused, n_views, view_off, weights, nobs, kinds, lgam, offsets,
+                      disp, dconst, usum, skip, gloss, n_kl, kl_scale, dFs, dnoise, dkl, ddisp, ws):
+    """gpsa_elbo_loss_nb_bwd (dconst: gpsa_nb_const's per-output table; usum: a fused NB term's per-output sums of u;
+    ddisp: per term the gradient of rho, written for the NB terms - the other terms' entries are not touched)"""
+    n, terms, Zp, nparts = _ll_arrays(Fs, Ys, noise, noise_idx, shapes or None, fused or None)
+    tabs, _keep = _pois_tables(n, n_views, view_off, weights, nobs, kinds, lgam, offsets)
+    grads = _grad_arrays(dFs, dnoise, noise_idx, fused or None)
+    _lib.check(_lib.load().gpsa_elbo_loss_nb_bwd(n, *terms, Zp, nparts, *tabs, _opt_ptrs(n, disp),
+                                                 _opt_ptrs(n, dconst), _opt_ptrs(n, usum), int(skip), gloss.data_ptr(),
+                                                 int(n_kl), float(kl_scale), *grads, 0 if dkl is None else dkl.data_ptr(),
+                                                 _opt_ptrs(n, ddisp), ws.data_ptr(), ws.numel(),
+                                                 _raw_stream(gloss.device.index)), "gpsa_elbo_loss_nb_bwd")
+
+
+_engine_op("elbo_loss_nb_bwd(Tensor[] Fs, Tensor[] Ys, Tensor noise, int[] noise_idx, int[] shapes, int[] fused, "
+           "int[] n_views, int[] view_off, Tensor[] weights, Tensor?[] nobs, int[] kinds, Tensor?[] lgam, "
+           "Tensor?[] offsets, Tensor?[] disp, Tensor?[] dconst, Tensor?[] usum, int skip, Tensor gloss, int n_kl, "
+           "float kl_scale, Tensor(a!)[] dFs, Tensor(b!) dnoise, Tensor(c!)? dkl, Tensor(d!)[] ddisp, Tensor(e!) ws) -> ()",
+           _elbo_loss_nb_bwd)
+
+
+def _lmc_loglik_fused_nb(F, W, Y, offset, disp, skip, zpart, dF, dW, usum, ws):
+    """gpsa_lmc_loglik_fused_nb_f32: lmc_loglik_fused for a negative binomial modality - F W is the log mean, zpart sums
+    t = y a - (y + r) softplus(a), a = F W + offset[row] - disp[p] (offset: [N] or None), usum [P] fp64 receives the
+    per-output sums of u (elbo_loss_nb_bwd's usum)"""
+    S, N, L = (int(d) for d in F.shape)
+    _lib.check(_lib.load().gpsa_lmc_loglik_fused_nb_f32(F.data_ptr(), W.data_ptr(), Y.data_ptr(),
+                                                        0 if offset is None else offset.data_ptr(), disp.data_ptr(),
+                                                        int(skip), S, N, L, int(W.shape[1]), zpart.data_ptr(),
+                                                        zpart.numel(), dF.data_ptr(), dW.data_ptr(), usum.data_ptr(),
+                                                        ws.data_ptr(), ws.numel(), _raw_stream(F.device.index)),
+               "gpsa_lmc_loglik_fused_nb_f32")
+
+
+_engine_op("lmc_loglik_fused_nb(Tensor F, Tensor W, Tensor Y, Tensor? offset, Tensor disp, int skip, Tensor(a!) zpart, "
+           "Tensor(b!) dF, Tensor(c!) dW, Tensor(d!) usum, Tensor(e!) ws) -> ()", _lmc_loglik_fused_nb)

@@ -100,7 +100,7 @@ class Microbatches:
                 idx = torch.cat(rows).to(d["spatial_coords"].device)
                 dd[mod] = {"spatial_coords": d["spatial_coords"][idx].contiguous(),
                            "outputs": d["outputs"][idx].contiguous(), "n_samples_list": new_ns}
-                if d.get("log_offset") is not None:  # (a Poisson modality's per-row log offsets)
+                if d.get("log_offset") is not None:  # (a count modality's per-row log offsets)
                     dd[mod]["log_offset"] = d["log_offset"][idx].contiguous()
             vi, Ns, _, _ = model.create_view_idx_dict(dd)
             self.slices.append((dd, vi, Ns))
