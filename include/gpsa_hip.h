@@ -1051,6 +1051,24 @@ int gpsa_predict_counts_f32(const float* meanT, const float* v, const double* q,
                             int L, int P, const float* W, const float* log_offset, const float* Y, float* Y_mean,
                             float* Y_var, double* lpd, void* stream);
 
+/* ---- the learned warp as a function of the point (csrc/warp_field.hip): mean, Jacobian, determinant, inverse ----------
+ * A non-fixed view's warp mean is closed form in x (vgpsa.py:174-204, mean only):
+ *   g(x) = x A + b + k(x, Z) beta,   J[j, d] = d g_j / d x_d = A[d, j] + sum_m beta[m, j] cd(x, z_m) (x[d] - z_m[d])
+ * Z, beta [M, D] (beta = K_uu^-1 (delta_G - (Z A + b)), formed by the caller), A [D, D], b [D], ls_u / var_u: device
+ * scalars, unconstrained, as gpsa_kmat takes them; kind: GPSA_K_*.  Everything fp64; k(X, Z) is never formed in memory.
+ * gpsa_warp_field_f64: X [n, D] -> G [n, D] and, where non-NULL, J [n, D, D] and det [n] = det J.
+ * gpsa_warp_invert_f64: exactly `iters` undamped Newton updates x <- x - J(x)^-1 (g(x) - target) from x0 [n, D] in one
+ *   launch (no early exit), then residual [n] = |g(X) - target|_2 evaluated at the returned X [n, D].  A zero or non-finite
+ *   pivot of the D x D solve (partial pivoting) or a non-finite iterate fails the row: X = NaN, residual = +inf.
+ * A row's result depends on its own inputs and M alone (not on n or its neighbours), the same bits from run to run.
+ * GPSA_EINVAL: a NULL pointer (J / det excepted), n, M, D < 1, an unknown kind, iters < 0;  GPSA_EUNSUPPORTED: D > 4. */
+int gpsa_warp_field_f64(int kind, const double* Z, const double* beta, const double* A, const double* b,
+                        const double* ls_u, const double* var_u, const double* X, long long n, int M, int D, double* G,
+                        double* J, double* det, void* stream);
+int gpsa_warp_invert_f64(int kind, const double* Z, const double* beta, const double* A, const double* b,
+                         const double* ls_u, const double* var_u, const double* target, const double* x0, int iters,
+                         long long n, int M, int D, double* X, double* residual, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from .util import (
     polar_warp,
     rbf_kernel_numpy,
 )
+from .warp import transfer, unwarp, warp_field
 
 __all__ = [
     "GPSA",
@@ -27,5 +28,8 @@ __all__ = [
     "ConvergenceChecker",
     "fit",
     "predict",
+    "warp_field",
+    "unwarp",
+    "transfer",
 ]
 __version__ = "0.1.0"

@@ -814,6 +814,26 @@ class VariationalGPSA(GPSA):
 
         return _predict(self, X_spatial, view_idx, Ns, **kwargs)
 
+    def warp_field(self, X, view, **kwargs):
+        """The mean of view ``view``'s learned warp at any points ``X`` [n, D] of its native coordinates, with its
+        Jacobian, ``det`` (local area / volume change) and the folding count ``n_folded`` (``warp.warp_field``)."""
+        from ..warp import warp_field as _warp_field
+
+        return _warp_field(self, X, view, **kwargs)
+
+    def unwarp(self, G, view, **kwargs):
+        """Where aligned locations ``G`` [n, D] lie in view ``view``'s own coordinates: Newton's iteration on the warp's
+        mean, with an honest ``residual`` / ``converged`` per row (``warp.unwarp``)."""
+        from ..warp import unwarp as _unwarp
+
+        return _unwarp(self, G, view, **kwargs)
+
+    def transfer(self, X, view_from, view_to, **kwargs):
+        """Points ``X`` [n, D] of view ``view_from`` in view ``view_to``'s coordinates (``warp.transfer``)."""
+        from ..warp import transfer as _transfer
+
+        return _transfer(self, X, view_from, view_to, **kwargs)
+
     def _lazy_obs(self, plan, G_test, prediction_mode, grads):
         """per modality: True = an LMC modality whose F_obs = F_latent W is left to whoever asks for it (training;
         loss_fn runs gpsa_lmc_loglik_fused_f32 on (F_latent, W, Y) instead of forming it).  ``grads``: gradients are

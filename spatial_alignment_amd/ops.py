@@ -543,6 +543,69 @@ class HipOps:
         _lib.check(rc, "gpsa_predict_counts_f32")
         return Ym, Yv, lpd
 
+    def _warp_model_args(self, what, kind, Z, beta, A, b, ls_u, var_u):
+        """the model side of the two warp entries as contiguous fp64 tensors, shapes checked -> (tensors, M, D)"""
+        if kind not in KINDS:
+            raise ValueError(f"{what}: kind must be one of {sorted(KINDS)}, not {kind!r}")
+        Z, beta, A, b, ls_u, var_u = (self._f64(t) for t in (Z, beta, A, b, ls_u, var_u))
+        if Z.dim() != 2:
+            raise ValueError(f"{what}: Z has shape {tuple(Z.shape)}, [M, D] is needed")
+        M, D = (int(s) for s in Z.shape)
+        for name, t, sh in (("beta", beta, (M, D)), ("A", A, (D, D)), ("b", b, (D,))):
+            if tuple(t.shape) != sh:
+                raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, Z gives {sh}")
+        return (Z, beta, A, b, ls_u.reshape(-1), var_u.reshape(-1)), M, D
+
+    def warp_field(self, kind, Z, beta, A, b, ls_u, var_u, X, jacobian=True, out=None):
+        """gpsa_warp_field_f64: the warp mean g(x) = x A + b + k(x, Z) beta at X [n, D] and, with ``jacobian``, its
+        Jacobian J [n, D, D] (J[n, j, d] = d g_j / d x_d) and det J [n]; all fp64.  -> (G, J or None, det or None);
+        ``out``: the same three, preallocated (contiguous row slices of the caller's results)."""
+        mdl, M, D = self._warp_model_args("warp_field", kind, Z, beta, A, b, ls_u, var_u)
+        X = self._f64(X)
+        if X.dim() != 2 or X.shape[1] != D or X.shape[0] < 1:
+            raise ValueError(f"warp_field: X has shape {tuple(X.shape)}, [n >= 1, {D}] is needed")
+        n = int(X.shape[0])
+        f64, dev = torch.float64, X.device
+        if out is None:
+            out = (torch.empty(n, D, dtype=f64, device=dev),
+                   torch.empty(n, D, D, dtype=f64, device=dev) if jacobian else None,
+                   torch.empty(n, dtype=f64, device=dev) if jacobian else None)
+        G, J, det = out
+        for t, sh in ((G, (n, D)), (J, (n, D, D)), (det, (n,))):
+            assert t is None or (tuple(t.shape) == sh and t.dtype == f64 and t.is_contiguous()), sh
+        rc = self.lib.gpsa_warp_field_f64(KINDS[kind], *(_p(t) for t in mdl), _p(X), n, M, D, _p(G), _p(J), _p(det),
+                                          self._stream(X))
+        _lib.check(rc, "gpsa_warp_field_f64")
+        return G, J, det
+
+    def warp_invert(self, kind, Z, beta, A, b, ls_u, var_u, target, x0, iters, out=None):
+        """gpsa_warp_invert_f64: exactly ``iters`` Newton updates of g(x) = target [n, D] from x0 [n, D] in one launch
+        -> (X [n, D], residual [n] = |g(X) - target|_2 at the returned X); a failed row is NaN / +inf.  All fp64."""
+        mdl, M, D = self._warp_model_args("warp_invert", kind, Z, beta, A, b, ls_u, var_u)
+        target, x0 = self._f64(target), self._f64(x0)
+        if target.dim() != 2 or target.shape[1] != D or target.shape[0] < 1 or tuple(x0.shape) != tuple(target.shape):
+            raise ValueError(f"warp_invert: target {tuple(target.shape)} and x0 {tuple(x0.shape)} must both be "
+                             f"[n >= 1, {D}]")
+        iters = int(iters)
+        if iters < 0:
+            raise ValueError(f"warp_invert: iters must be >= 0, not {iters}")
+        n = int(target.shape[0])
+        f64, dev = torch.float64, target.device
+        if out is None:
+            out = (torch.empty(n, D, dtype=f64, device=dev), torch.empty(n, dtype=f64, device=dev))
+        X, res = out
+        for t, sh in ((X, (n, D)), (res, (n,))):
+            assert tuple(t.shape) == sh and t.dtype == f64 and t.is_contiguous(), sh
+        rc = self.lib.gpsa_warp_invert_f64(KINDS[kind], *(_p(t) for t in mdl), _p(target), _p(x0), iters, n, M, D, _p(X),
+                                           _p(res), self._stream(target))
+        _lib.check(rc, "gpsa_warp_invert_f64")
+        return X, res
+
+    @staticmethod
+    def _f64(t):
+        t = t if t.dtype == torch.float64 else t.double()
+        return t if t.is_contiguous() else t.contiguous()
+
     @staticmethod
     def _f32(t):
         t = t if t.dtype == torch.float32 else t.float()

@@ -18,6 +18,7 @@ each with
    (4) reparameterised draws                gpsa::gauss_sample_F (+ _bwd)              (vgpsa.py:423-426)
        ... closed as moments (prediction)   gpsa::predict_moments                      (predict.py)
        ... closed as counts (prediction)    gpsa::predict_counts                       (predict.py, scale="response")
+       the warp as a function of the point  gpsa::warp_field, gpsa::warp_invert        (warp.py; csrc/warp_field.hip)
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
@@ -269,6 +270,43 @@ def _(meanT, v, q, var_u, S, W=None, log_offset=None, Y=None):
     P = L if W is None else W.shape[1]
     return (meanT.new_empty(c, P), meanT.new_empty(c, P),
             meanT.new_empty(c if Y is not None else 0, dtype=torch.float64))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# (4d) the warp as a function of the point: mean, Jacobian, determinant; and its Newton inverse (warp.py)
+# ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("gpsa::warp_field", mutates_args=(), device_types="cuda")
+def warp_field(Z: torch.Tensor, beta: torch.Tensor, A: torch.Tensor, b: torch.Tensor, ls_u: torch.Tensor,
+               var_u: torch.Tensor, X: torch.Tensor, kind: str,
+               jacobian: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """g(x) = x A + b + k(x, Z) beta at X [n, D] -> (G [n, D], J [n, D, D], det [n]), fp64; J and det are empty tensors
+    without ``jacobian`` (csrc/warp_field.hip)"""
+    G, J, det = _o().warp_field(kind, Z, beta, A, b, ls_u, var_u, X, jacobian)
+    none = lambda t: G.new_empty(0) if t is None else t
+    return G, none(J), none(det)
+
+
+@warp_field.register_fake
+def _(Z, beta, A, b, ls_u, var_u, X, kind, jacobian=True):
+    n, D = X.shape
+    f64 = torch.float64
+    return (X.new_empty(n, D, dtype=f64), X.new_empty((n, D, D) if jacobian else (0,), dtype=f64),
+            X.new_empty(n if jacobian else 0, dtype=f64))
+
+
+@torch.library.custom_op("gpsa::warp_invert", mutates_args=(), device_types="cuda")
+def warp_invert(Z: torch.Tensor, beta: torch.Tensor, A: torch.Tensor, b: torch.Tensor, ls_u: torch.Tensor,
+                var_u: torch.Tensor, target: torch.Tensor, x0: torch.Tensor, kind: str,
+                iters: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """exactly ``iters`` Newton updates of g(x) = target from x0 -> (X [n, D], residual [n]), fp64; a failed row is
+    NaN / +inf (csrc/warp_field.hip)"""
+    return _o().warp_invert(kind, Z, beta, A, b, ls_u, var_u, target, x0, iters)
+
+
+@warp_invert.register_fake
+def _(Z, beta, A, b, ls_u, var_u, target, x0, kind, iters):
+    n, D = target.shape
+    return target.new_empty(n, D, dtype=torch.float64), target.new_empty(n, dtype=torch.float64)
 
 
 # ---------------------------------------------------------------------------------------------------------
