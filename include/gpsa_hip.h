@@ -1069,6 +1069,32 @@ int gpsa_warp_invert_f64(int kind, const double* Z, const double* beta, const do
                          const double* ls_u, const double* var_u, const double* target, const double* x0, int iters,
                          long long n, int M, int D, double* X, double* residual, void* stream);
 
+/* ---- neighbour statistics (csrc/neighbors.hip): exact k nearest neighbours and the neighbours' weighted average ---------
+ * gpsa_knn_f64: for every row of Q [nq, D] the k rows of R [nr, D] with the smallest key (d2, index), ascending in that
+ *   key: d2 = sum_d (q_d - r_d)^2 in fp64 in difference form, ties in d2 to the lower index (a total order, so the result
+ *   is the same bits for every `parts`).  idx [nq, k] int32, d2 [nq, k] fp64.  exclude_self != 0 skips reference j == i
+ *   for query i (leave-one-out: the caller passes the same array as Q and R; where Q points at a later row of R's array,
+ *   a row slice for a chunked call, the row skipped is the query's own row of R).  A distance that is NaN counts as +inf.
+ *   parts: slices of the reference axis scanned by separate workgroups and merged by a second kernel by the same key;
+ *   0 = auto (enough workgroups in flight when nq is small).  No atomics.  workspace >= gpsa_knn_workspace(nq, nr, k,
+ *   parts) bytes (0 when the call resolves to one slice).
+ *   GPSA_EINVAL: a NULL pointer, nq, nr, D, k < 1, parts < 0, k > nr - (exclude_self ? 1 : 0);  GPSA_EUNSUPPORTED: D > 4,
+ *   k > 32;  GPSA_EWORKSPACE.  Every check runs before the first launch.
+ * gpsa_knn_average_f32: out[i, p] = sum_j w_ij Y[idx[i, j], p] / sum_j w_ij over the neighbours j whose Y entry is not
+ *   NaN (none: NaN), accumulated in fp64 in the order j = 0 .. k-1.  idx [nq, k], Y [nr, P] fp32, out [nq, P] fp32.
+ *   weights 0: uniform (d2 may be NULL);  1: inverse distance, w = 1 / sqrt(d2), and in a row where some d2 == 0 exactly
+ *   the zero-distance neighbours get weight 1 and the others 0.  No workspace.  Indices are not validated.
+ *   GPSA_EINVAL: a NULL pointer (d2 with weights 0 excepted), nq, k, nr, P < 1, an unknown `weights`.
+ * gpsa_knn_average_f64: the same kernel with Y and out in fp64 (Moran's I needs the lag of a centred column to fp64
+ *   rounding; an fp32 result carries 6e-8). */
+long long gpsa_knn_workspace(long long nq, long long nr, int k, int parts);
+int gpsa_knn_f64(const double* Q, long long nq, const double* R, long long nr, int D, int k, int exclude_self, int parts,
+                 int* idx, double* d2, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_knn_average_f32(const int* idx, const double* d2, long long nq, int k, const float* Y, long long nr, int P,
+                         int weights, float* out, void* stream);
+int gpsa_knn_average_f64(const int* idx, const double* d2, long long nq, int k, const double* Y, long long nr, int P,
+                         int weights, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

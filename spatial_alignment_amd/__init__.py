@@ -4,6 +4,7 @@ Same public names as the reference package (gpsa/__init__.py:1-10) for the parts
 """
 from .kernels import matern12_kernel, matern32_kernel, rbf_kernel
 from .models import GPSA, VariationalGPSA
+from .neighbors import alignment_score, knn, knn_regress, kth_neighbor_distance, moran_i, spatial_r2
 from .parallel import fit
 from .predict import predict
 from .util import (
@@ -31,5 +32,11 @@ __all__ = [
     "warp_field",
     "unwarp",
     "transfer",
+    "knn",
+    "knn_regress",
+    "spatial_r2",
+    "kth_neighbor_distance",
+    "moran_i",
+    "alignment_score",
 ]
 __version__ = "0.1.0"

@@ -226,6 +226,11 @@ SIGNATURES.update({
     # the warp as a function of the point: mean / Jacobian / determinant and the Newton inverse (csrc/warp_field.hip)
     "gpsa_warp_field_f64": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp]),
     "gpsa_warp_invert_f64": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ll, _i, _i, _vp, _vp, _vp]),
+    # neighbour statistics: exact kNN and the neighbours' weighted average (csrc/neighbors.hip)
+    "gpsa_knn_workspace": (_ll, [_ll, _ll, _i, _i]),
+    "gpsa_knn_f64": (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_knn_average_f32": (_i, [_vp, _vp, _ll, _i, _vp, _ll, _i, _i, _vp, _vp]),
+    "gpsa_knn_average_f64": (_i, [_vp, _vp, _ll, _i, _vp, _ll, _i, _i, _vp, _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

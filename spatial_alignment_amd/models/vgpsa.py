@@ -834,6 +834,14 @@ class VariationalGPSA(GPSA):
 
         return _transfer(self, X, view_from, view_to, **kwargs)
 
+    def alignment_score(self, X_spatial, Y, view_idx=None, **kwargs):
+        """Did the alignment get better?  Per modality, every view's outputs predicted from every other view's spots by
+        kNN regression at the aligned coordinates, scored by R^2 and Pearson's r, with the same from the native
+        coordinates for comparison (``neighbors.alignment_score``)."""
+        from ..neighbors import alignment_score as _alignment_score
+
+        return _alignment_score(self, X_spatial, Y, view_idx, **kwargs)
+
     def _lazy_obs(self, plan, G_test, prediction_mode, grads):
         """per modality: True = an LMC modality whose F_obs = F_latent W is left to whoever asks for it (training;
         loss_fn runs gpsa_lmc_loglik_fused_f32 on (F_latent, W, Y) instead of forming it).  ``grads``: gradients are

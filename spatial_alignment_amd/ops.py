@@ -601,6 +601,71 @@ class HipOps:
         _lib.check(rc, "gpsa_warp_invert_f64")
         return X, res
 
+    def knn(self, Q, R, k, exclude_self=False, parts=0, out=None):
+        """gpsa_knn_f64: for every row of Q [nq, D] the k rows of R [nr, D] with the smallest key (squared distance in
+        fp64, index), ascending -> (idx [nq, k] int32, d2 [nq, k] fp64).  ``exclude_self`` skips a query's own row of
+        R (Q is then R itself or a contiguous row slice of R's storage: a chunk); ``parts``: slices of the reference axis, 0 = auto - the result is the
+        same bits for every value.  ``out``: the same two, preallocated."""
+        Q, R = self._f64(Q), self._f64(R)
+        if Q.dim() != 2 or R.dim() != 2 or Q.shape[0] < 1 or R.shape[0] < 1 or Q.shape[1] != R.shape[1]:
+            raise ValueError(f"knn: Q {tuple(Q.shape)} and R {tuple(R.shape)} must be [nq >= 1, D] and [nr >= 1, D]")
+        (nq, D), nr = (int(s) for s in Q.shape), int(R.shape[0])
+        k, parts, excl = int(k), int(parts), 1 if exclude_self else 0
+        if D < 1 or D > 4:
+            raise ValueError(f"knn: D = {D}; 1 to 4 coordinates are supported")
+        if k < 1 or k > 32:
+            raise ValueError(f"knn: k = {k}; 1 to 32 neighbours are supported")
+        if k > nr - excl:
+            raise ValueError(f"knn: k = {k} neighbours asked of {nr - excl} reference rows"
+                             + (" (the point itself is excluded)" if excl else ""))
+        if excl and nq > nr:
+            raise ValueError(f"knn: exclude_self needs Q to be R or a row slice of it, not {nq} rows against {nr}")
+        if parts < 0:
+            raise ValueError(f"knn: parts must be >= 0, not {parts}")
+        dev = Q.device
+        if out is None:
+            out = (torch.empty(nq, k, dtype=torch.int32, device=dev), torch.empty(nq, k, dtype=torch.float64, device=dev))
+        idx, d2 = out
+        for t, dt in ((idx, torch.int32), (d2, torch.float64)):
+            assert tuple(t.shape) == (nq, k) and t.dtype == dt and t.is_contiguous(), (nq, k)
+        nbytes = self._wsq("gpsa_knn_workspace", nq, nr, k, parts)
+        ws = self._ws(nbytes, Q) if nbytes else None
+        rc = self.lib.gpsa_knn_f64(_p(Q), nq, _p(R), nr, D, k, excl, parts, _p(idx), _p(d2), _p(ws), nbytes,
+                                   self._stream(Q))
+        _lib.check(rc, "gpsa_knn_f64")
+        return idx, d2
+
+    def knn_average(self, idx, d2, Y, weights="uniform", out=None):
+        """gpsa_knn_average_f32: out[i, p] = sum_j w_ij Y[idx[i, j], p] / sum_j w_ij over the neighbours whose Y entry
+        is not NaN (none: NaN), fp64 accumulation in neighbour order -> [nq, P] fp32 (an fp64 Y goes through
+        gpsa_knn_average_f64 and gives fp64; every other dtype is taken to fp32).  ``weights``: "uniform" (d2 may be
+        None) or "distance" (1 / sqrt(d2); a row with zero distances averages exactly those neighbours).  The indices
+        are not validated: they must be rows of Y."""
+        if weights not in ("uniform", "distance"):
+            raise ValueError(f"knn_average: weights must be 'uniform' or 'distance', not {weights!r}")
+        if idx.dim() != 2 or idx.dtype != torch.int32 or idx.shape[0] < 1 or idx.shape[1] < 1:
+            raise ValueError(f"knn_average: idx must be int32 [nq >= 1, k >= 1], not {idx.dtype} {tuple(idx.shape)}")
+        if Y.dim() != 2 or Y.shape[0] < 1 or Y.shape[1] < 1:
+            raise ValueError(f"knn_average: Y has shape {tuple(Y.shape)}, [nr >= 1, P >= 1] is needed")
+        wcode = 1 if weights == "distance" else 0
+        if wcode:
+            if d2 is None or tuple(d2.shape) != tuple(idx.shape):
+                raise ValueError("knn_average: weights='distance' needs d2 of idx's shape "
+                                 f"{tuple(idx.shape)}, not {None if d2 is None else tuple(d2.shape)}")
+            d2 = self._f64(d2)
+        else:
+            d2 = None
+        wide = Y.dtype == torch.float64
+        idx, Y = self._c(idx), (self._f64(Y) if wide else self._f32(Y))
+        (nq, k), (nr, P) = (int(s) for s in idx.shape), (int(s) for s in Y.shape)
+        if out is None:
+            out = torch.empty(nq, P, dtype=Y.dtype, device=Y.device)
+        assert tuple(out.shape) == (nq, P) and out.dtype == Y.dtype and out.is_contiguous(), (nq, P)
+        name = "gpsa_knn_average_f64" if wide else "gpsa_knn_average_f32"
+        rc = getattr(self.lib, name)(_p(idx), _p(d2), nq, k, _p(Y), nr, P, wcode, _p(out), self._stream(Y))
+        _lib.check(rc, name)
+        return out
+
     @staticmethod
     def _f64(t):
         t = t if t.dtype == torch.float64 else t.double()

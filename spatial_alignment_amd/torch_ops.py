@@ -19,6 +19,7 @@ each with
        ... closed as moments (prediction)   gpsa::predict_moments                      (predict.py)
        ... closed as counts (prediction)    gpsa::predict_counts                       (predict.py, scale="response")
        the warp as a function of the point  gpsa::warp_field, gpsa::warp_invert        (warp.py; csrc/warp_field.hip)
+       neighbour statistics                 gpsa::knn, gpsa::knn_average               (neighbors.py; csrc/neighbors.hip)
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
@@ -307,6 +308,35 @@ def warp_invert(Z: torch.Tensor, beta: torch.Tensor, A: torch.Tensor, b: torch.T
 def _(Z, beta, A, b, ls_u, var_u, target, x0, kind, iters):
     n, D = target.shape
     return target.new_empty(n, D, dtype=torch.float64), target.new_empty(n, dtype=torch.float64)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# (4e) neighbour statistics: exact k nearest neighbours and the neighbours' weighted average (neighbors.py)
+# ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("gpsa::knn", mutates_args=(), device_types="cuda")
+def knn(Q: torch.Tensor, R: torch.Tensor, k: int, exclude_self: bool = False,
+        parts: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """the k rows of R [nr, D] nearest each row of Q [nq, D] by the key (fp64 squared distance, index), ascending ->
+    (idx [nq, k] int32, d2 [nq, k] fp64); the same bits for every ``parts`` (csrc/neighbors.hip)"""
+    return _o().knn(Q, R, k, exclude_self, parts)
+
+
+@knn.register_fake
+def _(Q, R, k, exclude_self=False, parts=0):
+    nq = Q.shape[0]
+    return Q.new_empty(nq, k, dtype=torch.int32), Q.new_empty(nq, k, dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::knn_average", mutates_args=(), device_types="cuda")
+def knn_average(idx: torch.Tensor, d2: Optional[torch.Tensor], Y: torch.Tensor, weights: str = "uniform") -> torch.Tensor:
+    """the NaN-skipping weighted average of Y's rows idx [nq, k] -> [nq, P] fp32 (fp64 for an fp64 Y); weights "uniform"
+    or "distance" (csrc/neighbors.hip)"""
+    return _o().knn_average(idx, d2, Y, weights)
+
+
+@knn_average.register_fake
+def _(idx, d2, Y, weights="uniform"):
+    return Y.new_empty(idx.shape[0], Y.shape[1], dtype=torch.float64 if Y.dtype == torch.float64 else torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------
