@@ -5,6 +5,8 @@ import ctypes as C
 import pytest
 import torch
 
+from fp64_products_util import LONGK_SHAPES
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 f64, f32 = torch.float64, torch.float32
@@ -173,8 +175,7 @@ def _longk(hip, G, Bm, d, sym, alpha, beta, out):
     return rc, wsb
 
 
-@pytest.mark.parametrize("M,K,n", [(200, 100000, 1), (200, 10048, 2), (25, 1000, 3), (100, 4098, 2), (256, 2048, 1),
-                                   (200, 1282, 6), (50, 20000, 4)])
+@pytest.mark.parametrize("M,K,n", LONGK_SHAPES)
 @pytest.mark.parametrize("mode", ["G+dB/f32", "G+dB/f64", "dB/sym", "G"])
 def test_longk_f64(hip, M, K, n, mode):
     """out = beta out + alpha (G + d o B) B^T, nprob long-K fp64 products in one launch, left operand formed in registers;
@@ -187,9 +188,9 @@ def test_longk_f64(hip, M, K, n, mode):
     out = [o.clone() for o in out0]
     alpha, beta = [(-1.0) ** i * (1.0 + 0.5 * i) for i in range(n)], [float(i % 2) for i in range(n)]
     rc, wsb = _longk(hip, G, Bm, d, mode == "dB/sym", alpha, beta, out)
-    if wsb == 0:
-        assert rc != 0  # not covered: the caller keeps its generic path
-        pytest.skip("shape not covered by the long-K kernel")
+    # every listed shape is one the kernel takes (tests/test_fp64_products_shapes.py holds the list to that without a
+    # GPU; the declined shapes have a test of their own in tests/test_fp64_products_gpu.py)
+    assert wsb > 0, (M, K, n)
     assert rc == 0
     for i in range(n):
         A = (G[i] if G is not None else 0.0) + (d[i].double()[None, :] * Bm[i] if d is not None else 0.0)
