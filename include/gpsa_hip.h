@@ -1095,6 +1095,43 @@ int gpsa_knn_average_f32(const int* idx, const double* d2, long long nq, int k, 
 int gpsa_knn_average_f64(const int* idx, const double* d2, long long nq, int k, const double* Y, long long nr, int P,
                          int weights, double* out, void* stream);
 
+/* ---- count preprocessing (csrc/counts.hip): margins, Poisson deviance, residual transforms, per-view z-score -------------
+ * Y [N, P] fp32, row-major, counts held as floats.  Every sum is fp64 in a fixed order, no atomics, nothing of N * P
+ * elements is allocated.  The three reductions take workspace >= gpsa_count_workspace(N, P) bytes (a pure host query:
+ * the column partials of at most 1024 row groups while a group stays <= 512 rows, about 16 * 1024 * P bytes).
+ * Common refusals, all before the first launch: GPSA_EINVAL for a NULL pointer, N < 1, P < 1, P >= 2^31, N > 16 (2^31 - 1)
+ * (the grids' extents);
+ * GPSA_EWORKSPACE for a NULL or short workspace.
+ * gpsa_count_margins_f32: ONE read of Y -> row_sum [N] fp64, col_sum [P] fp64, row_nnz [N] and col_nnz [P] int64 (entries
+ *   > 0), n_invalid (one int64 on the device): the entries that are NaN, +-inf or < 0.
+ * gpsa_count_deviance_f32: log_sz [N] fp64 -> ll_sat[g] = sum_i y log y - y log_sz_i and abs_sat[g] = sum_i |y log y| +
+ *   |y log_sz_i| (terms of y = 0 are 0), both [P] fp64.  The deviance 2 (ll_sat - col_sum log(col_sum / sum_i sz_i)) is
+ *   closed by the caller.
+ * gpsa_count_transform_f32: elementwise, fp64 arithmetic, rounded once to fp32; out [N, P] may be Y.  With
+ *   mu = row_sum_i col_sum_g / total (an entry with mu = 0 gives 0):
+ *     mode 0, Pearson:  z = (y - mu) / sqrt(mu + mu^2 / theta), clipped to +-clip when clip > 0   (theta = inf: Poisson)
+ *     mode 1, NB deviance residual: sign(y - mu) sqrt(max(0, 2 (y log(y / mu) - (y + theta) log((y + theta) / (mu + theta)))))
+ *     mode 2, Poisson deviance residual: sign(y - mu) sqrt(max(0, 2 (y log(y / mu) - (y - mu))))
+ *     mode 3: log1p(y target / row_sum_i), 0 in a row with row_sum = 0 (col_sum may be NULL)
+ *   Each mode reads only its own scalars.  GPSA_EINVAL also for an unknown mode, total or target not in (0, inf),
+ *   theta <= 0 or NaN (modes 0, 1), theta = inf in mode 1, clip < 0.
+ * gpsa_standardize_views_f32: out = (y - mean) / std per (view, column) over the consecutive row ranges
+ *   view_off [V + 1] (a HOST array, 0 = view_off[0] < ... < view_off[V] = N); std is the population value (ddof 0), the
+ *   moments are Welford updates joined by Chan's formula.  A column that is constant within a view is written as 0 and
+ *   counted in n_constant [V] (int64, device).  out may be Y.  GPSA_EINVAL also for V < 1, offsets that do not
+ *   partition [0, N) or an empty view. */
+long long gpsa_count_workspace(long long N, long long P);
+int gpsa_count_margins_f32(const float* Y, long long N, long long P, double* row_sum, double* col_sum, long long* row_nnz,
+                           long long* col_nnz, long long* n_invalid, void* workspace, long long workspace_bytes,
+                           void* stream);
+int gpsa_count_deviance_f32(const float* Y, long long N, long long P, const double* log_sz, double* ll_sat, double* abs_sat,
+                            void* workspace, long long workspace_bytes, void* stream);
+int gpsa_count_transform_f32(int mode, const float* Y, long long N, long long P, const double* row_sum,
+                             const double* col_sum, double total, double theta, double clip, double target, float* out,
+                             void* stream);
+int gpsa_standardize_views_f32(const float* Y, long long N, long long P, const long long* view_off, int V, float* out,
+                               long long* n_constant, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

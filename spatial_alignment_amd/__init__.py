@@ -2,6 +2,17 @@
 
 Same public names as the reference package (gpsa/__init__.py:1-10) for the parts on the hot path.
 """
+from .counts import (
+    count_stats,
+    deviance_feature_selection,
+    deviance_residuals,
+    normalize_log1p,
+    pearson_residuals,
+    poisson_deviance,
+    prepare_counts,
+    size_factors,
+    standardize_views,
+)
 from .kernels import matern12_kernel, matern32_kernel, rbf_kernel
 from .models import GPSA, VariationalGPSA
 from .neighbors import alignment_score, knn, knn_regress, kth_neighbor_distance, moran_i, spatial_r2
@@ -38,5 +49,14 @@ __all__ = [
     "kth_neighbor_distance",
     "moran_i",
     "alignment_score",
+    "count_stats",
+    "size_factors",
+    "poisson_deviance",
+    "deviance_feature_selection",
+    "pearson_residuals",
+    "deviance_residuals",
+    "normalize_log1p",
+    "standardize_views",
+    "prepare_counts",
 ]
 __version__ = "0.1.0"

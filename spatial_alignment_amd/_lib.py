@@ -231,6 +231,12 @@ SIGNATURES.update({
     "gpsa_knn_f64": (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_knn_average_f32": (_i, [_vp, _vp, _ll, _i, _vp, _ll, _i, _i, _vp, _vp]),
     "gpsa_knn_average_f64": (_i, [_vp, _vp, _ll, _i, _vp, _ll, _i, _i, _vp, _vp]),
+    # count preprocessing: margins, deviance, residual transforms, per-view z-score (csrc/counts.hip)
+    "gpsa_count_workspace": (_ll, [_ll, _ll]),
+    "gpsa_count_margins_f32": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_count_deviance_f32": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_count_transform_f32": (_i, [_i, _vp, _ll, _ll, _vp, _vp, _d, _d, _d, _d, _vp, _vp]),
+    "gpsa_standardize_views_f32": (_i, [_vp, _ll, _ll, C.POINTER(_ll), _i, _vp, _vp, _vp, _ll, _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

@@ -4,6 +4,7 @@ PyTorch is used here only as plumbing: it owns device memory (torch.empty), the 
 (torch.cuda.current_stream) and autograd bookkeeping.  Every numerical kernel below is a
 hand-written HIP kernel in csrc/, reached through ctypes with raw device pointers.
 """
+import ctypes as C
 import os
 
 import torch
@@ -665,6 +666,89 @@ class HipOps:
         rc = getattr(self.lib, name)(_p(idx), _p(d2), nq, k, _p(Y), nr, P, wcode, _p(out), self._stream(Y))
         _lib.check(rc, name)
         return out
+
+    # ------------------------------------------------------------------ count preprocessing (csrc/counts.hip)
+    COUNT_MODES = {"pearson": 0, "nb_deviance": 1, "poisson_deviance": 2, "log1p": 3}
+
+    @staticmethod
+    def _count_matrix(Y, what):
+        if Y.dim() != 2 or Y.shape[0] < 1 or Y.shape[1] < 1 or Y.dtype != torch.float32 or not Y.is_contiguous():
+            raise ValueError(f"{what}: Y must be a contiguous fp32 [N >= 1, P >= 1], not {Y.dtype} {tuple(Y.shape)}")
+        return int(Y.shape[0]), int(Y.shape[1])
+
+    @staticmethod
+    def _count_out(out, N, P, what):
+        if tuple(out.shape) != (N, P) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous fp32 [{N}, {P}], not {out.dtype} {tuple(out.shape)}")
+
+    def _count_ws(self, N, P, like):
+        nbytes = self._wsq("gpsa_count_workspace", N, P)
+        return self._ws(nbytes, like), nbytes
+
+    def count_margins(self, Y):
+        """gpsa_count_margins_f32: one read of Y [N, P] fp32 -> (row_sum [N] fp64, col_sum [P] fp64, row_nnz [N] int64,
+        col_nnz [P] int64, n_invalid [1] int64 on the device: the entries that are NaN, +-inf or < 0)"""
+        N, P = self._count_matrix(Y, "count_margins")
+        dev = Y.device
+        rs, cs = torch.empty(N, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev)
+        rn, cn = torch.empty(N, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.int64, device=dev)
+        bad = torch.empty(1, dtype=torch.int64, device=dev)
+        ws, nbytes = self._count_ws(N, P, Y)
+        rc = self.lib.gpsa_count_margins_f32(_p(Y), N, P, _p(rs), _p(cs), _p(rn), _p(cn), _p(bad), _p(ws), nbytes,
+                                             self._stream(Y))
+        _lib.check(rc, "gpsa_count_margins_f32")
+        return rs, cs, rn, cn, bad
+
+    def count_deviance(self, Y, log_sz):
+        """gpsa_count_deviance_f32: (ll_sat, abs_sat) [P] fp64 with ll_sat[g] = sum_i y log y - y log_sz_i and
+        abs_sat[g] = sum_i |y log y| + |y log_sz_i|; log_sz [N] fp64"""
+        N, P = self._count_matrix(Y, "count_deviance")
+        if log_sz.dim() != 1 or log_sz.shape[0] != N:
+            raise ValueError(f"count_deviance: log_sz has shape {tuple(log_sz.shape)}, [{N}] is needed")
+        log_sz = self._f64(log_sz)
+        ll, ab = (torch.empty(P, dtype=torch.float64, device=Y.device) for _ in range(2))
+        ws, nbytes = self._count_ws(N, P, Y)
+        rc = self.lib.gpsa_count_deviance_f32(_p(Y), N, P, _p(log_sz), _p(ll), _p(ab), _p(ws), nbytes, self._stream(Y))
+        _lib.check(rc, "gpsa_count_deviance_f32")
+        return ll, ab
+
+    def count_transform(self, Y, mode, row_sum, col_sum=None, total=1.0, theta=1.0, clip=0.0, target=1.0, out=None):
+        """gpsa_count_transform_f32: ``mode`` "pearson" | "nb_deviance" | "poisson_deviance" | "log1p", elementwise in
+        fp64, rounded once to fp32 -> [N, P] fp32.  ``out`` may be Y itself."""
+        N, P = self._count_matrix(Y, "count_transform")
+        if mode not in self.COUNT_MODES:
+            raise ValueError(f"count_transform: mode must be one of {sorted(self.COUNT_MODES)}, not {mode!r}")
+        if row_sum.dim() != 1 or row_sum.shape[0] != N:
+            raise ValueError(f"count_transform: row_sum has shape {tuple(row_sum.shape)}, [{N}] is needed")
+        if mode != "log1p" and (col_sum is None or col_sum.dim() != 1 or col_sum.shape[0] != P):
+            raise ValueError(f"count_transform: col_sum must be [{P}] for mode {mode!r}")
+        row_sum = self._f64(row_sum)
+        col_sum = None if mode == "log1p" else self._f64(col_sum)
+        if out is None:
+            out = torch.empty_like(Y)
+        self._count_out(out, N, P, "count_transform")
+        rc = self.lib.gpsa_count_transform_f32(self.COUNT_MODES[mode], _p(Y), N, P, _p(row_sum), _p(col_sum), float(total),
+                                               float(theta), float(clip), float(target), _p(out), self._stream(Y))
+        _lib.check(rc, "gpsa_count_transform_f32")
+        return out
+
+    def standardize_views(self, Y, view_off, out=None):
+        """gpsa_standardize_views_f32: (y - mean) / std per (view, column) over the row ranges view_off (a list of V + 1
+        ints, 0 ... N) -> (out [N, P] fp32, n_constant [V] int64 on the device); a column constant within a view: 0"""
+        N, P = self._count_matrix(Y, "standardize_views")
+        off = [int(v) for v in view_off]
+        V = len(off) - 1
+        if V < 1 or off[0] != 0 or off[-1] != N or any(b <= a for a, b in zip(off, off[1:])):
+            raise ValueError(f"standardize_views: view_off {off} must rise strictly from 0 to N = {N}")
+        if out is None:
+            out = torch.empty_like(Y)
+        self._count_out(out, N, P, "standardize_views")
+        nconst = torch.empty(V, dtype=torch.int64, device=Y.device)
+        ws, nbytes = self._count_ws(N, P, Y)
+        rc = self.lib.gpsa_standardize_views_f32(_p(Y), N, P, (C.c_longlong * (V + 1))(*off), V, _p(out), _p(nconst),
+                                                 _p(ws), nbytes, self._stream(Y))
+        _lib.check(rc, "gpsa_standardize_views_f32")
+        return out, nconst
 
     @staticmethod
     def _f64(t):

@@ -20,6 +20,8 @@ each with
        ... closed as counts (prediction)    gpsa::predict_counts                       (predict.py, scale="response")
        the warp as a function of the point  gpsa::warp_field, gpsa::warp_invert        (warp.py; csrc/warp_field.hip)
        neighbour statistics                 gpsa::knn, gpsa::knn_average               (neighbors.py; csrc/neighbors.hip)
+       count preprocessing                  gpsa::count_margins, gpsa::count_deviance, (counts.py; csrc/counts.hip)
+                                            gpsa::count_transform, gpsa::standardize_views
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
@@ -337,6 +339,60 @@ def knn_average(idx: torch.Tensor, d2: Optional[torch.Tensor], Y: torch.Tensor, 
 @knn_average.register_fake
 def _(idx, d2, Y, weights="uniform"):
     return Y.new_empty(idx.shape[0], Y.shape[1], dtype=torch.float64 if Y.dtype == torch.float64 else torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# (4f) count preprocessing: margins, Poisson deviance, residual transforms, per-view z-score (counts.py)
+# ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("gpsa::count_margins", mutates_args=(), device_types="cuda")
+def count_margins(Y: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """one read of Y [N, P] fp32 -> (row_sum [N] fp64, col_sum [P] fp64, row_nnz [N] int64, col_nnz [P] int64,
+    n_invalid [1] int64) (csrc/counts.hip)"""
+    return _o().count_margins(Y)
+
+
+@count_margins.register_fake
+def _(Y):
+    N, P = Y.shape
+    return (Y.new_empty(N, dtype=torch.float64), Y.new_empty(P, dtype=torch.float64), Y.new_empty(N, dtype=torch.int64),
+            Y.new_empty(P, dtype=torch.int64), Y.new_empty(1, dtype=torch.int64))
+
+
+@torch.library.custom_op("gpsa::count_deviance", mutates_args=(), device_types="cuda")
+def count_deviance(Y: torch.Tensor, log_sz: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(ll_sat, abs_sat) [P] fp64: sum_i y log y - y log_sz_i and the sum of the terms' magnitudes (csrc/counts.hip)"""
+    return _o().count_deviance(Y, log_sz)
+
+
+@count_deviance.register_fake
+def _(Y, log_sz):
+    P = Y.shape[1]
+    return Y.new_empty(P, dtype=torch.float64), Y.new_empty(P, dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::count_transform", mutates_args=(), device_types="cuda")
+def count_transform(Y: torch.Tensor, mode: str, row_sum: torch.Tensor, col_sum: Optional[torch.Tensor] = None,
+                    total: float = 1.0, theta: float = 1.0, clip: float = 0.0, target: float = 1.0) -> torch.Tensor:
+    """"pearson" | "nb_deviance" | "poisson_deviance" | "log1p" of Y [N, P] fp32, fp64 per element -> [N, P] fp32
+    (csrc/counts.hip; the in-place form is ops.count_transform(..., out=Y))"""
+    return _o().count_transform(Y, mode, row_sum, col_sum, total, theta, clip, target)
+
+
+@count_transform.register_fake
+def _(Y, mode, row_sum, col_sum=None, total=1.0, theta=1.0, clip=0.0, target=1.0):
+    return Y.new_empty(Y.shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("gpsa::standardize_views", mutates_args=(), device_types="cuda")
+def standardize_views(Y: torch.Tensor, view_off: list[int]) -> tuple[torch.Tensor, torch.Tensor]:
+    """(y - mean) / std per (view, column) over the row ranges view_off [V + 1] -> ([N, P] fp32, n_constant [V] int64)
+    (csrc/counts.hip)"""
+    return _o().standardize_views(Y, view_off)
+
+
+@standardize_views.register_fake
+def _(Y, view_off):
+    return Y.new_empty(Y.shape, dtype=torch.float32), Y.new_empty(len(view_off) - 1, dtype=torch.int64)
 
 
 # ---------------------------------------------------------------------------------------------------------

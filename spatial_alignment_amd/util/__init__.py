@@ -2,7 +2,12 @@ from .util import (  # noqa: F401
     ConvergenceChecker,
     LossNotDecreasingChecker,
     compute_distance,
+    compute_size_factors,
+    deviance_feature_selection,
+    deviance_residuals,
     get_st_coordinates,
+    pearson_residuals,
+    poisson_deviance,
     polar_warp,
     rbf_kernel_numpy,
 )
