@@ -1132,6 +1132,39 @@ int gpsa_count_transform_f32(int mode, const float* Y, long long N, long long P,
 int gpsa_standardize_views_f32(const float* Y, long long N, long long P, const long long* view_off, int V, float* out,
                                long long* n_constant, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- exact GP regression (csrc/gpr.hip): sklearn's GaussianProcessRegressor with [C *] k + WhiteKernel ------------------
+ * What the reference's experiments fit on the CPU around GPSA: the prediction baselines
+ * (experiments/simulations/two_dimensional_prediction.py:126-155, 238, one_dimensional_prediction.py:128-139,
+ * expression/st/st_prediction.py:142-156, 251) and the data kernel's starting length scale (two_dimensional.py:84-91).
+ * All fp64.  K(theta) = a k(X, X; l) + (tau2 + jitter) I with theta = (log a, log l, log tau2), three doubles on the
+ * DEVICE; a = 1 (theta[0] is not read for it) unless amplitude != 0, sklearn's ConstantKernel() * k.  kind: GPSA_K_*, in
+ * sklearn's forms: rbf exp(-d^2 / (2 l^2)); matern32 (1 + r) exp(-r), r = sqrt(3) d / l; matern12 exp(-d / l).  D <= 4.
+ * gpsa_gpr_cov_f64: K [na, nb] = a k(XA, XB)  (kernel(X) / kernel(X*, X) of GaussianProcessRegressor.fit / .predict).
+ *   same != 0 (XA and XB are the same array, na == nb): the diagonal gets (a + tau2) + jitter, every off-diagonal 64 x 64
+ *   tile is computed once and written to both places - K is symmetric to the bit.
+ * gpsa_gpr_lml_grad_f64: out[0..2] = dLML / d(log a, log l, log tau2) = 1/2 sum_ij W_ij dK_ij / dtheta, W = alpha alpha^T -
+ *   P Kinv  (log_marginal_likelihood(theta, eval_gradient=True)'s einsum over the K_gradient cube).  X [N, D], alpha =
+ *   K^-1 Y [N, P], Kinv [N, N].  Per tile (I, J <= I) of the pair grid alpha_I alpha_J^T runs on v_mfma_f64_16x16x4_f64
+ *   (P zero-padded to a multiple of 4 in registers), k and dk / dlog l come from X_I, X_J on the fly, off-diagonal tiles
+ *   count twice; the tau2 entry is 1/2 tau2 (sum_i |alpha_i|^2 - P tr Kinv) from the diagonal tiles.  out[0] is written
+ *   with a = 1 when amplitude == 0.  Nothing of N x N is written; no atomics: per-workgroup partials in the workspace
+ *   (>= gpsa_gpr_lml_grad_workspace(N, P) bytes, a pure host query) are added in a fixed order by a second launch, so
+ *   a repeated call gives the same bits.
+ * gpsa_gpr_mean_f64: out [ns, P] = a k(XS, X) alpha  (GaussianProcessRegressor.predict's K_trans @ alpha_).  The kernel
+ *   tile is generated straight into the MFMA's A operand: no [ns, N] matrix exists.  The sum over the training rows runs
+ *   in one fixed order that does not depend on which rows of XS are passed together.
+ * GPSA_EINVAL: a NULL pointer, a size < 1, an unknown kind, jitter < 0 or NaN, same != 0 with XA != XB or na != nb;
+ * GPSA_EUNSUPPORTED: D > 4, a grid extent (N > 65535 * 64 rows in gpsa_gpr_lml_grad_f64 / gpsa_gpr_cov_f64's na);
+ * GPSA_EWORKSPACE.  Every check runs before the first launch. */
+int gpsa_gpr_cov_f64(int kind, const double* XA, long long na, const double* XB, long long nb, int D, const double* theta,
+                     int amplitude, int same, double jitter, double* K, void* stream);
+long long gpsa_gpr_lml_grad_workspace(long long N, int P);
+int gpsa_gpr_lml_grad_f64(int kind, const double* X, long long N, int D, const double* theta, int amplitude,
+                          const double* alpha, int P, const double* Kinv, double* out, void* workspace,
+                          long long workspace_bytes, void* stream);
+int gpsa_gpr_mean_f64(int kind, const double* XS, long long ns, const double* X, long long N, int D, const double* theta,
+                      int amplitude, const double* alpha, int P, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from .counts import (
     size_factors,
     standardize_views,
 )
+from .gpr import GPRegression, gp_regress, prediction_baselines
 from .kernels import matern12_kernel, matern32_kernel, rbf_kernel
 from .models import GPSA, VariationalGPSA
 from .neighbors import alignment_score, knn, knn_regress, kth_neighbor_distance, moran_i, spatial_r2
@@ -58,5 +59,8 @@ __all__ = [
     "normalize_log1p",
     "standardize_views",
     "prepare_counts",
+    "gp_regress",
+    "GPRegression",
+    "prediction_baselines",
 ]
 __version__ = "0.1.0"

@@ -237,6 +237,11 @@ SIGNATURES.update({
     "gpsa_count_deviance_f32": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_count_transform_f32": (_i, [_i, _vp, _ll, _ll, _vp, _vp, _d, _d, _d, _d, _vp, _vp]),
     "gpsa_standardize_views_f32": (_i, [_vp, _ll, _ll, C.POINTER(_ll), _i, _vp, _vp, _vp, _ll, _vp]),
+    # exact GP regression: covariance assembly, the LML gradient's fused reduction, the fused predictive mean (csrc/gpr.hip)
+    "gpsa_gpr_cov_f64": (_i, [_i, _vp, _ll, _vp, _ll, _i, _vp, _i, _i, _d, _vp, _vp]),
+    "gpsa_gpr_lml_grad_workspace": (_ll, [_ll, _i]),
+    "gpsa_gpr_lml_grad_f64": (_i, [_i, _vp, _ll, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_gpr_mean_f64": (_i, [_i, _vp, _ll, _vp, _ll, _i, _vp, _i, _vp, _i, _vp, _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

@@ -667,8 +667,95 @@ class HipOps:
         _lib.check(rc, name)
         return out
 
+    # ------------------------------------------------------------------ exact GP regression (csrc/gpr.hip)
+    def _gpr_args(self, what, kind, theta, *coords):
+        """-> (kind code, theta, D) after the checks the three gpr entries share: the kernel's name, theta = three fp64
+        values on the device, coordinates fp64 [n >= 1, D] with one D in 1 .. 4"""
+        if kind not in KINDS:
+            raise ValueError(f"{what}: kernel must be one of {sorted(KINDS)}, not {kind!r}")
+        if theta.dim() != 1 or theta.shape[0] != 3 or theta.dtype != torch.float64 or not theta.is_contiguous():
+            raise ValueError(f"{what}: theta must be a contiguous fp64 [3] (log a, log l, log tau2), not {theta.dtype} "
+                             f"{tuple(theta.shape)}")
+        D = int(coords[0].shape[1]) if coords[0].dim() == 2 else 0
+        for X in coords:
+            if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] != D or X.dtype != torch.float64 or not X.is_contiguous():
+                raise ValueError(f"{what}: coordinates must be contiguous fp64 [n >= 1, D] with one D, not {X.dtype} "
+                                 f"{tuple(X.shape)}")
+        if D < 1 or D > 4:
+            raise ValueError(f"{what}: D = {D}; 1 to 4 coordinates are supported")
+        return KINDS[kind], theta, D
+
+    def gpr_cov(self, kind, XA, XB, theta, amplitude=False, same=False, jitter=0.0, out=None):
+        """gpsa_gpr_cov_f64: K [na, nb] = a k(XA, XB) in sklearn's kernel forms, fp64; ``same`` (XB is XA): plus
+        (tau2 + jitter) on the diagonal, exactly symmetric.  theta [3] fp64 on the device: log a, log l, log tau2."""
+        kd, theta, D = self._gpr_args("gpr_cov", kind, theta, XA, XB)
+        na, nb = int(XA.shape[0]), int(XB.shape[0])
+        if same and (XA.data_ptr() != XB.data_ptr() or na != nb):
+            raise ValueError("gpr_cov: same=True takes one array as XA and XB")
+        if out is None:
+            out = torch.empty(na, nb, dtype=torch.float64, device=XA.device)
+        assert tuple(out.shape) == (na, nb) and out.dtype == torch.float64 and out.is_contiguous(), (na, nb)
+        rc = self.lib.gpsa_gpr_cov_f64(kd, _p(XA), na, _p(XB), nb, D, _p(theta), int(bool(amplitude)), int(bool(same)),
+                                       float(jitter), _p(out), self._stream(XA))
+        _lib.check(rc, "gpsa_gpr_cov_f64")
+        return out
+
+    def gpr_lml_grad(self, kind, X, theta, alpha, Kinv, amplitude=False, out=None):
+        """gpsa_gpr_lml_grad_f64: dLML / d(log a, log l, log tau2) [3] fp64 from X [N, D], alpha = K^-1 Y [N, P] and
+        Kinv [N, N]: 1/2 sum_ij (alpha alpha^T - P Kinv)_ij dK_ij, fused (nothing of N x N is written), fixed order."""
+        kd, theta, D = self._gpr_args("gpr_lml_grad", kind, theta, X)
+        N = int(X.shape[0])
+        for t, name, sh in ((alpha, "alpha", (N, None)), (Kinv, "Kinv", (N, N))):
+            if t.dim() != 2 or t.shape[0] != sh[0] or (sh[1] is not None and t.shape[1] != sh[1]) or t.shape[1] < 1 \
+                    or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError(f"gpr_lml_grad: {name} must be a contiguous fp64 [{N}, {sh[1] or 'P >= 1'}], not {t.dtype} "
+                                 f"{tuple(t.shape)}")
+        P = int(alpha.shape[1])
+        if out is None:
+            out = torch.empty(3, dtype=torch.float64, device=X.device)
+        assert tuple(out.shape) == (3,) and out.dtype == torch.float64 and out.is_contiguous()
+        nbytes = self._wsq("gpsa_gpr_lml_grad_workspace", N, P)
+        ws = self._ws(nbytes, X)
+        rc = self.lib.gpsa_gpr_lml_grad_f64(kd, _p(X), N, D, _p(theta), int(bool(amplitude)), _p(alpha), P, _p(Kinv),
+                                            _p(out), _p(ws), nbytes, self._stream(X))
+        _lib.check(rc, "gpsa_gpr_lml_grad_f64")
+        return out
+
+    def gpr_mean(self, kind, XS, X, theta, alpha, amplitude=False, out=None):
+        """gpsa_gpr_mean_f64: [ns, P] = a k(XS, X) alpha, fp64, the kernel tile generated into the MFMA operand (no
+        [ns, N] matrix); a row's result does not depend on the rows passed with it."""
+        kd, theta, D = self._gpr_args("gpr_mean", kind, theta, XS, X)
+        ns, N = int(XS.shape[0]), int(X.shape[0])
+        if alpha.dim() != 2 or alpha.shape[0] != N or alpha.shape[1] < 1 or alpha.dtype != torch.float64 \
+                or not alpha.is_contiguous():
+            raise ValueError(f"gpr_mean: alpha must be a contiguous fp64 [{N}, P >= 1], not {alpha.dtype} "
+                             f"{tuple(alpha.shape)}")
+        P = int(alpha.shape[1])
+        if out is None:
+            out = torch.empty(ns, P, dtype=torch.float64, device=XS.device)
+        assert tuple(out.shape) == (ns, P) and out.dtype == torch.float64 and out.is_contiguous(), (ns, P)
+        rc = self.lib.gpsa_gpr_mean_f64(kd, _p(XS), ns, _p(X), N, D, _p(theta), int(bool(amplitude)), _p(alpha), P,
+                                        _p(out), self._stream(XS))
+        _lib.check(rc, "gpsa_gpr_mean_f64")
+        return out
+
+    def chol_inv_blocked(self, A):
+        """gpsa_chol_inv_blocked_f64 for ONE matrix A [N, N] fp64 of any size (not modified) -> L^-1 [N, N] (upper part
+        zero), logdet [1] = log det A, info [1] int32 (0, or the 1-based column where the factorisation broke down)"""
+        A = self._c(A)
+        N = int(A.shape[-1])
+        Linv = torch.empty_like(A)
+        logdet = torch.empty(1, dtype=torch.float64, device=A.device)
+        info = torch.empty(1, dtype=torch.int32, device=A.device)
+        nbytes = self._wsq("gpsa_chol_inv_blocked_workspace", N, 1)
+        ws = self._ws(nbytes, A)
+        rc = self.lib.gpsa_chol_inv_blocked_f64(_p(A), _p(Linv), N, 1, _p(logdet), _p(info), _p(ws), ws.numel(),
+                                                self._stream(A))
+        _lib.check(rc, "gpsa_chol_inv_blocked_f64")
+        return Linv, logdet, info
+
     # ------------------------------------------------------------------ count preprocessing (csrc/counts.hip)
-    COUNT_MODES = {"pearson": 0, "nb_deviance": 1, "poisson_deviance": 2, "log1p": 3}
+    COUNT_MODES ={"pearson": 0, "nb_deviance": 1, "poisson_deviance": 2, "log1p": 3}
 
     @staticmethod
     def _count_matrix(Y, what):

@@ -22,6 +22,8 @@ each with
        neighbour statistics                 gpsa::knn, gpsa::knn_average               (neighbors.py; csrc/neighbors.hip)
        count preprocessing                  gpsa::count_margins, gpsa::count_deviance, (counts.py; csrc/counts.hip)
                                             gpsa::count_transform, gpsa::standardize_views
+       exact GP regression                  gpsa::gpr_cov, gpsa::gpr_lml_grad,         (gpr.py; csrc/gpr.hip)
+                                            gpsa::gpr_mean
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
@@ -393,6 +395,47 @@ def standardize_views(Y: torch.Tensor, view_off: list[int]) -> tuple[torch.Tenso
 @standardize_views.register_fake
 def _(Y, view_off):
     return Y.new_empty(Y.shape, dtype=torch.float32), Y.new_empty(len(view_off) - 1, dtype=torch.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# (4g) exact GP regression: covariance assembly, the LML gradient's reduction, the predictive mean (gpr.py)
+# ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("gpsa::gpr_cov", mutates_args=(), device_types="cuda")
+def gpr_cov(XA: torch.Tensor, XB: torch.Tensor, theta: torch.Tensor, kind: str, amplitude: bool = False,
+            same: bool = False, jitter: float = 0.0) -> torch.Tensor:
+    """K [na, nb] = a k(XA, XB) in sklearn's kernel forms, fp64; theta [3] = (log a, log l, log tau2) on the device;
+    ``same``: XB is XA, (tau2 + jitter) on the diagonal, symmetric to the bit (csrc/gpr.hip)"""
+    return _o().gpr_cov(kind, XA, XA if same else XB, theta, amplitude, same, jitter)
+
+
+@gpr_cov.register_fake
+def _(XA, XB, theta, kind, amplitude=False, same=False, jitter=0.0):
+    return XA.new_empty(XA.shape[0], XB.shape[0], dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::gpr_lml_grad", mutates_args=(), device_types="cuda")
+def gpr_lml_grad(X: torch.Tensor, theta: torch.Tensor, alpha: torch.Tensor, Kinv: torch.Tensor, kind: str,
+                 amplitude: bool = False) -> torch.Tensor:
+    """dLML / d(log a, log l, log tau2) [3] fp64 = 1/2 sum_ij (alpha alpha^T - P Kinv)_ij dK_ij, fused, in a fixed order
+    (csrc/gpr.hip)"""
+    return _o().gpr_lml_grad(kind, X, theta, alpha, Kinv, amplitude)
+
+
+@gpr_lml_grad.register_fake
+def _(X, theta, alpha, Kinv, kind, amplitude=False):
+    return X.new_empty(3, dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::gpr_mean", mutates_args=(), device_types="cuda")
+def gpr_mean(XS: torch.Tensor, X: torch.Tensor, theta: torch.Tensor, alpha: torch.Tensor, kind: str,
+             amplitude: bool = False) -> torch.Tensor:
+    """[ns, P] = a k(XS, X) alpha, fp64, without the [ns, N] matrix (csrc/gpr.hip)"""
+    return _o().gpr_mean(kind, XS, X, theta, alpha, amplitude)
+
+
+@gpr_mean.register_fake
+def _(XS, X, theta, alpha, kind, amplitude=False):
+    return XS.new_empty(XS.shape[0], alpha.shape[1], dtype=torch.float64)
 
 
 # ---------------------------------------------------------------------------------------------------------
