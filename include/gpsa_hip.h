@@ -1132,6 +1132,46 @@ int gpsa_count_transform_f32(int mode, const float* Y, long long N, long long P,
 int gpsa_standardize_views_f32(const float* Y, long long N, long long P, const long long* view_off, int V, float* out,
                                long long* n_constant, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- count preprocessing from a sparse matrix (csrc/counts_sparse.hip): check, margins, deviance, gather ----------------
+ * The matrix is CSR on the device: crow [N + 1] int64, col [nnz] int32, val [nnz] fp32 (all device pointers; col and val
+ * may be NULL when nnz == 0).  The same rules as above: fp64 sums in a fixed order, no atomics, one writer per output
+ * element, the same bits on a repeated call.  Integer counts give the dense entries' results bit for bit; other values
+ * agree to rounding.  keep [N] uint8 (device) or NULL: a row with keep == 0 is skipped by the two reductions as if absent.
+ * gpsa_csr_check and the two reductions take workspace >= gpsa_count_csr_workspace(N, P) bytes (a pure host query, 0 for
+ * N < 1 or P < 1: the column partials of at most 32 row groups, the row partials of the P / 512 column tiles; it does
+ * not depend on nnz).
+ * Refusals, all before the first launch and with nothing written: GPSA_EINVAL for a NULL pointer (keep excepted), N < 1,
+ * P < 1, N or P >= 2^31, nnz < 0, nnz > N * P, nnz > 0 with a NULL col or val, n_rows < 1, G < 1 or G > P;
+ * GPSA_EWORKSPACE for a NULL or short workspace.
+ * gpsa_csr_check: out [4] int64 on the device = the number of crow violations (crow[0] != 0, a decrease, crow[N] != nnz);
+ *   of column indices outside [0, P); of places inside a row where the column index does not strictly increase (unsorted
+ *   rows and duplicates); of stored values equal to 0 (information, not an error).  Every read is bounded by
+ *   construction: crow over [0, N], col and val flat over [0, nnz), the per-row pass over row bounds clamped to [0, nnz].
+ * gpsa_count_margins_csr_f32: ONE read of the matrix -> row_sum [N], col_sum [P] fp64, row_nnz [N], col_nnz [P] int64 (the
+ *   stored entries > 0: a stored 0 does not count), n_invalid (one int64): the stored values that are NaN, +-inf or < 0.
+ *   A row masked out has row_sum = 0, row_nnz = 0 and contributes to no column.
+ * gpsa_count_deviance_csr_f32: log_sz [N] fp64 indexed by the original row -> ll_sat, abs_sat [P] as defined for
+ *   gpsa_count_deviance_f32; the caller closes the deviance.
+ * gpsa_csr_gather_dense_f32: out [n_rows, G] fp32 row-major, out[j, slot[g]] = the value stored at (rows[j], g) for every
+ *   gene g with slot[g] in [0, G) (slot [P] int32, -1: dropped; rows [n_rows] int64), 0 where nothing is stored.  A row is
+ *   assembled in LDS and stored coalesced: each element of out is written exactly once.
+ * Defence in depth: the three compute entries do not rely on the check.  They clamp every row range to [0, nnz] and skip
+ * a column index outside [0, P), a slot outside [0, G) and a row outside [0, N) (written as zeros), so a malformed matrix
+ * gives wrong sums but is never followed outside its buffers. */
+long long gpsa_count_csr_workspace(long long N, long long P);
+int gpsa_csr_check(const long long* crow, const int* col, const float* val, long long N, long long P, long long nnz,
+                   long long* out, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_count_margins_csr_f32(const long long* crow, const int* col, const float* val, const unsigned char* keep,
+                               long long N, long long P, long long nnz, double* row_sum, double* col_sum,
+                               long long* row_nnz, long long* col_nnz, long long* n_invalid, void* workspace,
+                               long long workspace_bytes, void* stream);
+int gpsa_count_deviance_csr_f32(const long long* crow, const int* col, const float* val, const unsigned char* keep,
+                                long long N, long long P, long long nnz, const double* log_sz, double* ll_sat,
+                                double* abs_sat, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_csr_gather_dense_f32(const long long* crow, const int* col, const float* val, long long N, long long P,
+                              long long nnz, const long long* rows, long long n_rows, const int* slot, long long G,
+                              float* out, void* stream);
+
 /* ---- exact GP regression (csrc/gpr.hip): sklearn's GaussianProcessRegressor with [C *] k + WhiteKernel ------------------
  * What the reference's experiments fit on the CPU around GPSA: the prediction baselines
  * (experiments/simulations/two_dimensional_prediction.py:126-155, 238, one_dimensional_prediction.py:128-139,

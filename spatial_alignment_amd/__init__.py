@@ -3,7 +3,10 @@
 Same public names as the reference package (gpsa/__init__.py:1-10) for the parts on the hot path.
 """
 from .counts import (
+    CSRCounts,
     count_stats,
+    csr_counts,
+    densify,
     deviance_feature_selection,
     deviance_residuals,
     normalize_log1p,
@@ -59,6 +62,9 @@ __all__ = [
     "normalize_log1p",
     "standardize_views",
     "prepare_counts",
+    "csr_counts",
+    "CSRCounts",
+    "densify",
     "gp_regress",
     "GPRegression",
     "prediction_baselines",

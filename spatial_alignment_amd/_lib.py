@@ -237,6 +237,12 @@ SIGNATURES.update({
     "gpsa_count_deviance_f32": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_count_transform_f32": (_i, [_i, _vp, _ll, _ll, _vp, _vp, _d, _d, _d, _d, _vp, _vp]),
     "gpsa_standardize_views_f32": (_i, [_vp, _ll, _ll, C.POINTER(_ll), _i, _vp, _vp, _vp, _ll, _vp]),
+    # ... from a CSR matrix on the device (csrc/counts_sparse.hip); crow / rows are DEVICE int64 arrays
+    "gpsa_count_csr_workspace": (_ll, [_ll, _ll]),
+    "gpsa_csr_check": (_i, [_vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _ll, _vp]),
+    "gpsa_count_margins_csr_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_count_deviance_csr_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_csr_gather_dense_f32": (_i, [_vp, _vp, _vp, _ll, _ll, _ll, _vp, _ll, _vp, _ll, _vp, _vp]),
     # exact GP regression: covariance assembly, the LML gradient's fused reduction, the fused predictive mean (csrc/gpr.hip)
     "gpsa_gpr_cov_f64": (_i, [_i, _vp, _ll, _vp, _ll, _i, _vp, _i, _i, _d, _vp, _vp]),
     "gpsa_gpr_lml_grad_workspace": (_ll, [_ll, _i]),

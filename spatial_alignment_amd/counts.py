@@ -11,7 +11,13 @@ to 2^24), every sum is fp64 in a fixed order, and nothing of N * P elements is a
 * ``count_stats``, ``size_factors``, ``poisson_deviance``, ``deviance_feature_selection``: the Poisson / NB route and the
   gene ranking;
 * ``pearson_residuals``, ``deviance_residuals``, ``normalize_log1p``, ``standardize_views``: the Gaussian route;
-* ``prepare_counts``: the one call, in the order the experiments use.
+* ``prepare_counts``: the one call, in the order the experiments use;
+* ``csr_counts`` / ``CSRCounts`` / ``densify``: sparse input (csrc/counts_sparse.hip).  ``count_stats``, ``size_factors``,
+  ``poisson_deviance``, ``deviance_feature_selection`` and ``prepare_counts`` take a ``CSRCounts`` or a ``torch.sparse_csr``
+  tensor where they take ``Y``, with the same return fields, and never build the dense [N, P] matrix: the margins and
+  the deviance are sums over the stored entries, the row filter is a mask, and only the selected block becomes dense.
+  Integer counts give the dense path's sums bit for bit; non-integer values agree to rounding.  The four calls whose
+  result is dense N x P refuse sparse input and point to ``prepare_counts`` / ``densify``.
 
 Deliberate departures from the reference: a gene with no counts has deviance exactly 0 (the reference drops it) and
 residual 0 (the reference divides 0 by 0); a column that is constant within a view standardises to 0 and is counted (the
@@ -29,6 +35,9 @@ f64, f32 = torch.float64, torch.float32
 # csrc/counts.hip: the rows of a group (at least / at most), the cap on the groups, the columns of a tile.  A matrix of
 # more than ROWS_MIN * MAX_GROUPS rows has more row blocks than the cap, and its groups grow.
 ROWS_MIN, ROWS_MAX, MAX_GROUPS, COL_TILE = 16, 512, 1024, 512
+# csrc/counts_sparse.hip: the rows of a group (at least), the cap on the groups, the columns of a tile, the output columns
+# the gather assembles at a time
+CSR_ROWS_MIN, CSR_MAX_GROUPS, CSR_COL_TILE, CSR_GATHER_TILE = 16, 32, 512, 8192
 TRANSFORMS = ("pearson", "deviance", "log1p", "counts")
 
 
@@ -113,7 +122,11 @@ def _log_size_factors(row_sum, what):
 
 
 def _deviance(o, Y, col_sum, log_sz):
-    ll_sat, abs_sat = o.count_deviance(Y, log_sz)
+    return _close_deviance(*o.count_deviance(Y, log_sz), col_sum, log_sz)
+
+
+def _close_deviance(ll_sat, abs_sat, col_sum, log_sz):
+    """2 (ll_sat - ll_null) from the entry's two sums; ``log_sz``: of the rows the sums ran over"""
     sum_sz = torch.exp(log_sz).sum()
     some = col_sum > 0
     ll_null = torch.where(some, col_sum * torch.log(torch.where(some, col_sum, torch.ones_like(col_sum)) / sum_sz),
@@ -163,6 +176,38 @@ def _offsets(ns):
     return off
 
 
+def _transform_selected(o, Ysel, fresh, margins, row_sum, log_sz, ns_kept, transform, theta, standardize, what):
+    """steps 4 and 5 of prepare_counts on the selected dense block ``Ysel`` (``fresh``: a copy of ours, transformed in
+    place).  ``margins()``: the margins of Ysel itself; ``row_sum``: of the kept rows over ALL genes
+    -> (outputs, log_offset, n_constant)"""
+    out_buf = Ysel if fresh else None  # in place on a copy of ours, never on the caller's matrix
+    log_offset, n_constant = None, None
+    if transform == "counts":
+        outputs, log_offset = (Ysel if fresh else Ysel.clone()), log_sz.to(f32)  # never the caller's own tensor
+    elif transform == "log1p":
+        outputs = o.count_transform(Ysel, "log1p", row_sum, target=_target(row_sum, None, what), out=out_buf)
+    else:
+        st_s = margins()
+        clip = math.sqrt(Ysel.shape[0])
+        try:
+            outputs = _residuals(o, Ysel, st_s, transform, theta, clip, out_buf)
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+    if transform != "counts" and standardize:
+        outputs, n_constant = o.standardize_views(outputs, _offsets(ns_kept), out=outputs)
+    return outputs, log_offset, n_constant
+
+
+def _view_counts(keep, ns, what):
+    """the rows each view keeps under the mask ``keep``; every view needs one"""
+    off = _offsets(ns)
+    kept = torch.cat([keep.new_zeros(1, dtype=torch.int64), torch.cumsum(keep.to(torch.int64), 0)])[off].tolist()
+    ns_kept = [b - a for a, b in zip(kept, kept[1:])]
+    if min(ns_kept) < 1:
+        raise ValueError(f"{what}: the row filter leaves {ns_kept} rows in the views: every view needs at least one")
+    return ns_kept
+
+
 def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize):
     what = "prepare_counts"
     N, P = (int(s) for s in Y.shape)
@@ -175,11 +220,7 @@ def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform
     if max_counts is not None:
         keep &= st.row_sum <= max_counts
     rows = torch.nonzero(keep).flatten()
-    off = _offsets(ns)
-    kept = torch.cat([keep.new_zeros(1, dtype=torch.int64), torch.cumsum(keep.to(torch.int64), 0)])[off].tolist()
-    ns_kept = [b - a for a, b in zip(kept, kept[1:])]
-    if min(ns_kept) < 1:
-        raise ValueError(f"{what}: the row filter leaves {ns_kept} rows in the views: every view needs at least one")
+    ns_kept = _view_counts(keep, ns, what)
     fresh = rows.numel() < N  # Yr is a copy of ours from here on
     Yr = Y[rows].contiguous() if fresh else Y
     # 2. genes, on the margins of the kept rows
@@ -198,25 +239,248 @@ def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform
         Ysel, fresh = Yr[:, genes].contiguous(), True
     else:
         Ysel = Yr
-    # 4. the transform
-    out_buf = Ysel if fresh else None  # in place on a copy of ours, never on the caller's matrix
-    log_offset, n_constant = None, None
-    if transform == "counts":
-        outputs, log_offset = (Ysel if fresh else Ysel.clone()), log_sz.to(f32)  # never the caller's own tensor
-    elif transform == "log1p":
-        outputs = o.count_transform(Ysel, "log1p", st_r.row_sum, target=_target(st_r.row_sum, None, what), out=out_buf)
-    else:
-        st_s = _stats(o, Ysel) if genes.numel() < P else st_r
-        clip = math.sqrt(Ysel.shape[0])
-        try:
-            outputs = _residuals(o, Ysel, st_s, transform, theta, clip, out_buf)
-        except ValueError as e:
-            raise ValueError(f"{what}: {e}") from None
-    # 5. the z-score per view
-    if transform != "counts" and standardize:
-        outputs, n_constant = o.standardize_views(outputs, _offsets(ns_kept), out=outputs)
+    # 4. the transform, 5. the z-score per view
+    margins = (lambda: _stats(o, Ysel)) if genes.numel() < P else (lambda: st_r)
+    outputs, log_offset, n_constant = _transform_selected(o, Ysel, fresh, margins, st_r.row_sum, log_sz, ns_kept, transform,
+                                                          theta, standardize, what)
     return Prediction(outputs=outputs, log_offset=log_offset, rows=rows, genes=genes, n_samples_list=ns_kept,
                       deviance=dev, n_constant=n_constant)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# sparse input: a CSR matrix on the device (csrc/counts_sparse.hip)
+# ------------------------------------------------------------------------------------------------------------------------
+class CSRCounts:
+    """A checked count matrix in CSR on the device, what ``csr_counts`` returns: ``crow`` [N + 1] int64, ``col`` [nnz]
+    int32 and ``values`` [nnz] fp32 (contiguous), ``shape`` (N, P), ``nnz`` and ``n_stored_zeros`` (the explicitly stored
+    zeros: allowed, they count as absent).  Rows are sorted by column and hold no duplicates.  Build it with
+    ``csr_counts``: the constructor itself checks nothing."""
+    __slots__ = ("crow", "col", "values", "shape", "nnz", "n_stored_zeros")
+
+    def __init__(self, crow, col, values, shape, n_stored_zeros=0):
+        self.crow, self.col, self.values = crow, col, values
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.nnz, self.n_stored_zeros = int(col.numel()), int(n_stored_zeros)
+
+    @property
+    def device(self):
+        return self.values.device
+
+    def __repr__(self):
+        return f"CSRCounts(shape={self.shape}, nnz={self.nnz}, n_stored_zeros={self.n_stored_zeros}, device={self.device})"
+
+
+def _is_scipy_sparse(m):
+    return type(m).__module__.startswith("scipy.sparse") and hasattr(m, "tocsr")
+
+
+def _is_sparse_tensor(Y):
+    return torch.is_tensor(Y) and Y.layout != torch.strided
+
+
+def _upload_device(device, what):
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: device {str(dev)!r}: the count kernels run on the GPU only and there is no host path")
+    return dev
+
+
+def _csr_parts(matrix, what):
+    """(crow, col, values, shape) of a torch.sparse_csr tensor or a 4-tuple, checked on the host: shapes, dtypes, one
+    device - before any device work"""
+    if _is_sparse_tensor(matrix):
+        if matrix.layout != torch.sparse_csr:
+            raise ValueError(f"{what}: a sparse tensor must have layout torch.sparse_csr, not {matrix.layout}; convert it "
+                             "with .to_sparse_csr()")
+        if matrix.dim() != 2:
+            raise ValueError(f"{what}: the sparse tensor has shape {tuple(matrix.shape)}; a [N, P] matrix is needed")
+        parts = (matrix.crow_indices(), matrix.col_indices(), matrix.values(), tuple(matrix.shape))
+    elif isinstance(matrix, (tuple, list)) and len(matrix) == 4:
+        parts = tuple(matrix)
+    else:
+        raise ValueError(f"{what}: a scipy.sparse matrix, a torch.sparse_csr tensor, a (crow, col, values, shape) tuple of "
+                         f"device tensors or a CSRCounts is needed, not {type(matrix).__name__}")
+    crow, col, val, shape = parts
+    try:
+        N, P = (int(v) for v in shape)
+        ok = len(tuple(shape)) == 2 and 1 <= N < 2**31 and 1 <= P < 2**31
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: shape {shape!r} must be (N, P) with 1 <= N, P < 2^31")
+    for name, t in (("crow", crow), ("col", col), ("values", val)):
+        if not torch.is_tensor(t) or t.dim() != 1 or t.layout != torch.strided:
+            raise ValueError(f"{what}: {name} must be a 1-D tensor, not "
+                             + (f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__))
+    for name, t in (("crow", crow), ("col", col)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{what}: {name} has dtype {t.dtype}; the index dtypes are int32 and int64")
+    if val.dtype == torch.bool or val.is_complex():
+        raise ValueError(f"{what}: values has dtype {val.dtype}; real counts are needed")
+    if crow.numel() != N + 1:
+        raise ValueError(f"{what}: crow has {crow.numel()} entries, shape {(N, P)} needs N + 1 = {N + 1}")
+    if col.numel() != val.numel():
+        raise ValueError(f"{what}: nnz differs: col has {col.numel()} entries, values has {val.numel()}")
+    if col.numel() > N * P:
+        raise ValueError(f"{what}: nnz = {col.numel()} is more than N * P = {N * P}")
+    _on_device(what, crow=crow, col=col, values=val)
+    return crow, col, val, (N, P)
+
+
+def _checked(o, crow, col, val, shape, what):
+    """the device check of arrays already in the kernels' types -> CSRCounts, or the ValueError that names the rule"""
+    N, P = shape
+    n_crow, n_range, n_order, n_zero = (int(v) for v in o.csr_check(crow, col, val, N, P).tolist())
+    if n_crow:
+        raise ValueError(f"{what}: crow is not a row pointer: {n_crow} violations (crow[0] must be 0, crow must not "
+                         f"decrease, crow[N] must be nnz = {col.numel()})")
+    if n_range:
+        raise ValueError(f"{what}: {n_range} column indices are outside [0, {P})")
+    if n_order:
+        raise ValueError(f"{what}: rows are not sorted / hold duplicates: at {n_order} places a row's column index does not "
+                         "strictly increase; use scipy's sum_duplicates / sort_indices or torch's coalesce first")
+    return CSRCounts(crow, col, val, shape, n_zero)
+
+
+def csr_counts(matrix, device=None, _what="csr_counts"):
+    """A count matrix in sparse form -> ``CSRCounts`` on the device, checked.  ``matrix`` is one of
+
+    * a scipy.sparse matrix of any format (scipy is imported only when one is passed): canonicalised on the host with
+      ``tocsr``, ``sum_duplicates`` and ``sort_indices`` (on a copy: the caller's matrix is not modified), then uploaded to
+      ``device`` (default: the current HIP device);
+    * a ``torch.sparse_csr`` tensor on the device;
+    * a tuple ``(crow, col, values, shape)`` of device tensors;
+    * a ``CSRCounts``, returned as it is.
+
+    Index dtypes int32 and int64 are accepted.  ``crow`` is taken to int64, ``col`` to int32 and the values to fp32:
+    each conversion that changes a dtype (or makes a tensor contiguous) copies that one array, an array already in its
+    type is shared with the caller, not copied.  Device-side input is never rewritten: it is checked by one kernel
+    (``gpsa_csr_check``) and a ``ValueError`` names the violated rule with its count - a malformed row pointer, column
+    indices outside [0, P), rows that are not sorted or hold duplicates.  Explicitly stored zeros are allowed and counted
+    in ``n_stored_zeros``.  CPU tensors are refused: there is no host path."""
+    what = _what
+    if isinstance(matrix, CSRCounts):
+        return matrix
+    if _is_scipy_sparse(matrix):
+        import numpy as np
+
+        dev = _upload_device(device, what)
+        m = matrix.tocsr(copy=True)
+        if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1 or m.shape[1] >= 2**31 or m.dtype.kind not in "iuf":
+            raise ValueError(f"{what}: the matrix has shape {m.shape} and dtype {m.dtype}; a real [N >= 1, P >= 1] matrix of "
+                             "counts is needed")
+        m.sum_duplicates()
+        m.sort_indices()
+        parts = (torch.from_numpy(m.indptr.astype(np.int64)).to(dev), torch.from_numpy(m.indices.astype(np.int32)).to(dev),
+                 torch.from_numpy(m.data.astype(np.float32)).to(dev), tuple(int(v) for v in m.shape))
+    else:
+        if device is not None:
+            raise ValueError(f"{what}: device is for scipy input; tensors stay where they are")
+        parts = _csr_parts(matrix, what)
+    crow, col, val, shape = parts
+    crow, col, val = crow.detach().to(torch.int64).contiguous(), col.detach().to(torch.int32).contiguous(), \
+        val.detach().to(f32).contiguous()
+    return _checked(_ops(), crow, col, val, shape, what)
+
+
+def _sparse_arg(Y, what):
+    """the CSRCounts behind a sparse ``Y`` (a torch.sparse_csr tensor is checked here, on entry), or None for a dense one"""
+    if isinstance(Y, CSRCounts):
+        return Y
+    if _is_sparse_tensor(Y) or _is_scipy_sparse(Y):
+        if _is_scipy_sparse(Y):
+            raise ValueError(f"{what}: Y is a scipy.sparse matrix; upload it once with csr_counts(Y) and pass the result")
+        return csr_counts(Y, _what=what)
+    return None
+
+
+def _refuse_sparse(Y, what):
+    if isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y):
+        raise ValueError(f"{what}: Y is sparse, and the result of {what} is a dense N x P matrix; use prepare_counts, which "
+                         "makes only the selected block dense, or densify(csr, rows, genes) first")
+
+
+def _stats_csr(o, A, keep=None):
+    rs, cs, rn, cn, bad = o.count_margins_csr(A.crow, A.col, A.values, A.shape[0], A.shape[1], keep)
+    return Prediction(row_sum=rs, col_sum=cs, row_nnz=rn, col_nnz=cn, n_invalid=int(bad.item()), total=float(rs.sum()))
+
+
+def _index_list(idx, n, name, what, device, unique):
+    """None (all) or indices into [0, n) -> int64 tensor on the device"""
+    if idx is None:
+        return torch.arange(n, device=device)
+    t = torch.as_tensor(idx)
+    if t.dim() != 1 or t.numel() < 1 or t.dtype in (torch.bool,) or t.is_floating_point() or t.is_complex():
+        raise ValueError(f"{what}: {name} must be None or a non-empty 1-D integer index list")
+    t = t.to(device=device, dtype=torch.int64).contiguous()
+    if int(t.min()) < 0 or int(t.max()) >= n:
+        raise ValueError(f"{what}: {name} holds indices outside [0, {n})")
+    if unique and torch.unique(t).numel() != t.numel():
+        raise ValueError(f"{what}: {name} holds an index twice")
+    return t
+
+
+def _gather(o, A, rows, genes):
+    N, P = A.shape
+    slot = torch.full((P,), -1, dtype=torch.int32, device=A.device)
+    slot[genes] = torch.arange(genes.numel(), dtype=torch.int32, device=A.device)
+    return o.csr_gather_dense(A.crow, A.col, A.values, N, P, rows, slot, int(genes.numel()))
+
+
+@torch.no_grad()
+def densify(csr, rows=None, genes=None):
+    """The block ``[rows, genes]`` of a sparse count matrix as a dense fp32 ``[len(rows), len(genes)]`` tensor with zeros
+    where nothing is stored (``None``: all rows / all genes).  ``csr``: a ``CSRCounts`` or anything ``csr_counts`` takes.
+    ``genes`` must not repeat an index.  One kernel; each element is written once."""
+    what = "densify"
+    A = csr_counts(csr, _what=what)
+    rows = _index_list(rows, A.shape[0], "rows", what, A.device, False)
+    genes = _index_list(genes, A.shape[1], "genes", what, A.device, True)
+    return _gather(_ops(), A, rows, genes)
+
+
+def _prepare_sparse(o, A, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize):
+    """_prepare on a CSRCounts: steps 1-3 on the CSR with the row filter as a mask, one gather of the selected block,
+    steps 4-5 by the dense code"""
+    what = "prepare_counts"
+    N, P = A.shape
+    dev = A.device
+    # 1. rows, on the row sums over all genes
+    st = _stats_csr(o, A)
+    _refuse_invalid(st, what)
+    keep = torch.ones(N, dtype=torch.bool, device=dev)
+    if min_counts is not None:
+        keep &= st.row_sum >= min_counts
+    if max_counts is not None:
+        keep &= st.row_sum <= max_counts
+    rows = torch.nonzero(keep).flatten()
+    ns_kept = _view_counts(keep, ns, what)
+    masked = rows.numel() < N
+    # 2. genes, on the margins of the kept rows: the filter is the kernels' mask, not a copy
+    st_r = _stats_csr(o, A, keep) if masked else st
+    row_sum = st_r.row_sum[rows] if masked else st.row_sum
+    passed = None if min_cells is None else st_r.col_nnz >= min_cells
+    # 3. ranking (log_sz is indexed by the original row in the kernel; a masked row's entry is not read)
+    log_sz = _log_size_factors(row_sum, what)
+    lsz_all = torch.zeros(N, dtype=f64, device=dev).index_copy_(0, rows, log_sz) if masked else log_sz
+    sat = o.count_deviance_csr(A.crow, A.col, A.values, N, P, lsz_all, keep if masked else None)
+    dev_g = _close_deviance(*sat, st_r.col_sum, log_sz).deviance
+    if n_top_genes is None and passed is None:
+        genes = torch.arange(P, device=dev)
+    else:
+        genes = torch.sort(_order(dev_g, passed, n_top_genes)).values
+    if genes.numel() < 1:
+        raise ValueError(f"{what}: no gene passes min_cells = {min_cells!r}")
+    Ysel = _gather(o, A, rows, genes)
+    # 4. the transform, 5. the z-score per view: the dense code on the dense block
+    if genes.numel() < P:
+        margins = lambda: _stats(o, Ysel)
+    else:
+        margins = lambda: Prediction(row_sum=row_sum, col_sum=st_r.col_sum, total=float(row_sum.sum()))
+    outputs, log_offset, n_constant = _transform_selected(o, Ysel, True, margins, row_sum, log_sz, ns_kept, transform, theta,
+                                                          standardize, what)
+    return Prediction(outputs=outputs, log_offset=log_offset, rows=rows, genes=genes, n_samples_list=ns_kept,
+                      deviance=dev_g, n_constant=n_constant)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -228,6 +492,9 @@ def count_stats(Y):
     for counts), ``row_nnz`` [N] and ``col_nnz`` [P] (int64: the entries > 0), ``total`` (float) and ``n_invalid`` (int:
     the entries that are NaN, infinite or negative - reported here, refused by every other call)."""
     what = "count_stats"
+    A = _sparse_arg(Y, what)
+    if A is not None:
+        return _stats_csr(_ops(), A)
     _matrix(Y, what)
     _on_device(what, Y=Y)
     return _stats(_ops(), _f32c(Y))
@@ -239,9 +506,11 @@ def size_factors(Y, log=False):
     [N] fp64; ``log=True`` returns their logs (what ``log_offset`` takes).  A row without counts raises a ``ValueError``
     that states how many there are: remove them with ``prepare_counts(min_counts=1)``."""
     what = "size_factors"
-    _matrix(Y, what)
-    _on_device(what, Y=Y)
-    st = _stats(_ops(), _f32c(Y))
+    A = _sparse_arg(Y, what)
+    if A is None:
+        _matrix(Y, what)
+        _on_device(what, Y=Y)
+    st = _stats(_ops(), _f32c(Y)) if A is None else _stats_csr(_ops(), A)
     _refuse_invalid(st, what)
     lsz = _log_size_factors(st.row_sum, what)
     return lsz if log else torch.exp(lsz)
@@ -260,10 +529,23 @@ def poisson_deviance(Y, log_sz=None, return_parts=False):
 
 def _poisson_deviance(what, Y, log_sz=None):
     """the checks and the two reads behind poisson_deviance and deviance_feature_selection, refusing under ``what``"""
-    _matrix(Y, what)
+    sparse = isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)
+    if not sparse:
+        _matrix(Y, what)
     if log_sz is not None and (not torch.is_tensor(log_sz) or tuple(log_sz.shape) != (Y.shape[0],)
                                or not log_sz.is_floating_point()):
         raise ValueError(f"{what}: log_sz must be a floating-point tensor of shape [{Y.shape[0]}]")
+    if sparse:
+        if log_sz is not None:
+            _on_device(what, log_sz=log_sz)
+        A, o = _sparse_arg(Y, what), _ops()
+        if log_sz is not None and log_sz.device != A.device:
+            raise ValueError(f"{what}: the tensors are on different devices: Y on {A.device}, log_sz on {log_sz.device}")
+        st = _stats_csr(o, A)
+        _refuse_invalid(st, what)
+        lsz = _log_size_factors(st.row_sum, what) if log_sz is None else log_sz.detach().to(f64).contiguous()
+        sat = o.count_deviance_csr(A.crow, A.col, A.values, A.shape[0], A.shape[1], lsz)
+        return _close_deviance(*sat, st.col_sum, lsz)
     _on_device(what, Y=Y, log_sz=log_sz)
     o, Y = _ops(), _f32c(Y)
     st = _stats(o, Y)
@@ -278,7 +560,8 @@ def deviance_feature_selection(Y, n_top=None):
     (int64 gene indices by descending deviance, equal values by the lower index; the first ``n_top`` when given).  Genes
     without counts have deviance 0 and rank last (the reference drops them)."""
     what = "deviance_feature_selection"
-    _matrix(Y, what)
+    if not (isinstance(Y, CSRCounts) or _is_sparse_tensor(Y)):
+        _matrix(Y, what)
     if n_top is not None and (isinstance(n_top, bool) or not isinstance(n_top, int) or not 1 <= n_top <= Y.shape[1]):
         raise ValueError(f"{what}: n_top must be None or an integer in [1, {Y.shape[1]}], not {n_top!r}")
     dev = _poisson_deviance(what, Y).deviance
@@ -310,6 +593,7 @@ def _inplace_ok(Y, inplace, what):
 
 
 def _residual_call(what, kind, Y, theta, clipping, inplace):
+    _refuse_sparse(Y, what)
     _matrix(Y, what)
     out = _inplace_ok(Y, inplace, what)
     _on_device(what, Y=Y)
@@ -328,6 +612,7 @@ def normalize_log1p(Y, target_sum=None, inplace=False):
     a formula.  ``target_sum=None``: the median of the row sums of the rows that have counts (the mean of the two middle
     values for an even number of them).  A row without counts stays 0.  [N, P] fp32."""
     what = "normalize_log1p"
+    _refuse_sparse(Y, what)
     _matrix(Y, what)
     if target_sum is not None:
         _target(None, target_sum, what)
@@ -347,6 +632,7 @@ def standardize_views(Y, n_samples_list, inplace=False):
     writes NaN there, which would poison the ELBO).  ``Y`` need not be counts (residuals are negative), so ``n_invalid``
     does not apply here; a NaN or an infinite entry is refused with a ``ValueError`` (one more read of ``Y``: the margins' row sums)."""
     what = "standardize_views"
+    _refuse_sparse(Y, what)
     _matrix(Y, what)
     ns = _check_views(n_samples_list, int(Y.shape[0]), what)
     out = _inplace_ok(Y, inplace, what)
@@ -382,7 +668,9 @@ def prepare_counts(Y, n_samples_list, *, min_counts=None, max_counts=None, min_c
     kept rows) and ``n_constant`` ([V] int64 or None).  ``Y`` itself is never modified, and ``outputs`` never shares its
     memory (a copy even where no row or gene is dropped)."""
     what = "prepare_counts"
-    _matrix(Y, what)
+    sparse = isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)
+    if not sparse:
+        _matrix(Y, what)
     N, P = (int(s) for s in Y.shape)
     ns = _check_views(n_samples_list, N, what)
     if transform not in TRANSFORMS:
@@ -392,6 +680,10 @@ def prepare_counts(Y, n_samples_list, *, min_counts=None, max_counts=None, min_c
     if n_top_genes is not None and (isinstance(n_top_genes, bool) or not isinstance(n_top_genes, int) or n_top_genes < 1):
         raise ValueError(f"{what}: n_top_genes must be None or a positive integer, not {n_top_genes!r}")
     theta = _check_theta(theta, what, True)
+    if sparse:
+        A = _sparse_arg(Y, what)  # (a torch.sparse_csr tensor is checked here)
+        return _prepare_sparse(_ops(), A, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta,
+                               bool(standardize))
     _on_device(what, Y=Y)
     return _prepare(_ops(), _f32c(Y), ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta,
                     bool(standardize))

@@ -837,6 +837,87 @@ class HipOps:
         _lib.check(rc, "gpsa_standardize_views_f32")
         return out, nconst
 
+    # ------------------------------------------------------------------ ... from a CSR matrix (csrc/counts_sparse.hip)
+    @staticmethod
+    def _csr_arrays(crow, col, val, N, P, what):
+        """crow [N + 1] int64, col [nnz] int32, val [nnz] fp32, contiguous, on one device -> nnz"""
+        N, P = int(N), int(P)
+        ok = (N >= 1 and P >= 1 and crow.dtype == torch.int64 and tuple(crow.shape) == (N + 1,) and col.dtype == torch.int32
+              and col.dim() == 1 and val.dtype == torch.float32 and val.shape == col.shape
+              and crow.is_contiguous() and col.is_contiguous() and val.is_contiguous())
+        if not ok:
+            raise ValueError(f"{what}: a CSR matrix [{N}, {P}] needs contiguous crow int64 [{N + 1}], col int32 [nnz] and "
+                             f"val fp32 [nnz], not {crow.dtype} {tuple(crow.shape)}, {col.dtype} {tuple(col.shape)}, "
+                             f"{val.dtype} {tuple(val.shape)}")
+        return int(col.numel())
+
+    @staticmethod
+    def _csr_keep(keep, N, what):
+        if keep is None:
+            return None
+        if tuple(keep.shape) != (N,) or keep.dtype not in (torch.bool, torch.uint8) or not keep.is_contiguous():
+            raise ValueError(f"{what}: keep must be a contiguous bool / uint8 [{N}], not {keep.dtype} {tuple(keep.shape)}")
+        return keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+
+    def _csr_ws(self, N, P, like):
+        nbytes = self._wsq("gpsa_count_csr_workspace", N, P)
+        return self._ws(nbytes, like), nbytes
+
+    def csr_check(self, crow, col, val, N, P):
+        """gpsa_csr_check -> [4] int64 on the device: crow violations, column indices outside [0, P), places inside a
+        row where the column index does not strictly increase, stored zeros"""
+        nnz = self._csr_arrays(crow, col, val, N, P, "csr_check")
+        out = torch.empty(4, dtype=torch.int64, device=crow.device)
+        ws, nbytes = self._csr_ws(N, P, crow)
+        rc = self.lib.gpsa_csr_check(_p(crow), _p(col), _p(val), N, P, nnz, _p(out), _p(ws), nbytes, self._stream(crow))
+        _lib.check(rc, "gpsa_csr_check")
+        return out
+
+    def count_margins_csr(self, crow, col, val, N, P, keep=None):
+        """gpsa_count_margins_csr_f32: count_margins of the CSR matrix [N, P]; ``keep`` [N] bool: rows to take"""
+        nnz = self._csr_arrays(crow, col, val, N, P, "count_margins_csr")
+        keep = self._csr_keep(keep, N, "count_margins_csr")
+        dev = crow.device
+        rs, cs = torch.empty(N, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev)
+        rn, cn = torch.empty(N, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.int64, device=dev)
+        bad = torch.empty(1, dtype=torch.int64, device=dev)
+        ws, nbytes = self._csr_ws(N, P, crow)
+        rc = self.lib.gpsa_count_margins_csr_f32(_p(crow), _p(col), _p(val), _p(keep), N, P, nnz, _p(rs), _p(cs), _p(rn),
+                                                 _p(cn), _p(bad), _p(ws), nbytes, self._stream(crow))
+        _lib.check(rc, "gpsa_count_margins_csr_f32")
+        return rs, cs, rn, cn, bad
+
+    def count_deviance_csr(self, crow, col, val, N, P, log_sz, keep=None):
+        """gpsa_count_deviance_csr_f32: count_deviance of the CSR matrix; log_sz [N] fp64 by the original row"""
+        nnz = self._csr_arrays(crow, col, val, N, P, "count_deviance_csr")
+        keep = self._csr_keep(keep, N, "count_deviance_csr")
+        if log_sz.dim() != 1 or log_sz.shape[0] != N:
+            raise ValueError(f"count_deviance_csr: log_sz has shape {tuple(log_sz.shape)}, [{N}] is needed")
+        log_sz = self._f64(log_sz)
+        ll, ab = (torch.empty(P, dtype=torch.float64, device=crow.device) for _ in range(2))
+        ws, nbytes = self._csr_ws(N, P, crow)
+        rc = self.lib.gpsa_count_deviance_csr_f32(_p(crow), _p(col), _p(val), _p(keep), N, P, nnz, _p(log_sz), _p(ll),
+                                                  _p(ab), _p(ws), nbytes, self._stream(crow))
+        _lib.check(rc, "gpsa_count_deviance_csr_f32")
+        return ll, ab
+
+    def csr_gather_dense(self, crow, col, val, N, P, rows, slot, G):
+        """gpsa_csr_gather_dense_f32: rows [n_rows] int64, slot [P] int32 (the output column of each gene or -1) ->
+        [n_rows, G] fp32 with zeros where nothing is stored"""
+        nnz = self._csr_arrays(crow, col, val, N, P, "csr_gather_dense")
+        G = int(G)
+        if rows.dtype != torch.int64 or rows.dim() != 1 or rows.numel() < 1 or not rows.is_contiguous():
+            raise ValueError(f"csr_gather_dense: rows must be a contiguous int64 [n_rows >= 1], not {rows.dtype} "
+                             f"{tuple(rows.shape)}")
+        if slot.dtype != torch.int32 or tuple(slot.shape) != (P,) or not slot.is_contiguous() or not 1 <= G <= P:
+            raise ValueError(f"csr_gather_dense: slot must be a contiguous int32 [{P}] and 1 <= G <= {P}, not {slot.dtype} "
+                             f"{tuple(slot.shape)}, G = {G}")
+        out = torch.empty(rows.numel(), G, dtype=torch.float32, device=crow.device)
+        rc = self.lib.gpsa_csr_gather_dense_f32(_p(crow), _p(col), _p(val), N, P, nnz, _p(rows), rows.numel(), _p(slot), G,
+                                                _p(out), self._stream(crow))
+        _lib.check(rc, "gpsa_csr_gather_dense_f32")
+        return out
+
     @staticmethod
     def _f64(t):
         t = t if t.dtype == torch.float64 else t.double()

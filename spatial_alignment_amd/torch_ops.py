@@ -22,6 +22,8 @@ each with
        neighbour statistics                 gpsa::knn, gpsa::knn_average               (neighbors.py; csrc/neighbors.hip)
        count preprocessing                  gpsa::count_margins, gpsa::count_deviance, (counts.py; csrc/counts.hip)
                                             gpsa::count_transform, gpsa::standardize_views
+       ... from a CSR matrix                gpsa::csr_check, gpsa::count_margins_csr,  (counts.py; csrc/counts_sparse.hip)
+                                            gpsa::count_deviance_csr, gpsa::csr_gather_dense
        exact GP regression                  gpsa::gpr_cov, gpsa::gpr_lml_grad,         (gpr.py; csrc/gpr.hip)
                                             gpsa::gpr_mean
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
@@ -395,6 +397,57 @@ def standardize_views(Y: torch.Tensor, view_off: list[int]) -> tuple[torch.Tenso
 @standardize_views.register_fake
 def _(Y, view_off):
     return Y.new_empty(Y.shape, dtype=torch.float32), Y.new_empty(len(view_off) - 1, dtype=torch.int64)
+
+
+# ... from a CSR matrix [N, P] on the device: crow [N + 1] int64, col [nnz] int32, val [nnz] fp32 (csrc/counts_sparse.hip)
+@torch.library.custom_op("gpsa::csr_check", mutates_args=(), device_types="cuda")
+def csr_check(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, N: int, P: int) -> torch.Tensor:
+    """[4] int64: crow violations, column indices outside [0, P), places inside a row where the column index does not
+    strictly increase, stored zeros"""
+    return _o().csr_check(crow, col, val, N, P)
+
+
+@csr_check.register_fake
+def _(crow, col, val, N, P):
+    return crow.new_empty(4, dtype=torch.int64)
+
+
+@torch.library.custom_op("gpsa::count_margins_csr", mutates_args=(), device_types="cuda")
+def count_margins_csr(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, N: int, P: int,
+                      keep: Optional[torch.Tensor] = None
+                      ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """gpsa::count_margins of the CSR matrix in one read; ``keep`` [N] bool: the rows to take (None: all)"""
+    return _o().count_margins_csr(crow, col, val, N, P, keep)
+
+
+@count_margins_csr.register_fake
+def _(crow, col, val, N, P, keep=None):
+    return (val.new_empty(N, dtype=torch.float64), val.new_empty(P, dtype=torch.float64),
+            val.new_empty(N, dtype=torch.int64), val.new_empty(P, dtype=torch.int64), val.new_empty(1, dtype=torch.int64))
+
+
+@torch.library.custom_op("gpsa::count_deviance_csr", mutates_args=(), device_types="cuda")
+def count_deviance_csr(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, N: int, P: int, log_sz: torch.Tensor,
+                       keep: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """gpsa::count_deviance of the CSR matrix; log_sz [N] by the original row"""
+    return _o().count_deviance_csr(crow, col, val, N, P, log_sz, keep)
+
+
+@count_deviance_csr.register_fake
+def _(crow, col, val, N, P, log_sz, keep=None):
+    return val.new_empty(P, dtype=torch.float64), val.new_empty(P, dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::csr_gather_dense", mutates_args=(), device_types="cuda")
+def csr_gather_dense(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, N: int, P: int, rows: torch.Tensor,
+                     slot: torch.Tensor, G: int) -> torch.Tensor:
+    """[len(rows), G] fp32: out[j, slot[g]] = the value stored at (rows[j], g), zeros elsewhere; slot [P] int32, -1: dropped"""
+    return _o().csr_gather_dense(crow, col, val, N, P, rows, slot, G)
+
+
+@csr_gather_dense.register_fake
+def _(crow, col, val, N, P, rows, slot, G):
+    return val.new_empty(rows.shape[0], G, dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------
