@@ -506,6 +506,15 @@ int gpsa_mvn_kl_grouped_bwd_acc(const double* mats, const double* inv, const int
                                 const int* pr_list, const int* grp_off, const int* order, const double* D,
                                 const double* KD, const double* g, int M, int T, int P, double* dOmega,
                                 double* dD, double* S, int accumulate, void* stream);
+/* gpsa_mvn_kl_grouped_fwd as the step launches it: a term's rows dealt to gpsa_mvn_kl_grouped_fwd_slices(M)
+ * workgroups (1 up to M = 64, then ceil(M / 64), at most 8) whose partial sums the last one to arrive adds in a
+ * fixed order.  part [T][slices] doubles (any contents), cnt [T] ints ZEROED by the caller and zero again afterwards;
+ * both NULL (or either): one workgroup per term.  kl_copy [T] or NULL: a second copy of kl.  GPSA_EINVAL on a NULL
+ * among the other pointers. */
+int gpsa_mvn_kl_grouped_fwd_slices(int M);
+int gpsa_mvn_kl_grouped_fwd_sliced(const double* mats, const double* inv, const double* logdet, const int* om_idx,
+                                   const int* pr_idx, const double* D, int M, int T, double* kl, double* KD,
+                                   double* kl_copy, double* part, int* cnt, void* stream);
 
 /* ==== the step engine: forward(S) and its backward as ONE host call each =================================
  * Replaces the body of VariationalGPSA.forward (gpsa/models/vgpsa.py:212-489) plus the KL terms of loss_fn

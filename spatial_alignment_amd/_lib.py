@@ -154,6 +154,8 @@ SIGNATURES.update({
     "gpsa_gram_batched_f64": (_i, [_vp, _vp, _i, _ll, _i, _vp, _i, _vp, _ll, _vp]),
     "gpsa_mvn_kl_grouped_bwd_acc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i,
                                          _vp]),
+    "gpsa_mvn_kl_grouped_fwd_slices": (_i, [_i]),
+    "gpsa_mvn_kl_grouped_fwd_sliced": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpsa_step_create": (_vp, [C.POINTER(StepDesc)]),
     "gpsa_step_describe": (_i, [C.POINTER(StepDesc), C.POINTER(_ll)]),
     "gpsa_step_destroy": (None, [_vp]),

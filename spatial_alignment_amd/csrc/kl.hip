@@ -239,6 +239,18 @@ int gpsa_mvn_kl_grouped_fwd(const double* mats, const double* inv, const double*
   return 0;
 }
 
+int gpsa_mvn_kl_grouped_fwd_slices(int M) { return gpsa::mvn_kl_grouped_fwd_slices(M); }
+
+int gpsa_mvn_kl_grouped_fwd_sliced(const double* mats, const double* inv, const double* logdet, const int* om_idx,
+                                   const int* pr_idx, const double* D, int M, int T, double* kl, double* KD,
+                                   double* kl_copy, double* part, int* cnt, void* stream) {
+  if (mats == nullptr || inv == nullptr || logdet == nullptr || om_idx == nullptr || pr_idx == nullptr ||
+      D == nullptr || kl == nullptr || KD == nullptr)
+    return GPSA_EINVAL;
+  return gpsa::mvn_kl_grouped_fwd_copy(mats, inv, logdet, om_idx, pr_idx, D, M, T, kl, KD, kl_copy, part, cnt,
+                                       as_stream(stream));
+}
+
 int gpsa_mvn_kl_grouped_bwd_acc(const double* mats, const double* inv, const int* om_idx,
                                 const int* pr_list, const int* grp_off, const int* order, const double* D,
                                 const double* KD, const double* g, int M, int T, int P, double* dOmega,
