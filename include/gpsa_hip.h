@@ -1181,6 +1181,42 @@ int gpsa_csr_gather_dense_f32(const long long* crow, const int* col, const float
                               long long nnz, const long long* rows, long long n_rows, const int* slot, long long G,
                               float* out, void* stream);
 
+/* ---- per-view column moments (csrc/moments.hip): what dispersion-based gene selection and a variance filter reduce to ----
+ * For every view v (the consecutive rows view_off[v] .. view_off[v + 1] - 1; view_off [V + 1] is a HOST array, 0 =
+ * view_off[0] < ... < view_off[V] = N, as gpsa_standardize_views_f32 takes it) and every column c:
+ *   s1[v, c] = sum t, s2[v, c] = sum t^2, abs1[v, c] = sum |t| over the view's rows, all [V, P] fp64 row-major, and
+ *   n_nonfinite (one int64 on the device): the number of t that are NaN or +-inf.
+ * t is formed in fp64 from the stored fp32 value y:
+ *   mode 0: t = y (negative values allowed: the variance filter on transformed data; abs1 is the error scale of s1);
+ *   mode 1: t = expm1(y) (the matrix is log1p of the normalised counts);
+ *   mode 2: t = y scale_i, scale [N] fp64 on the device (target / row_sum_i, 0 for an empty row): the moments of the
+ *           normalised counts straight from the raw counts.  scale is read in mode 2 only and may be NULL otherwise.
+ * The caller closes mean and variance.  The rules of the count entries hold: fp64 sums in a fixed order, no atomics, one
+ * writer per output element, the same bits on a repeated call, nothing of N * P elements allocated; a row group never
+ * mixes two views (the views are walked one after the other).  Integer values in mode 0 give the same s1 bit for bit
+ * from both entries.
+ * gpsa_column_moments_f32: Y [N, P] fp32 row-major.  workspace >= gpsa_column_moments_workspace(N, P, V) bytes (a pure
+ *   host query, 0 for N, P or V < 1: three column planes of at most 512 row groups, 24 * 512 * P bytes and change).
+ * gpsa_column_moments_csr_f32: the matrix in CSR as in the section above, keep [N] uint8 or NULL: a row with keep == 0
+ *   contributes to nothing.  Unstored entries contribute exactly 0 in all three modes (expm1(0) = 0): the sums and
+ *   n_nonfinite run over the stored entries.  scale is indexed by the row of the whole matrix.  workspace >=
+ *   gpsa_column_moments_csr_workspace(N, P, V) bytes (three column planes of at most 16 row groups; not a function of
+ *   nnz).  Every row range is clamped to [0, nnz] and every column index is checked inside the kernel: a malformed matrix
+ *   gives wrong sums but is never followed outside its buffers.
+ * Refusals, all before the first launch and with nothing written: GPSA_EINVAL for a NULL pointer (keep, and scale
+ * outside mode 2, excepted), an unknown mode, N < 1, P < 1, P >= 2^31, N > 16 (2^31 - 1) (dense) or N >= 2^31 (CSR),
+ * nnz < 0, nnz > N * P, nnz > 0 with a NULL col or val, V < 1, offsets that do not partition [0, N) or an empty view;
+ * GPSA_EWORKSPACE for a NULL or short workspace. */
+long long gpsa_column_moments_workspace(long long N, long long P, int V);
+long long gpsa_column_moments_csr_workspace(long long N, long long P, int V);
+int gpsa_column_moments_f32(int mode, const float* Y, long long N, long long P, const double* scale,
+                            const long long* view_off, int V, double* s1, double* s2, double* abs1,
+                            long long* n_nonfinite, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_column_moments_csr_f32(int mode, const long long* crow, const int* col, const float* val,
+                                const unsigned char* keep, long long N, long long P, long long nnz, const double* scale,
+                                const long long* view_off, int V, double* s1, double* s2, double* abs1,
+                                long long* n_nonfinite, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- exact GP regression (csrc/gpr.hip): sklearn's GaussianProcessRegressor with [C *] k + WhiteKernel ------------------
  * What the reference's experiments fit on the CPU around GPSA: the prediction baselines
  * (experiments/simulations/two_dimensional_prediction.py:126-155, 238, one_dimensional_prediction.py:128-139,

@@ -4,11 +4,13 @@ Same public names as the reference package (gpsa/__init__.py:1-10) for the parts
 """
 from .counts import (
     CSRCounts,
+    column_moments,
     count_stats,
     csr_counts,
     densify,
     deviance_feature_selection,
     deviance_residuals,
+    highly_variable_genes,
     normalize_log1p,
     pearson_residuals,
     poisson_deviance,
@@ -65,6 +67,8 @@ __all__ = [
     "csr_counts",
     "CSRCounts",
     "densify",
+    "column_moments",
+    "highly_variable_genes",
     "gp_regress",
     "GPRegression",
     "prediction_baselines",

@@ -245,6 +245,12 @@ SIGNATURES.update({
     "gpsa_count_margins_csr_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_count_deviance_csr_f32": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_csr_gather_dense_f32": (_i, [_vp, _vp, _vp, _ll, _ll, _ll, _vp, _ll, _vp, _ll, _vp, _vp]),
+    # per-view column moments, dense and CSR (csrc/moments.hip); view_off is a HOST int64 array
+    "gpsa_column_moments_workspace": (_ll, [_ll, _ll, _i]),
+    "gpsa_column_moments_csr_workspace": (_ll, [_ll, _ll, _i]),
+    "gpsa_column_moments_f32": (_i, [_i, _vp, _ll, _ll, _vp, C.POINTER(_ll), _i, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_column_moments_csr_f32": (_i, [_i, _vp, _vp, _vp, _vp, _ll, _ll, _ll, _vp, C.POINTER(_ll), _i, _vp, _vp, _vp,
+                                         _vp, _vp, _ll, _vp]),
     # exact GP regression: covariance assembly, the LML gradient's fused reduction, the fused predictive mean (csrc/gpr.hip)
     "gpsa_gpr_cov_f64": (_i, [_i, _vp, _ll, _vp, _ll, _i, _vp, _i, _i, _d, _vp, _vp]),
     "gpsa_gpr_lml_grad_workspace": (_ll, [_ll, _i]),

@@ -11,7 +11,10 @@ to 2^24), every sum is fp64 in a fixed order, and nothing of N * P elements is a
 * ``count_stats``, ``size_factors``, ``poisson_deviance``, ``deviance_feature_selection``: the Poisson / NB route and the
   gene ranking;
 * ``pearson_residuals``, ``deviance_residuals``, ``normalize_log1p``, ``standardize_views``: the Gaussian route;
-* ``prepare_counts``: the one call, in the order the experiments use;
+* ``column_moments``, ``highly_variable_genes``: mean and variance per (view, gene) in one read (csrc/moments.hip, dense
+  and CSR) and scanpy's Seurat-flavoured dispersion ranking on them - the gene selection the experiments' real-data
+  scripts use, and their per-slice variance filter;
+* ``prepare_counts``: the one call, in the order the experiments use (``selection="deviance"`` or ``"seurat"``);
 * ``csr_counts`` / ``CSRCounts`` / ``densify``: sparse input (csrc/counts_sparse.hip).  ``count_stats``, ``size_factors``,
   ``poisson_deviance``, ``deviance_feature_selection`` and ``prepare_counts`` take a ``CSRCounts`` or a ``torch.sparse_csr``
   tensor where they take ``Y``, with the same return fields, and never build the dense [N, P] matrix: the margins and
@@ -39,6 +42,12 @@ ROWS_MIN, ROWS_MAX, MAX_GROUPS, COL_TILE = 16, 512, 1024, 512
 # the gather assembles at a time
 CSR_ROWS_MIN, CSR_MAX_GROUPS, CSR_COL_TILE, CSR_GATHER_TILE = 16, 32, 512, 8192
 TRANSFORMS = ("pearson", "deviance", "log1p", "counts")
+# csrc/moments.hip: the rows of a group (at least), the caps on a view's groups (dense, CSR), the columns of a tile
+MOM_ROWS_MIN, MOM_MAX_GROUPS, MOM_CSR_MAX_GROUPS, MOM_COL_TILE = 16, 512, 16, 512
+MOMENT_TRANSFORMS = ("identity", "expm1", "normalize")
+SELECTIONS = ("deviance", "seurat")
+COMBINE = ("intersection", "union")
+HVG_DEFAULTS = dict(min_mean=0.0125, max_mean=3, min_disp=0.5, max_disp=math.inf, n_bins=20)  # scanpy's
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -208,7 +217,157 @@ def _view_counts(keep, ns, what):
     return ns_kept
 
 
-def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize):
+# ------------------------------------------------------------------------------------------------------------------------
+# per-view column moments and the Seurat ranking on them (csrc/moments.hip; the ranking is fp64 torch on P-long vectors)
+# ------------------------------------------------------------------------------------------------------------------------
+def _scale(row_sum, target):
+    """target / row sum per row, 0 for a row without counts: what mode "normalize" multiplies a row by"""
+    some = row_sum > 0
+    return torch.where(some, target / torch.where(some, row_sum, torch.ones_like(row_sum)), torch.zeros_like(row_sum))
+
+
+def _close_moments(s1, s2, n):
+    """mean and scanpy's variance (mean of squares - mean^2) n / (n - 1) from the sums; ``n``: rows per view, a list"""
+    n = torch.tensor([float(v) for v in n], dtype=f64, device=s1.device).unsqueeze(1)
+    mean = s1 / n
+    var = (s2 / n - mean * mean) * (n / (n - 1.0))
+    return mean, var
+
+
+def _seurat_bins(means, sel, n_bins):
+    """the bin of every gene: ``n_bins`` equal-width, right-closed bins over [min, max] of ``means[sel]`` with the lowest
+    edge moved down by 0.1 % of the range, and both ends moved out by 0.1 % of their magnitude (0.001 at 0) where the range
+    is zero - ``pandas.cut(x, bins=n)``; the edges are ``numpy.linspace``'s, start + i step with the last one set to the
+    maximum -> (bin [P] int64 in [0, n_bins), edges [n_bins + 1])"""
+    inf = torch.full_like(means, math.inf)
+    mn, mx = torch.where(sel, means, inf).min(), torch.where(sel, means, -inf).max()
+    same = mn == mx
+    pad = lambda v: torch.where(v != 0, 0.001 * v.abs(), torch.full_like(v, 0.001))
+    lo, hi = torch.where(same, mn - pad(mn), mn), torch.where(same, mx + pad(mx), mx)
+    edges = torch.arange(n_bins + 1, dtype=f64, device=means.device) * ((hi - lo) / n_bins) + lo
+    edges[-1] = hi
+    edges[0] = torch.where(same, edges[0], edges[0] - (mx - mn) * 0.001)
+    idx = torch.searchsorted(edges, means.contiguous()) - 1  # right-closed: a value on an edge belongs to the bin below
+    return idx.clamp_(0, n_bins - 1), edges
+
+
+def _seurat_rank(mean, var, sel, n_bins):
+    """scanpy's ``highly_variable_genes(flavor="seurat")`` for one view, on ``mean`` / ``var`` [P] fp64 of the normalised
+    counts, restricted to the genes ``sel`` [P] bool -> (means, dispersions, dispersions_norm, bin), NaN in
+    dispersions_norm outside ``sel``.  Every sum is a masked ``sum`` over the genes in torch's fixed order; the largest
+    temporary is [n_bins, P] doubles."""
+    nan = torch.full_like(mean, math.nan)
+    mean = torch.where(mean == 0, torch.full_like(mean, 1e-12), mean)
+    disp = var / mean
+    disp = torch.log(torch.where(disp == 0, nan, disp))
+    means = torch.log1p(mean)
+    idx, _ = _seurat_bins(means, sel, n_bins)
+    valid = sel & ~torch.isnan(disp)
+    d0 = torch.where(valid, disp, torch.zeros_like(disp))
+    # mean and ddof = 1 standard deviation per bin, NaN skipped, two-pass: row b of ``member`` [n_bins, P] is bin b
+    member = valid.unsqueeze(0) & (idx.unsqueeze(0) == torch.arange(n_bins, device=idx.device).unsqueeze(1))
+    zero = torch.zeros((), dtype=f64, device=mean.device)
+    cnt = member.sum(1).to(f64)
+    bmean = torch.where(member, d0.unsqueeze(0), zero).sum(1) / cnt  # (an empty bin: 0 / 0)
+    ss = torch.where(member, (d0.unsqueeze(0) - bmean.unsqueeze(1)) ** 2, zero).sum(1)
+    bstd = torch.where(cnt >= 2, torch.sqrt(ss / (cnt - 1.0)), nan[0])
+    one = torch.isnan(bstd)  # a bin of one gene: its normalised dispersion is 1
+    bstd = torch.where(one, bmean, bstd)
+    bmean = torch.where(one, torch.zeros_like(bmean), bmean)
+    dnorm = torch.where(sel, (disp - bmean[idx]) / bstd[idx], nan)
+    return means, disp, dnorm, idx
+
+
+def _seurat_select(means, dnorm, sel, n_top_genes, min_mean, max_mean, min_disp, max_disp, what):
+    """-> highly_variable [P] bool"""
+    if n_top_genes is None:
+        dn = torch.where(torch.isnan(dnorm), torch.zeros_like(dnorm), dnorm)
+        return sel & (means > min_mean) & (means < max_mean) & (dn > min_disp) & (dn < max_disp)
+    ranked = sel & ~torch.isnan(dnorm)
+    n_ranked = int(ranked.sum())
+    if n_ranked < 1:
+        raise ValueError(f"{what}: no gene has a normalised dispersion (all NaN): nothing to rank")
+    if n_top_genes > n_ranked:
+        import warnings
+
+        warnings.warn(f"{what}: n_top_genes = {n_top_genes} is more than the {n_ranked} genes with a normalised "
+                      "dispersion; all of them are selected")
+        n_top_genes = n_ranked
+    top = torch.topk(torch.where(ranked, dnorm, torch.full_like(dnorm, -math.inf)), n_top_genes).values
+    return sel & (torch.nan_to_num(dnorm) >= top[-1])  # ties at the cutoff are all kept
+
+
+def _check_hvg(what, n_top_genes, min_mean, max_mean, min_disp, max_disp, n_bins, combine):
+    if n_top_genes is not None and (isinstance(n_top_genes, bool) or not isinstance(n_top_genes, int) or n_top_genes < 1):
+        raise ValueError(f"{what}: n_top_genes must be None or a positive integer, not {n_top_genes!r}")
+    for name, v in (("min_mean", min_mean), ("max_mean", max_mean), ("min_disp", min_disp), ("max_disp", max_disp)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
+            raise ValueError(f"{what}: {name} must be a number, not {v!r}")
+    if isinstance(n_bins, bool) or not isinstance(n_bins, int) or n_bins < 1:
+        raise ValueError(f"{what}: n_bins must be a positive integer, not {n_bins!r}")
+    if combine not in COMBINE:
+        raise ValueError(f"{what}: combine must be one of {COMBINE}, not {combine!r}")
+
+
+def _check_moment_views(n_samples_list, N, what):
+    ns = [N] if n_samples_list is None else _check_views(n_samples_list, N, what)
+    if min(ns) < 2:
+        raise ValueError(f"{what}: the views have {ns} rows; a variance needs at least 2 in every view")
+    return ns
+
+
+def _check_moment_transform(transform, target_sum, what):
+    if transform not in MOMENT_TRANSFORMS:
+        raise ValueError(f"{what}: transform must be one of {MOMENT_TRANSFORMS}, not {transform!r}")
+    if target_sum is not None:
+        _target(None, target_sum, what)
+        if transform != "normalize":
+            raise ValueError(f"{what}: target_sum goes with transform='normalize', not with {transform!r}")
+
+
+def _moment_input(Y, what):
+    """-> (A, Y): the CSRCounts behind a sparse Y (scipy matrices are uploaded) or the dense matrix, checked"""
+    if _is_scipy_sparse(Y):
+        return csr_counts(Y, _what=what), None
+    A = _sparse_arg(Y, what)
+    if A is None:
+        _matrix(Y, what)
+        _on_device(what, Y=Y)
+    return A, Y
+
+
+def _moments(o, A, Y, ns, transform, target_sum, what):
+    """the sums of one read of the matrix (two for "normalize": the row sums first), closed -> Prediction"""
+    scale = None
+    if transform == "normalize":
+        st = _stats(o, Y) if A is None else _stats_csr(o, A)
+        _refuse_invalid(st, what)
+        scale = _scale(st.row_sum, _target(st.row_sum, target_sum, what))
+    if A is None:
+        s1, s2, ab, bad = o.column_moments(Y, transform, _offsets(ns), scale)
+    else:
+        s1, s2, ab, bad = o.column_moments_csr(A.crow, A.col, A.values, A.shape[0], A.shape[1], transform, _offsets(ns),
+                                               scale)
+    mean, var = _close_moments(s1, s2, ns)
+    return Prediction(mean=mean, var=var, n_nonfinite=int(bad.item()), abs_sum=ab)
+
+
+def _prepare_seurat(o, moments, n_rows, row_sum, passed, n_top_genes, what):
+    """step 3 of prepare_counts with selection="seurat": pooled over the kept rows, from the raw counts (mode
+    "normalize": the row sums over all genes, their median as the target) -> (genes, dispersions_norm)"""
+    if n_rows < 2:
+        raise ValueError(f"{what}: the row filter leaves {n_rows} rows; selection='seurat' needs a variance, so at least 2")
+    s1, s2, _, _ = moments(_scale(row_sum, _target(row_sum, None, what)))
+    mean, var = _close_moments(s1, s2, [n_rows])
+    sel = torch.ones_like(mean[0], dtype=torch.bool) if passed is None else passed
+    means, _, dnorm, _ = _seurat_rank(mean[0], var[0], sel, HVG_DEFAULTS["n_bins"])
+    hv = _seurat_select(means, dnorm, sel, n_top_genes, HVG_DEFAULTS["min_mean"], HVG_DEFAULTS["max_mean"],
+                        HVG_DEFAULTS["min_disp"], HVG_DEFAULTS["max_disp"], what)
+    return torch.nonzero(hv).flatten(), dnorm
+
+
+def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize,
+             selection="deviance"):
     what = "prepare_counts"
     N, P = (int(s) for s in Y.shape)
     # 1. rows, on the row sums over all genes
@@ -228,13 +387,21 @@ def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform
     passed = None if min_cells is None else st_r.col_nnz >= min_cells
     # 3. ranking: the deviance over all genes of the kept rows (a row without counts is refused here)
     log_sz = _log_size_factors(st_r.row_sum, what)
-    dev = _deviance(o, Yr, st_r.col_sum, log_sz).deviance
-    if n_top_genes is None and passed is None:
-        genes = torch.arange(P, device=Y.device)
+    dev, extra = None, {}
+    if selection == "seurat":  # ... or the normalised dispersion, pooled over the kept rows
+        n_rows = int(rows.numel())
+        genes, dnorm = _prepare_seurat(o, lambda scale: o.column_moments(Yr, "normalize", [0, n_rows], scale), n_rows,
+                                       st_r.row_sum, passed, n_top_genes, what)
+        extra = dict(dispersions_norm=dnorm)
     else:
-        genes = torch.sort(_order(dev, passed, n_top_genes)).values
+        dev = _deviance(o, Yr, st_r.col_sum, log_sz).deviance
+        if n_top_genes is None and passed is None:
+            genes = torch.arange(P, device=Y.device)
+        else:
+            genes = torch.sort(_order(dev, passed, n_top_genes)).values
     if genes.numel() < 1:
-        raise ValueError(f"{what}: no gene passes min_cells = {min_cells!r}")
+        raise ValueError(f"{what}: no gene passes min_cells = {min_cells!r}" if selection == "deviance" else
+                         f"{what}: no gene is selected (min_cells = {min_cells!r}, n_top_genes = {n_top_genes!r})")
     if genes.numel() < P:
         Ysel, fresh = Yr[:, genes].contiguous(), True
     else:
@@ -244,7 +411,7 @@ def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform
     outputs, log_offset, n_constant = _transform_selected(o, Ysel, fresh, margins, st_r.row_sum, log_sz, ns_kept, transform,
                                                           theta, standardize, what)
     return Prediction(outputs=outputs, log_offset=log_offset, rows=rows, genes=genes, n_samples_list=ns_kept,
-                      deviance=dev, n_constant=n_constant)
+                      deviance=dev, n_constant=n_constant, **extra)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -439,7 +606,8 @@ def densify(csr, rows=None, genes=None):
     return _gather(_ops(), A, rows, genes)
 
 
-def _prepare_sparse(o, A, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize):
+def _prepare_sparse(o, A, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize,
+                    selection="deviance"):
     """_prepare on a CSRCounts: steps 1-3 on the CSR with the row filter as a mask, one gather of the selected block,
     steps 4-5 by the dense code"""
     what = "prepare_counts"
@@ -462,15 +630,23 @@ def _prepare_sparse(o, A, ns, min_counts, max_counts, min_cells, n_top_genes, tr
     passed = None if min_cells is None else st_r.col_nnz >= min_cells
     # 3. ranking (log_sz is indexed by the original row in the kernel; a masked row's entry is not read)
     log_sz = _log_size_factors(row_sum, what)
-    lsz_all = torch.zeros(N, dtype=f64, device=dev).index_copy_(0, rows, log_sz) if masked else log_sz
-    sat = o.count_deviance_csr(A.crow, A.col, A.values, N, P, lsz_all, keep if masked else None)
-    dev_g = _close_deviance(*sat, st_r.col_sum, log_sz).deviance
-    if n_top_genes is None and passed is None:
-        genes = torch.arange(P, device=dev)
+    by_row = lambda v: torch.zeros(N, dtype=f64, device=dev).index_copy_(0, rows, v) if masked else v
+    dev_g, extra = None, {}
+    if selection == "seurat":  # ... or the normalised dispersion, pooled over the kept rows (the mask again)
+        moments = lambda scale: o.column_moments_csr(A.crow, A.col, A.values, N, P, "normalize", [0, N], by_row(scale),
+                                                     keep if masked else None)
+        genes, dnorm = _prepare_seurat(o, moments, int(rows.numel()), row_sum, passed, n_top_genes, what)
+        extra = dict(dispersions_norm=dnorm)
     else:
-        genes = torch.sort(_order(dev_g, passed, n_top_genes)).values
+        sat = o.count_deviance_csr(A.crow, A.col, A.values, N, P, by_row(log_sz), keep if masked else None)
+        dev_g = _close_deviance(*sat, st_r.col_sum, log_sz).deviance
+        if n_top_genes is None and passed is None:
+            genes = torch.arange(P, device=dev)
+        else:
+            genes = torch.sort(_order(dev_g, passed, n_top_genes)).values
     if genes.numel() < 1:
-        raise ValueError(f"{what}: no gene passes min_cells = {min_cells!r}")
+        raise ValueError(f"{what}: no gene passes min_cells = {min_cells!r}" if selection == "deviance" else
+                         f"{what}: no gene is selected (min_cells = {min_cells!r}, n_top_genes = {n_top_genes!r})")
     Ysel = _gather(o, A, rows, genes)
     # 4. the transform, 5. the z-score per view: the dense code on the dense block
     if genes.numel() < P:
@@ -480,7 +656,7 @@ def _prepare_sparse(o, A, ns, min_counts, max_counts, min_cells, n_top_genes, tr
     outputs, log_offset, n_constant = _transform_selected(o, Ysel, True, margins, row_sum, log_sz, ns_kept, transform, theta,
                                                           standardize, what)
     return Prediction(outputs=outputs, log_offset=log_offset, rows=rows, genes=genes, n_samples_list=ns_kept,
-                      deviance=dev_g, n_constant=n_constant)
+                      deviance=dev_g, n_constant=n_constant, **extra)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -647,8 +823,84 @@ def standardize_views(Y, n_samples_list, inplace=False):
 
 
 @torch.no_grad()
+def column_moments(Y, n_samples_list=None, *, transform="identity", target_sum=None):
+    """Mean and variance per (view, column) in one read of ``Y`` [N, P], without a second N x P matrix: a ``Prediction``
+    with ``mean`` and ``var`` [V, P] fp64, ``n_nonfinite`` (int: the transformed values that are NaN or infinite - their
+    columns' moments are then NaN) and ``abs_sum`` [V, P] (the sum of the magnitudes: the scale of the mean's rounding
+    error).  ``Y``: dense, a ``CSRCounts``, a ``torch.sparse_csr`` tensor or a scipy.sparse matrix (uploaded); the views
+    are the consecutive row ranges ``n_samples_list`` (``None``: one view), each of at least 2 rows.  ``transform``:
+
+    * "identity": the values as they are (any sign) - the variance filter ``Y[a:b].var(0) > 0.1`` on transformed data;
+    * "expm1": ``expm1(y)`` - ``Y`` is log1p of normalised counts, scanpy's convention;
+    * "normalize": ``y target_sum / row_sum_i`` - ``Y`` holds raw counts (refused otherwise); ``target_sum=None``: the
+      median of the positive row sums, as in ``normalize_log1p``.  One more read for the row sums.
+
+    The variance is scanpy's: ``(mean of squares - mean^2) n / (n - 1)``, every value and square formed in fp64 and
+    summed in fp64 in a fixed order (csrc/moments.hip).  In a sparse matrix the unstored entries count as zeros."""
+    what = "column_moments"
+    _check_moment_transform(transform, target_sum, what)
+    if not (isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)):
+        _matrix(Y, what)
+    ns = _check_moment_views(n_samples_list, int(Y.shape[0]), what)
+    A, Y = _moment_input(Y, what)
+    return _moments(_ops(), A, None if A is not None else _f32c(Y), ns, transform, target_sum, what)
+
+
+@torch.no_grad()
+def highly_variable_genes(Y, n_samples_list=None, *, transform="expm1", target_sum=None, n_top_genes=None,
+                          min_mean=HVG_DEFAULTS["min_mean"], max_mean=HVG_DEFAULTS["max_mean"],
+                          min_disp=HVG_DEFAULTS["min_disp"], max_disp=HVG_DEFAULTS["max_disp"],
+                          n_bins=HVG_DEFAULTS["n_bins"], gene_mask=None, combine="intersection"):
+    """Dispersion-based gene selection per view, the Seurat flavour as scanpy's ``highly_variable_genes(flavor="seurat")``
+    computes it, on the moments of ``column_moments(Y, n_samples_list, transform=..., target_sum=...)`` (default: ``Y`` is
+    log1p of normalised counts).  Per view: a mean of 0 is set to 1e-12; ``dispersions = log(var / mean)`` with a ratio of
+    0 made NaN; ``means = log1p(mean)``; the genes fall into ``n_bins`` equal-width right-closed bins of ``means``
+    (``pandas.cut``: the lowest edge 0.1 % of the range lower); ``dispersions_norm = (dispersions - bin mean) / bin
+    std`` with NaN skipped, ddof = 1, and 1 for the only gene of a bin.  With ``n_top_genes`` the genes at or above the
+    ``n_top_genes``-th largest ``dispersions_norm`` are selected (ties at the cutoff are all kept; a warning where fewer
+    genes have a value), without it the genes with ``min_mean < means < max_mean`` and ``min_disp < dispersions_norm <
+    max_disp``, NaN counting as 0.  ``gene_mask`` [P] bool: only these genes are binned, ranked and selected, as if the
+    others were absent (their ``dispersions_norm`` is NaN).
+
+    Returns a ``Prediction``: ``means``, ``dispersions``, ``dispersions_norm`` [V, P] fp64, ``highly_variable`` [V, P] bool,
+    ``genes`` (int64, ascending: selected in every view for ``combine="intersection"``, in any view for "union") and
+    ``n_nonfinite``.  The reduction is the HIP kernel of ``column_moments``; binning and ranking are fp64 torch on P-long
+    vectors on the device.  Not pinned to scanpy itself ("Highly variable genes")."""
+    what = "highly_variable_genes"
+    _check_moment_transform(transform, target_sum, what)
+    _check_hvg(what, n_top_genes, min_mean, max_mean, min_disp, max_disp, n_bins, combine)
+    if not (isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)):
+        _matrix(Y, what)
+    N, P = (int(s) for s in Y.shape)
+    ns = _check_moment_views(n_samples_list, N, what)
+    if gene_mask is not None:
+        gene_mask = torch.as_tensor(gene_mask)
+        if gene_mask.dtype != torch.bool or tuple(gene_mask.shape) != (P,):
+            raise ValueError(f"{what}: gene_mask must be a bool [{P}], not {gene_mask.dtype} {tuple(gene_mask.shape)}")
+    A, Y = _moment_input(Y, what)
+    mom = _moments(_ops(), A, None if A is not None else _f32c(Y), ns, transform, target_sum, what)
+    return _hvg_from_moments(mom, gene_mask, n_top_genes, min_mean, max_mean, min_disp, max_disp, n_bins, combine, what)
+
+
+def _hvg_from_moments(mom, gene_mask, n_top_genes, min_mean, max_mean, min_disp, max_disp, n_bins, combine, what):
+    dev = mom.mean.device
+    sel = torch.ones(mom.mean.shape[1], dtype=torch.bool, device=dev) if gene_mask is None else gene_mask.to(dev)
+    if not bool(sel.any()):
+        raise ValueError(f"{what}: gene_mask selects no gene")
+    per_view = []
+    for v in range(mom.mean.shape[0]):
+        means, disp, dnorm, _ = _seurat_rank(mom.mean[v], mom.var[v], sel, n_bins)
+        hv = _seurat_select(means, dnorm, sel, n_top_genes, min_mean, max_mean, min_disp, max_disp, what)
+        per_view.append((means, disp, dnorm, hv))
+    means, disp, dnorm, hv = (torch.stack(t) for t in zip(*per_view))
+    genes = torch.nonzero(hv.all(0) if combine == "intersection" else hv.any(0)).flatten()
+    return Prediction(means=means, dispersions=disp, dispersions_norm=dnorm, highly_variable=hv, genes=genes,
+                      n_nonfinite=mom.n_nonfinite)
+
+
+@torch.no_grad()
 def prepare_counts(Y, n_samples_list, *, min_counts=None, max_counts=None, min_cells=None, n_top_genes=None,
-                   transform="pearson", theta=100.0, standardize=True):
+                   transform="pearson", theta=100.0, standardize=True, selection="deviance"):
     """From raw counts ``Y`` [N, P] (the views' rows one after the other, ``n_samples_list``) to the outputs of a fit, in
     the order the reference's experiments use:
 
@@ -662,6 +914,12 @@ def prepare_counts(Y, n_samples_list, *, min_counts=None, max_counts=None, min_c
        counts untouched plus ``log_offset``, the log size factors in fp32 from all genes - the pair the Poisson /
        negative binomial likelihood takes;
     5. the z-score per view (``standardize``; never for "counts").
+
+    ``selection="seurat"`` replaces step 3's ranking by ``highly_variable_genes``: the normalised dispersion pooled over
+    all kept rows, from the raw counts (``y target / row_sum_i`` with the row sums over ALL genes of the kept rows and
+    their median as the target - the sums step 4's "log1p" uses), among the genes that passed ``min_cells``;
+    ``n_top_genes=None`` then selects by scanpy's default bounds.  The result carries ``dispersions_norm`` [P] fp64 (NaN for
+    a gene that did not pass or has no dispersion) and ``deviance`` is None.
 
     Returns a ``Prediction``: ``outputs`` [N', P'] fp32, ``log_offset`` ([N'] fp32, None except for "counts"), ``rows`` and
     ``genes`` (the kept indices, int64, ascending), ``n_samples_list`` of the kept rows, ``deviance`` ([P] fp64, over the
@@ -680,10 +938,12 @@ def prepare_counts(Y, n_samples_list, *, min_counts=None, max_counts=None, min_c
     if n_top_genes is not None and (isinstance(n_top_genes, bool) or not isinstance(n_top_genes, int) or n_top_genes < 1):
         raise ValueError(f"{what}: n_top_genes must be None or a positive integer, not {n_top_genes!r}")
     theta = _check_theta(theta, what, True)
+    if selection not in SELECTIONS:
+        raise ValueError(f"{what}: selection must be one of {SELECTIONS}, not {selection!r}")
     if sparse:
         A = _sparse_arg(Y, what)  # (a torch.sparse_csr tensor is checked here)
         return _prepare_sparse(_ops(), A, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta,
-                               bool(standardize))
+                               bool(standardize), selection)
     _on_device(what, Y=Y)
     return _prepare(_ops(), _f32c(Y), ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta,
-                    bool(standardize))
+                    bool(standardize), selection)

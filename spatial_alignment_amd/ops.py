@@ -918,6 +918,60 @@ class HipOps:
         _lib.check(rc, "gpsa_csr_gather_dense_f32")
         return out
 
+    # ------------------------------------------------------------------ per-view column moments (csrc/moments.hip)
+    MOMENT_MODES = {"identity": 0, "expm1": 1, "normalize": 2}
+
+    def _moment_args(self, what, mode, N, view_off, scale):
+        """-> (mode number, offsets, V, scale as a contiguous fp64 [N] or None)"""
+        if mode not in self.MOMENT_MODES:
+            raise ValueError(f"{what}: mode must be one of {sorted(self.MOMENT_MODES)}, not {mode!r}")
+        off = [int(v) for v in view_off]
+        V = len(off) - 1
+        if V < 1 or off[0] != 0 or off[-1] != N or any(b <= a for a, b in zip(off, off[1:])):
+            raise ValueError(f"{what}: view_off {off} must rise strictly from 0 to N = {N}")
+        if mode == "normalize":
+            if scale is None or scale.dim() != 1 or scale.shape[0] != N:
+                raise ValueError(f"{what}: mode 'normalize' needs scale [{N}]")
+            scale = self._f64(scale)
+        else:
+            scale = None
+        return self.MOMENT_MODES[mode], off, V, scale
+
+    @staticmethod
+    def _moment_outputs(V, P, dev):
+        s1, s2, ab = (torch.empty(V, P, dtype=torch.float64, device=dev) for _ in range(3))
+        return s1, s2, ab, torch.empty(1, dtype=torch.int64, device=dev)
+
+    def column_moments(self, Y, mode, view_off, scale=None):
+        """gpsa_column_moments_f32: Y [N, P] fp32, ``mode`` "identity" | "expm1" | "normalize" (t = y, expm1(y), y scale_i),
+        view_off a list of V + 1 ints 0 ... N -> (s1, s2, abs1 [V, P] fp64: the sums of t, t^2, |t| per (view, column),
+        n_nonfinite [1] int64 on the device)"""
+        N, P = self._count_matrix(Y, "column_moments")
+        m, off, V, scale = self._moment_args("column_moments", mode, N, view_off, scale)
+        s1, s2, ab, bad = self._moment_outputs(V, P, Y.device)
+        nbytes = self._wsq("gpsa_column_moments_workspace", N, P, V)
+        ws = self._ws(nbytes, Y)
+        rc = self.lib.gpsa_column_moments_f32(m, _p(Y), N, P, _p(scale), (C.c_longlong * (V + 1))(*off), V, _p(s1), _p(s2),
+                                              _p(ab), _p(bad), _p(ws), nbytes, self._stream(Y))
+        _lib.check(rc, "gpsa_column_moments_f32")
+        return s1, s2, ab, bad
+
+    def column_moments_csr(self, crow, col, val, N, P, mode, view_off, scale=None, keep=None):
+        """gpsa_column_moments_csr_f32: column_moments of the CSR matrix [N, P] over its stored entries; scale [N] by the
+        original row; ``keep`` [N] bool: rows to take"""
+        nnz = self._csr_arrays(crow, col, val, N, P, "column_moments_csr")
+        N, P = int(N), int(P)
+        keep = self._csr_keep(keep, N, "column_moments_csr")
+        m, off, V, scale = self._moment_args("column_moments_csr", mode, N, view_off, scale)
+        s1, s2, ab, bad = self._moment_outputs(V, P, crow.device)
+        nbytes = self._wsq("gpsa_column_moments_csr_workspace", N, P, V)
+        ws = self._ws(nbytes, crow)
+        rc = self.lib.gpsa_column_moments_csr_f32(m, _p(crow), _p(col), _p(val), _p(keep), N, P, nnz, _p(scale),
+                                                  (C.c_longlong * (V + 1))(*off), V, _p(s1), _p(s2), _p(ab), _p(bad),
+                                                  _p(ws), nbytes, self._stream(crow))
+        _lib.check(rc, "gpsa_column_moments_csr_f32")
+        return s1, s2, ab, bad
+
     @staticmethod
     def _f64(t):
         t = t if t.dtype == torch.float64 else t.double()

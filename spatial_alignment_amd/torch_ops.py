@@ -24,6 +24,7 @@ each with
                                             gpsa::count_transform, gpsa::standardize_views
        ... from a CSR matrix                gpsa::csr_check, gpsa::count_margins_csr,  (counts.py; csrc/counts_sparse.hip)
                                             gpsa::count_deviance_csr, gpsa::csr_gather_dense
+       per-view column moments              gpsa::column_moments, gpsa::column_moments_csr (counts.py; csrc/moments.hip)
        exact GP regression                  gpsa::gpr_cov, gpsa::gpr_lml_grad,         (gpr.py; csrc/gpr.hip)
                                             gpsa::gpr_mean
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
@@ -448,6 +449,35 @@ def csr_gather_dense(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, N
 @csr_gather_dense.register_fake
 def _(crow, col, val, N, P, rows, slot, G):
     return val.new_empty(rows.shape[0], G, dtype=torch.float32)
+
+
+# ... and the per-view column moments, dense and CSR (csrc/moments.hip)
+@torch.library.custom_op("gpsa::column_moments", mutates_args=(), device_types="cuda")
+def column_moments(Y: torch.Tensor, mode: str, view_off: list[int], scale: Optional[torch.Tensor] = None
+                   ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(s1, s2, abs1 [V, P] fp64, n_nonfinite [1] int64): the sums of t, t^2, |t| per (view, column) of Y [N, P] fp32 with
+    t = y ("identity"), expm1(y) ("expm1") or y scale_i ("normalize"); view_off [V + 1]"""
+    return _o().column_moments(Y, mode, view_off, scale)
+
+
+@column_moments.register_fake
+def _(Y, mode, view_off, scale=None):
+    V, P = len(view_off) - 1, Y.shape[1]
+    return tuple(Y.new_empty(V, P, dtype=torch.float64) for _ in range(3)) + (Y.new_empty(1, dtype=torch.int64),)
+
+
+@torch.library.custom_op("gpsa::column_moments_csr", mutates_args=(), device_types="cuda")
+def column_moments_csr(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, N: int, P: int, mode: str,
+                       view_off: list[int], scale: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None
+                       ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """gpsa::column_moments of the CSR matrix over its stored entries; scale [N] by the original row; ``keep`` [N] bool"""
+    return _o().column_moments_csr(crow, col, val, N, P, mode, view_off, scale, keep)
+
+
+@column_moments_csr.register_fake
+def _(crow, col, val, N, P, mode, view_off, scale=None, keep=None):
+    V = len(view_off) - 1
+    return tuple(val.new_empty(V, P, dtype=torch.float64) for _ in range(3)) + (val.new_empty(1, dtype=torch.int64),)
 
 
 # ---------------------------------------------------------------------------------------------------------
