@@ -1250,6 +1250,54 @@ int gpsa_gpr_lml_grad_f64(int kind, const double* X, long long N, int D, const d
 int gpsa_gpr_mean_f64(int kind, const double* XS, long long ns, const double* X, long long N, int D, const double* theta,
                       int amplitude, const double* alpha, int P, double* out, void* stream);
 
+/* ---- optimal-transport slice alignment (csrc/ot.hip): entropic fused Gromov-Wasserstein between two slices --------------
+ * The pieces of a projected-gradient solve (Peyre, Cuturi and Solomon 2016) whose outer step is
+ *   cost = (1 - alpha) M + 2 alpha (cA 1^T + 1 cB^T - 2 C1 T C2),   T <- argmin <cost, T> + e KL(T || a x b)
+ * next to gpsa_gemm, which forms P log Q^T and C1 T C2.  All fp64, row-major; expression is read as fp32.  Every sum runs
+ * in a fixed order without atomics (a repeated call gives the same bits); nothing of n m elements is allocated; every
+ * *_workspace is a pure host query.
+ *
+ * gpsa_ot_dist_f64: Cm [n, n] = |x_i - x_k| (Euclidean, not squared) from X [n, D]; difference form, symmetric to the
+ *   bit, the diagonal exactly 0.
+ * gpsa_ot_sqmatvec_f64: out [n] = sum_k Cm_ik^2 v_k for Cm [n, ncol]  (cA = (C1 o C1) a).
+ * gpsa_ot_expr_rows_f32: Y [n, P] fp32 ->
+ *   mode 0 ("kl"):        Pm = (y + 0.01) / row sum, Lg = log Pm, term [n] = sum_p Pm Lg; n_invalid (one int64 on the
+ *                         device) counts the entries that are negative, NaN or inf;
+ *   mode 1 ("euclidean"): Pm = y, term = sum_p y^2 (Lg may be NULL); n_invalid counts the NaN or inf entries.
+ * gpsa_ot_expr_cost_f64: in place over G [n, m]: mode 0  M = ra_i - G_ij  (G = P log Q^T);
+ *   mode 1  M = max(0, ra_i + rb_j - 2 G_ij)  (G = A B^T: the SQUARED Euclidean distance of expression rows).
+ * gpsa_ot_cost_f64: in place over G = C1 T C2 [n, m]: the cost above; the same pass writes sums[0..2] = sum |cost|,
+ *   <M, T>, <cAt 1^T + 1 cBt^T - 2 G, T>  (cAt, cBt: (C o C) times T's own marginals; alpha in [0, 1]).
+ * gpsa_ot_sinkhorn_f64: `iters` log-domain sweeps on the stream, f and g read and updated in place:
+ *   f_i = -e LSE_j((g_j - cost_ij) / e + log b_j), then g_j = -e LSE_i((f_i - cost_ij) / e + log a_i); e = *eps, a DEVICE
+ *   double.  A row is never split over workgroups; the column pass keeps a (max, sum) partial per (row group, column) in
+ *   the workspace and merges the groups in order.  Running maxima are subtracted before every exp.
+ * gpsa_ot_plan_f64: T_ij = a_i b_j exp((f_i + g_j - cost_ij) / e) written over T (the previous plan); rowsum [n] = T 1,
+ *   colsum [m] = T^T 1, sums[0..2] = |T 1 - a|_1, |T^T 1 - b|_1, |T - T_old|_1.
+ *
+ * GPSA_EINVAL: a NULL pointer (Lg in mode 1, rb in mode 0 excepted), a size < 1, an unknown mode, alpha outside [0, 1],
+ * iters < 0;  GPSA_EUNSUPPORTED: D > 4, n or m >= 2^31, n > 65535 * 64 in gpsa_ot_dist_f64;  GPSA_EWORKSPACE.  Every check
+ * runs before the first launch. */
+int gpsa_ot_dist_f64(const double* X, long long n, int D, double* Cm, void* stream);
+int gpsa_ot_sqmatvec_f64(const double* Cm, long long n, long long ncol, const double* v, double* out, void* stream);
+long long gpsa_ot_expr_rows_workspace(long long n);
+int gpsa_ot_expr_rows_f32(int mode, const float* Y, long long n, long long P, double* Pm, double* Lg, double* term,
+                          long long* n_invalid, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_ot_expr_cost_f64(int mode, double* G, long long n, long long m, const double* ra, const double* rb,
+                          void* stream);
+long long gpsa_ot_cost_workspace(long long n, long long m);
+int gpsa_ot_cost_f64(double* G, const double* M, const double* T, const double* cA, const double* cB, const double* cAt,
+                     const double* cBt, double alpha, long long n, long long m, double* sums, void* workspace,
+                     long long workspace_bytes, void* stream);
+long long gpsa_ot_sinkhorn_workspace(long long n, long long m);
+int gpsa_ot_sinkhorn_f64(const double* cost, long long n, long long m, const double* loga, const double* logb,
+                         const double* eps, double* f, double* g, int iters, void* workspace,
+                         long long workspace_bytes, void* stream);
+long long gpsa_ot_plan_workspace(long long n, long long m);
+int gpsa_ot_plan_f64(const double* cost, long long n, long long m, const double* f, const double* g, const double* a,
+                     const double* b, const double* eps, double* T, double* rowsum, double* colsum, double* sums,
+                     void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ from .gpr import GPRegression, gp_regress, prediction_baselines
 from .kernels import matern12_kernel, matern32_kernel, rbf_kernel
 from .models import GPSA, VariationalGPSA
 from .neighbors import alignment_score, knn, knn_regress, kth_neighbor_distance, moran_i, spatial_r2
+from .ot import OTAlignment, ot_align, paste_baseline, stack_slices
 from .parallel import fit
 from .predict import predict
 from .util import (
@@ -72,5 +73,9 @@ __all__ = [
     "gp_regress",
     "GPRegression",
     "prediction_baselines",
+    "ot_align",
+    "OTAlignment",
+    "stack_slices",
+    "paste_baseline",
 ]
 __version__ = "0.1.0"

@@ -256,6 +256,19 @@ SIGNATURES.update({
     "gpsa_gpr_lml_grad_workspace": (_ll, [_ll, _i]),
     "gpsa_gpr_lml_grad_f64": (_i, [_i, _vp, _ll, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _ll, _vp]),
     "gpsa_gpr_mean_f64": (_i, [_i, _vp, _ll, _vp, _ll, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    # optimal-transport slice alignment: distances, expression rows and cost, the outer step's cost, the Sinkhorn sweeps,
+    # the plan (csrc/ot.hip); eps is a DEVICE double
+    "gpsa_ot_dist_f64": (_i, [_vp, _ll, _i, _vp, _vp]),
+    "gpsa_ot_sqmatvec_f64": (_i, [_vp, _ll, _ll, _vp, _vp, _vp]),
+    "gpsa_ot_expr_rows_workspace": (_ll, [_ll]),
+    "gpsa_ot_expr_rows_f32": (_i, [_i, _vp, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "gpsa_ot_expr_cost_f64": (_i, [_i, _vp, _ll, _ll, _vp, _vp, _vp]),
+    "gpsa_ot_cost_workspace": (_ll, [_ll, _ll]),
+    "gpsa_ot_cost_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _ll, _ll, _vp, _vp, _ll, _vp]),
+    "gpsa_ot_sinkhorn_workspace": (_ll, [_ll, _ll]),
+    "gpsa_ot_sinkhorn_f64": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _vp, _ll, _vp]),
+    "gpsa_ot_plan_workspace": (_ll, [_ll, _ll]),
+    "gpsa_ot_plan_f64": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

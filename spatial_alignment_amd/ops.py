@@ -739,6 +739,127 @@ class HipOps:
         _lib.check(rc, "gpsa_gpr_mean_f64")
         return out
 
+    # ------------------------------------------------------------------ optimal-transport alignment (csrc/ot.hip)
+    OT_MODES = {"kl": 0, "euclidean": 1}
+
+    @staticmethod
+    def _ot_f64(what, **tensors):
+        """every tensor a contiguous fp64 of the named shape (None in a shape: any extent >= 1)"""
+        for name, (t, shape) in tensors.items():
+            ok = torch.is_tensor(t) and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == len(shape) and all(
+                (s >= 1) if want is None else (s == want) for s, want in zip(t.shape, shape))
+            if not ok:
+                got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
+                want = "[" + ", ".join("n >= 1" if s is None else str(s) for s in shape) + "]"
+                raise ValueError(f"{what}: {name} must be a contiguous fp64 {want}, not {got}")
+
+    def ot_dist(self, X, out=None):
+        """gpsa_ot_dist_f64: X [n, D <= 4] fp64 -> [n, n] Euclidean distances, symmetric to the bit, zero diagonal"""
+        self._ot_f64("ot_dist", X=(X, (None, None)))
+        n, D = int(X.shape[0]), int(X.shape[1])
+        if D > 4:
+            raise ValueError(f"ot_dist: D = {D}; 1 to 4 coordinates are supported")
+        if out is None:
+            out = torch.empty(n, n, dtype=torch.float64, device=X.device)
+        self._ot_f64("ot_dist", out=(out, (n, n)))
+        _lib.check(self.lib.gpsa_ot_dist_f64(_p(X), n, D, _p(out), self._stream(X)), "gpsa_ot_dist_f64")
+        return out
+
+    def ot_sqmatvec(self, Cm, v):
+        """gpsa_ot_sqmatvec_f64: [n] = sum_k Cm_ik^2 v_k for Cm [n, ncol], v [ncol] fp64"""
+        self._ot_f64("ot_sqmatvec", Cm=(Cm, (None, None)))
+        n, ncol = int(Cm.shape[0]), int(Cm.shape[1])
+        self._ot_f64("ot_sqmatvec", v=(v, (ncol,)))
+        out = torch.empty(n, dtype=torch.float64, device=Cm.device)
+        _lib.check(self.lib.gpsa_ot_sqmatvec_f64(_p(Cm), n, ncol, _p(v), _p(out), self._stream(Cm)), "gpsa_ot_sqmatvec_f64")
+        return out
+
+    def ot_expr_rows(self, Y, mode="kl"):
+        """gpsa_ot_expr_rows_f32: Y [n, P] fp32 -> (Pm [n, P], Lg [n, P], term [n] fp64, n_invalid [1] int64 on the device);
+        "kl": Pm = (y + 0.01) / row sum, Lg = log Pm, term = sum Pm Lg; "euclidean": Pm = y, Lg is Pm, term = sum y^2"""
+        if mode not in self.OT_MODES:
+            raise ValueError(f"ot_expr_rows: dissimilarity must be one of {sorted(self.OT_MODES)}, not {mode!r}")
+        if not torch.is_tensor(Y) or Y.dtype != torch.float32 or Y.dim() != 2 or Y.shape[0] < 1 or Y.shape[1] < 1 \
+                or not Y.is_contiguous():
+            got = f"{Y.dtype} {tuple(Y.shape)}" if torch.is_tensor(Y) else type(Y).__name__
+            raise ValueError(f"ot_expr_rows: Y must be a contiguous fp32 [n >= 1, P >= 1], not {got}")
+        n, P = int(Y.shape[0]), int(Y.shape[1])
+        Pm = torch.empty(n, P, dtype=torch.float64, device=Y.device)
+        Lg = torch.empty_like(Pm) if mode == "kl" else None
+        term = torch.empty(n, dtype=torch.float64, device=Y.device)
+        bad = torch.empty(1, dtype=torch.int64, device=Y.device)
+        nbytes = self._wsq("gpsa_ot_expr_rows_workspace", n)
+        ws = self._ws(nbytes, Y)
+        rc = self.lib.gpsa_ot_expr_rows_f32(self.OT_MODES[mode], _p(Y), n, P, _p(Pm), _p(Lg), _p(term), _p(bad), _p(ws),
+                                            nbytes, self._stream(Y))
+        _lib.check(rc, "gpsa_ot_expr_rows_f32")
+        return Pm, (Pm if Lg is None else Lg), term, bad
+
+    def ot_expr_cost(self, G, ra, rb=None, mode="kl"):
+        """gpsa_ot_expr_cost_f64, in place over G [n, m]: "kl" M = ra_i - G_ij; "euclidean" M = max(0, ra_i + rb_j - 2 G_ij)"""
+        if mode not in self.OT_MODES:
+            raise ValueError(f"ot_expr_cost: dissimilarity must be one of {sorted(self.OT_MODES)}, not {mode!r}")
+        self._ot_f64("ot_expr_cost", G=(G, (None, None)))
+        n, m = int(G.shape[0]), int(G.shape[1])
+        self._ot_f64("ot_expr_cost", ra=(ra, (n,)))
+        if mode == "euclidean":
+            self._ot_f64("ot_expr_cost", rb=(rb, (m,)))
+        else:
+            rb = None
+        rc = self.lib.gpsa_ot_expr_cost_f64(self.OT_MODES[mode], _p(G), n, m, _p(ra), _p(rb), self._stream(G))
+        _lib.check(rc, "gpsa_ot_expr_cost_f64")
+        return G
+
+    def ot_cost(self, G, M, T, cA, cB, cAt, cBt, alpha, sums=None):
+        """gpsa_ot_cost_f64, in place over G = C1 T C2 [n, m]: cost = (1 - alpha) M + 2 alpha (cA 1^T + 1 cB^T - 2 G);
+        -> (G, sums [3] fp64 on the device: sum |cost|, <M, T>, <cAt 1^T + 1 cBt^T - 2 G, T>)"""
+        self._ot_f64("ot_cost", G=(G, (None, None)))
+        n, m = int(G.shape[0]), int(G.shape[1])
+        self._ot_f64("ot_cost", M=(M, (n, m)), T=(T, (n, m)), cA=(cA, (n,)), cB=(cB, (m,)), cAt=(cAt, (n,)), cBt=(cBt, (m,)))
+        alpha = float(alpha)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"ot_cost: alpha = {alpha} is outside [0, 1]")
+        if sums is None:
+            sums = torch.empty(3, dtype=torch.float64, device=G.device)
+        self._ot_f64("ot_cost", sums=(sums, (3,)))
+        nbytes = self._wsq("gpsa_ot_cost_workspace", n, m)
+        ws = self._ws(nbytes, G)
+        rc = self.lib.gpsa_ot_cost_f64(_p(G), _p(M), _p(T), _p(cA), _p(cB), _p(cAt), _p(cBt), alpha, n, m, _p(sums), _p(ws),
+                                       nbytes, self._stream(G))
+        _lib.check(rc, "gpsa_ot_cost_f64")
+        return G, sums
+
+    def ot_sinkhorn(self, cost, loga, logb, eps, f, g, iters):
+        """gpsa_ot_sinkhorn_f64: ``iters`` log-domain sweeps, f [n] and g [m] updated in place; eps [1] fp64 on the device"""
+        self._ot_f64("ot_sinkhorn", cost=(cost, (None, None)))
+        n, m = int(cost.shape[0]), int(cost.shape[1])
+        self._ot_f64("ot_sinkhorn", loga=(loga, (n,)), logb=(logb, (m,)), eps=(eps, (1,)), f=(f, (n,)), g=(g, (m,)))
+        iters = int(iters)
+        if iters < 0:
+            raise ValueError(f"ot_sinkhorn: iters = {iters} is negative")
+        nbytes = self._wsq("gpsa_ot_sinkhorn_workspace", n, m)
+        ws = self._ws(nbytes, cost)
+        rc = self.lib.gpsa_ot_sinkhorn_f64(_p(cost), n, m, _p(loga), _p(logb), _p(eps), _p(f), _p(g), iters, _p(ws), nbytes,
+                                           self._stream(cost))
+        _lib.check(rc, "gpsa_ot_sinkhorn_f64")
+        return f, g
+
+    def ot_plan(self, cost, f, g, a, b, eps, T):
+        """gpsa_ot_plan_f64: T_ij = a_i b_j exp((f_i + g_j - cost_ij) / eps) written over T (the previous plan) ->
+        (T, rowsum [n], colsum [m], sums [3]: |T 1 - a|_1, |T^T 1 - b|_1, |T - T_old|_1)"""
+        self._ot_f64("ot_plan", cost=(cost, (None, None)))
+        n, m = int(cost.shape[0]), int(cost.shape[1])
+        self._ot_f64("ot_plan", f=(f, (n,)), g=(g, (m,)), a=(a, (n,)), b=(b, (m,)), eps=(eps, (1,)), T=(T, (n, m)))
+        rowsum = torch.empty(n, dtype=torch.float64, device=cost.device)
+        colsum = torch.empty(m, dtype=torch.float64, device=cost.device)
+        sums = torch.empty(3, dtype=torch.float64, device=cost.device)
+        nbytes = self._wsq("gpsa_ot_plan_workspace", n, m)
+        ws = self._ws(nbytes, cost)
+        rc = self.lib.gpsa_ot_plan_f64(_p(cost), n, m, _p(f), _p(g), _p(a), _p(b), _p(eps), _p(T), _p(rowsum), _p(colsum),
+                                       _p(sums), _p(ws), nbytes, self._stream(cost))
+        _lib.check(rc, "gpsa_ot_plan_f64")
+        return T, rowsum, colsum, sums
+
     def chol_inv_blocked(self, A):
         """gpsa_chol_inv_blocked_f64 for ONE matrix A [N, N] fp64 of any size (not modified) -> L^-1 [N, N] (upper part
         zero), logdet [1] = log det A, info [1] int32 (0, or the 1-based column where the factorisation broke down)"""

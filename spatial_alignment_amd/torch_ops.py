@@ -27,6 +27,7 @@ each with
        per-view column moments              gpsa::column_moments, gpsa::column_moments_csr (counts.py; csrc/moments.hip)
        exact GP regression                  gpsa::gpr_cov, gpsa::gpr_lml_grad,         (gpr.py; csrc/gpr.hip)
                                             gpsa::gpr_mean
+       optimal-transport alignment          gpsa::ot_dist, ot_sqmatvec, ot_expr_rows, ot_expr_cost, ot_cost, ot_sinkhorn, ot_plan (ot.py; csrc/ot.hip)
    (5) KL between Gaussians                 gpsa::mvn_kl                                (vgpsa.py:498-530)
    (6) Gaussian log-likelihood              gpsa::gauss_loglik_sum (+ _bwd)             (vgpsa.py:532-538)
    the whole step                           gpsa::step_forward, gpsa::step_backward,   (vgpsa.py:212-540,
@@ -519,6 +520,96 @@ def gpr_mean(XS: torch.Tensor, X: torch.Tensor, theta: torch.Tensor, alpha: torc
 @gpr_mean.register_fake
 def _(XS, X, theta, alpha, kind, amplitude=False):
     return XS.new_empty(XS.shape[0], alpha.shape[1], dtype=torch.float64)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# (4h) optimal-transport slice alignment: the pieces of an entropic fused Gromov-Wasserstein solve (ot.py; csrc/ot.hip)
+# ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("gpsa::ot_dist", mutates_args=(), device_types="cuda")
+def ot_dist(X: torch.Tensor) -> torch.Tensor:
+    """[n, n] Euclidean distances of X [n, D <= 4] fp64: symmetric to the bit, zero diagonal"""
+    return _o().ot_dist(X)
+
+
+@ot_dist.register_fake
+def _(X):
+    return X.new_empty(X.shape[0], X.shape[0], dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::ot_sqmatvec", mutates_args=(), device_types="cuda")
+def ot_sqmatvec(Cm: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """[n] = sum_k Cm_ik^2 v_k"""
+    return _o().ot_sqmatvec(Cm, v)
+
+
+@ot_sqmatvec.register_fake
+def _(Cm, v):
+    return Cm.new_empty(Cm.shape[0], dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::ot_expr_rows", mutates_args=(), device_types="cuda")
+def ot_expr_rows(Y: torch.Tensor, mode: str = "kl") -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Y [n, P] fp32 -> (Pm [n, P], Lg, term [n] fp64, n_invalid [1] int64); "kl": rows on the simplex after the 0.01
+    shift, Lg [n, P] their logs, term = sum Pm Lg; "euclidean": Pm = y, Lg is empty [0, P], term = sum y^2"""
+    Pm, Lg, term, bad = _o().ot_expr_rows(Y, mode)
+    return Pm, (Pm.new_empty(0, Pm.shape[1]) if Lg is Pm else Lg), term, bad
+
+
+@ot_expr_rows.register_fake
+def _(Y, mode="kl"):
+    n, P = Y.shape
+    return (Y.new_empty(n, P, dtype=torch.float64), Y.new_empty(n if mode == "kl" else 0, P, dtype=torch.float64),
+            Y.new_empty(n, dtype=torch.float64), Y.new_empty(1, dtype=torch.int64))
+
+
+@torch.library.custom_op("gpsa::ot_expr_cost", mutates_args=("G",), device_types="cuda")
+def ot_expr_cost(G: torch.Tensor, ra: torch.Tensor, rb: Optional[torch.Tensor] = None, mode: str = "kl") -> None:
+    """in place over G [n, m]: "kl" M = ra_i - G_ij; "euclidean" M = max(0, ra_i + rb_j - 2 G_ij)"""
+    _o().ot_expr_cost(G, ra, rb, mode)
+
+
+@ot_expr_cost.register_fake
+def _(G, ra, rb=None, mode="kl"):
+    return None
+
+
+@torch.library.custom_op("gpsa::ot_cost", mutates_args=("G",), device_types="cuda")
+def ot_cost(G: torch.Tensor, M: torch.Tensor, T: torch.Tensor, cA: torch.Tensor, cB: torch.Tensor, cAt: torch.Tensor,
+            cBt: torch.Tensor, alpha: float) -> torch.Tensor:
+    """in place over G = C1 T C2: the outer step's cost; -> sums [3]: sum |cost|, <M, T>, <cAt 1^T + 1 cBt^T - 2 G, T>"""
+    return _o().ot_cost(G, M, T, cA, cB, cAt, cBt, alpha)[1]
+
+
+@ot_cost.register_fake
+def _(G, M, T, cA, cB, cAt, cBt, alpha):
+    return G.new_empty(3, dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::ot_sinkhorn", mutates_args=("f", "g"), device_types="cuda")
+def ot_sinkhorn(cost: torch.Tensor, loga: torch.Tensor, logb: torch.Tensor, eps: torch.Tensor, f: torch.Tensor,
+                g: torch.Tensor, iters: int) -> None:
+    """``iters`` log-domain Sinkhorn sweeps on the stream; f [n], g [m] in place; eps [1] fp64 on the device"""
+    _o().ot_sinkhorn(cost, loga, logb, eps, f, g, iters)
+
+
+@ot_sinkhorn.register_fake
+def _(cost, loga, logb, eps, f, g, iters):
+    return None
+
+
+@torch.library.custom_op("gpsa::ot_plan", mutates_args=("T",), device_types="cuda")
+def ot_plan(cost: torch.Tensor, f: torch.Tensor, g: torch.Tensor, a: torch.Tensor, b: torch.Tensor, eps: torch.Tensor,
+            T: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """T = a_i b_j exp((f_i + g_j - cost_ij) / eps) over the previous plan; -> (T 1 [n], T^T 1 [m], sums [3]: the two
+    marginal errors and |T - T_old|_1)"""
+    return _o().ot_plan(cost, f, g, a, b, eps, T)[1:]
+
+
+@ot_plan.register_fake
+def _(cost, f, g, a, b, eps, T):
+    n, m = cost.shape
+    return (cost.new_empty(n, dtype=torch.float64), cost.new_empty(m, dtype=torch.float64),
+            cost.new_empty(3, dtype=torch.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------
