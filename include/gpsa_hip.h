@@ -347,7 +347,8 @@ int gpsa_loglik_bwd(const float* F, const float* Y, const float* noise_u, const 
  * out[b] = sum_i A[b,i]*B[b,i] (strideA/strideB in elements; 0 broadcasts) */
 int gpsa_bdot(int dtype, const void* A, long long strideA, const void* B, long long strideB,
               long long n, int batch, void* out, void* workspace, long long workspace_bytes,
-              void* stream);  /* workspace >= 8*32*batch bytes */
+              void* stream);  /* workspace >= 8*min(32, ceil(n/2048))*batch bytes (GPSA_EWORKSPACE below that;
+                                 8*32*batch is enough for every n) */
 /* A[b] += s * I  (A [batch,M,M]) */
 int gpsa_add_diag(int dtype, void* A, int M, int batch, double s, void* stream);
 
