@@ -1299,6 +1299,55 @@ int gpsa_ot_plan_f64(const double* cost, long long n, long long m, const double*
                      const double* b, const double* eps, double* T, double* rowsum, double* colsum, double* sums,
                      void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- histology images (csrc/image.hip): the pixel modality out of an image, and an image read at any coordinates -------
+ * img is [H, W, C] row-major, C in 1..4; a uint8 value u is (float)u / 255.0f (one fp32 division), an fp32 value is taken
+ * as is.  No atomics, every sum in a fixed order, one writer per output element, the same bits on a repeated call;
+ * nothing of H W elements is allocated; gpsa_image_select_workspace is a pure host query (0 for sizes an entry refuses).
+ *
+ * select: `bin` = b in 1..64 reduces the image to H' = H div b, W' = W div b output pixels, each the mean of its full
+ *   b x b block per channel (fp64 sum in row-major order within the block, / b^2 in fp64, rounded to fp32 once; partial
+ *   blocks at the right and bottom edges are dropped).  Output pixel (r, c) lies at x = c b + (b - 1) / 2,
+ *   y = r b + (b - 1) / 2 and is
+ *     background  when every channel has rintf(v * 10.0f) == rintf(bg * 10.0f)  (fp32 product, round-half-even: numpy's
+ *                 round(v, 1) == bg on fp32; a NaN channel is never background; has_bg = 0: the rule is off);
+ *     outside     when it is not background and fails xmin < x < xmax && ymin < y < ymax, strict, in fp64, with
+ *                 bbox = {xmin, xmax, ymin, ymax}, a HOST array (has_bbox = 0: the rule is off, bbox may be NULL);
+ *     kept        otherwise.
+ *   gpsa_image_select_count_*: per-tile class counts into the workspace, scanned in tile order into tile offsets; the
+ *     totals (kept, background, outside) are left as three int64 at the head of the workspace, on the device.
+ *   gpsa_image_select_write_*: the same arguments and the SAME workspace after a count; recomputes the class and writes
+ *     the kept pixels in the row-major order of the output pixels (a stable compaction): coords [n, 2] fp32 = (x, y),
+ *     pixels [n, C] fp32.  It reads the kept total back from the workspace (8 bytes, the stream is synchronised); with
+ *     capacity (the rows of coords / pixels) below it nothing is written: GPSA_EINVAL.  A kept total of 0 launches nothing.
+ * sample: out [n, C] fp32 and valid [n] uint8 at xy [n, 2] fp64 = (x, y) in pixel coordinates, x the column.  A row is
+ *   valid when 0 <= x <= W - 1 && 0 <= y <= H - 1 (NaN and +-inf are not); an invalid row reads nothing and is `fill` in
+ *   every channel.  order 1: bilinear in fp64 on the cell x0 = min(floor(x), W - 2) (0 when W = 1), fx = x - x0, likewise
+ *   y: top = I[y0,x0] (1 - fx) + I[y0,x1] fx, bot the same on y1, out = top (1 - fy) + bot fy, rounded to fp32 once, so
+ *   x = W - 1 never reads column W.  order 0: the pixel at floor(x + 0.5), clamped into the image.  A row's result does
+ *   not depend on the other rows or on n.
+ *
+ * GPSA_EINVAL: a NULL pointer, H or W < 1, C outside 1..4, bin outside 1..64 or larger than H or W, H' W' >= 2^31, a bbox
+ * with a NaN, capacity < 1 or below the kept total, n < 1 or >= 2^31, an order other than 0 and 1;  GPSA_EWORKSPACE: a
+ * workspace that is NULL or shorter than gpsa_image_select_workspace(H, W, bin).  Every check runs before the first
+ * launch. */
+long long gpsa_image_select_workspace(long long H, long long W, int bin);
+int gpsa_image_select_count_u8(const unsigned char* img, long long H, long long W, int C, int bin, int has_bg, float bg,
+                               int has_bbox, const double* bbox, void* workspace, long long workspace_bytes,
+                               void* stream);
+int gpsa_image_select_count_f32(const float* img, long long H, long long W, int C, int bin, int has_bg, float bg,
+                                int has_bbox, const double* bbox, void* workspace, long long workspace_bytes,
+                                void* stream);
+int gpsa_image_select_write_u8(const unsigned char* img, long long H, long long W, int C, int bin, int has_bg, float bg,
+                               int has_bbox, const double* bbox, void* workspace, long long workspace_bytes,
+                               float* coords, float* pixels, long long capacity, void* stream);
+int gpsa_image_select_write_f32(const float* img, long long H, long long W, int C, int bin, int has_bg, float bg,
+                                int has_bbox, const double* bbox, void* workspace, long long workspace_bytes,
+                                float* coords, float* pixels, long long capacity, void* stream);
+int gpsa_image_sample_u8(const unsigned char* img, long long H, long long W, int C, const double* xy, long long n,
+                         int order, float fill, float* out, unsigned char* valid, void* stream);
+int gpsa_image_sample_f32(const float* img, long long H, long long W, int C, const double* xy, long long n, int order,
+                          float fill, float* out, unsigned char* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

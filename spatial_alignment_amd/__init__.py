@@ -19,6 +19,7 @@ from .counts import (
     standardize_views,
 )
 from .gpr import GPRegression, gp_regress, prediction_baselines
+from .image import Frame, ImagePixels, histology_modality, image_pixels, scale_spatial_coords, warp_image
 from .kernels import matern12_kernel, matern32_kernel, rbf_kernel
 from .models import GPSA, VariationalGPSA
 from .neighbors import alignment_score, knn, knn_regress, kth_neighbor_distance, moran_i, spatial_r2
@@ -77,5 +78,11 @@ __all__ = [
     "OTAlignment",
     "stack_slices",
     "paste_baseline",
+    "Frame",
+    "scale_spatial_coords",
+    "image_pixels",
+    "ImagePixels",
+    "histology_modality",
+    "warp_image",
 ]
 __version__ = "0.1.0"

@@ -269,6 +269,17 @@ SIGNATURES.update({
     "gpsa_ot_sinkhorn_f64": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _i, _vp, _ll, _vp]),
     "gpsa_ot_plan_workspace": (_ll, [_ll, _ll]),
     "gpsa_ot_plan_f64": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    # histology images: the pixel modality out of an image, an image read at any coordinates (csrc/image.hip); bbox is a
+    # HOST array of four doubles
+    "gpsa_image_select_workspace": (_ll, [_ll, _ll, _i]),
+    "gpsa_image_select_count_u8": (_i, [_vp, _ll, _ll, _i, _i, _i, C.c_float, _i, C.POINTER(_d), _vp, _ll, _vp]),
+    "gpsa_image_select_count_f32": (_i, [_vp, _ll, _ll, _i, _i, _i, C.c_float, _i, C.POINTER(_d), _vp, _ll, _vp]),
+    "gpsa_image_select_write_u8": (_i, [_vp, _ll, _ll, _i, _i, _i, C.c_float, _i, C.POINTER(_d), _vp, _ll, _vp, _vp, _ll,
+                                        _vp]),
+    "gpsa_image_select_write_f32": (_i, [_vp, _ll, _ll, _i, _i, _i, C.c_float, _i, C.POINTER(_d), _vp, _ll, _vp, _vp, _ll,
+                                         _vp]),
+    "gpsa_image_sample_u8": (_i, [_vp, _ll, _ll, _i, _vp, _ll, _i, C.c_float, _vp, _vp, _vp]),
+    "gpsa_image_sample_f32": (_i, [_vp, _ll, _ll, _i, _vp, _ll, _i, C.c_float, _vp, _vp, _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

@@ -834,6 +834,13 @@ class VariationalGPSA(GPSA):
 
         return _transfer(self, X, view_from, view_to, **kwargs)
 
+    def warp_image(self, img, view, **kwargs):
+        """Slice ``view``'s image ``img`` [H, W(, C)] resampled in the common coordinate system: every output pixel is
+        sent through ``unwarp`` into the slice and read there by bilinear interpolation (``image.warp_image``)."""
+        from ..image import warp_image as _warp_image
+
+        return _warp_image(self, img, view, **kwargs)
+
     def alignment_score(self, X_spatial, Y, view_idx=None, **kwargs):
         """Did the alignment get better?  Per modality, every view's outputs predicted from every other view's spots by
         kNN regression at the aligned coordinates, scored by R^2 and Pearson's r, with the same from the native

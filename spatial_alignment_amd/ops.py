@@ -1039,8 +1039,88 @@ class HipOps:
         _lib.check(rc, "gpsa_csr_gather_dense_f32")
         return out
 
+    # ------------------------------------------------------------------ histology images (csrc/image.hip)
+    @staticmethod
+    def _image(img, what):
+        """img [H, W, C] contiguous uint8 or fp32 on a device, C in 1..4 -> (H, W, C, "u8" | "f32")"""
+        if (not torch.is_tensor(img) or img.dim() != 3 or img.dtype not in (torch.uint8, torch.float32)
+                or not img.is_contiguous() or min(img.shape) < 1 or img.shape[2] > 4):
+            got = f"{img.dtype} {tuple(img.shape)}" if torch.is_tensor(img) else type(img).__name__
+            raise ValueError(f"{what}: img must be a contiguous uint8 or fp32 [H >= 1, W >= 1, C in 1..4], not {got}")
+        if not img.is_cuda:
+            raise ValueError(f"{what}: img is on {img.device}; the image kernels run on the device")
+        H, W, Cn = (int(s) for s in img.shape)
+        return H, W, Cn, "u8" if img.dtype == torch.uint8 else "f32"
+
+    def image_select(self, img, bin=1, background=None, bbox=None):
+        """gpsa_image_select_count_* / _write_*: the pixels of img [H, W, C] (uint8: u / 255; or fp32), reduced by the mean
+        over ``bin`` x ``bin`` blocks, that are not ``background`` (every channel rounds to it at one decimal; None: the
+        rule is off) and lie strictly inside ``bbox`` = (xmin, xmax, ymin, ymax) (None: off), in row-major order ->
+        (coords [n, 2] fp32 = (x, y), pixels [n, C] fp32, counts [3] int64 on the HOST = (kept, background, outside)).
+        One small host read (the counts) between the two passes; n = 0 skips the second."""
+        H, W, Cn, sfx = self._image(img, "image_select")
+        if isinstance(bin, bool) or int(bin) != bin or not 1 <= bin <= 64 or bin > min(H, W):
+            raise ValueError(f"image_select: bin must be an integer in 1..64 and at most min(H, W) = {min(H, W)}, "
+                             f"not {bin!r}")
+        bin = int(bin)
+        if (H // bin) * (W // bin) >= 2 ** 31:
+            raise ValueError(f"image_select: {H // bin} x {W // bin} output pixels; fewer than 2^31 are supported "
+                             "(raise bin)")
+        has_bg = background is not None
+        bg = float(background) if has_bg else 0.0
+        if has_bg and bg != bg:
+            raise ValueError("image_select: background is NaN (None switches the rule off)")
+        box = None
+        if bbox is not None:
+            vals = [float(v) for v in bbox]
+            if len(vals) != 4 or any(v != v for v in vals):
+                raise ValueError(f"image_select: bbox must be four numbers (xmin, xmax, ymin, ymax) without a NaN, "
+                                 f"not {bbox!r}")
+            box = (C.c_double * 4)(*vals)
+        nbytes = self._wsq("gpsa_image_select_workspace", H, W, bin)
+        ws = self._ws(nbytes, img)
+        args = (_p(img), H, W, Cn, bin, int(has_bg), bg, int(box is not None), box, _p(ws), nbytes)
+        name = f"gpsa_image_select_count_{sfx}"
+        _lib.check(getattr(self.lib, name)(*args, self._stream(img)), name)
+        counts = ws[:24].view(torch.int64).cpu()
+        n = int(counts[0])
+        coords = torch.empty(n, 2, dtype=torch.float32, device=img.device)
+        pixels = torch.empty(n, Cn, dtype=torch.float32, device=img.device)
+        if n:
+            name = f"gpsa_image_select_write_{sfx}"
+            _lib.check(getattr(self.lib, name)(*args, _p(coords), _p(pixels), n, self._stream(img)), name)
+        return coords, pixels, counts
+
+    def image_sample(self, img, xy, order=1, fill=float("nan"), out=None):
+        """gpsa_image_sample_*: img [H, W, C] read at xy [n, 2] fp64 = (x, y) in pixel coordinates (x the column) ->
+        (out [n, C] fp32, valid [n] uint8); order 1 bilinear in fp64, order 0 nearest; a row outside
+        [0, W - 1] x [0, H - 1] (or NaN) is ``fill`` and valid = 0.  ``out``: the same two, preallocated."""
+        H, W, Cn, sfx = self._image(img, "image_sample")
+        if order not in (0, 1) or isinstance(order, bool):
+            raise ValueError(f"image_sample: order must be 0 (nearest) or 1 (bilinear), not {order!r}")
+        if not torch.is_tensor(xy) or xy.dim() != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
+            shape = tuple(xy.shape) if torch.is_tensor(xy) else type(xy).__name__
+            raise ValueError(f"image_sample: xy has shape {shape}, [n >= 1, 2] is needed")
+        if xy.device != img.device:
+            raise ValueError(f"image_sample: xy is on {xy.device}, img on {img.device}")
+        xy = self._f64(xy)
+        n = int(xy.shape[0])
+        if n >= 2 ** 31:
+            raise ValueError(f"image_sample: n = {n} rows; fewer than 2^31 per call are supported")
+        if out is None:
+            out = (torch.empty(n, Cn, dtype=torch.float32, device=img.device),
+                   torch.empty(n, dtype=torch.uint8, device=img.device))
+        vals, valid = out
+        for t, sh, dt in ((vals, (n, Cn), torch.float32), (valid, (n,), torch.uint8)):
+            assert tuple(t.shape) == sh and t.dtype == dt and t.is_contiguous(), sh
+        name = f"gpsa_image_sample_{sfx}"
+        rc = getattr(self.lib, name)(_p(img), H, W, Cn, _p(xy), n, int(order), float(fill), _p(vals), _p(valid),
+                                     self._stream(img))
+        _lib.check(rc, name)
+        return vals, valid
+
     # ------------------------------------------------------------------ per-view column moments (csrc/moments.hip)
-    MOMENT_MODES = {"identity": 0, "expm1": 1, "normalize": 2}
+    MOMENT_MODES ={"identity": 0, "expm1": 1, "normalize": 2}
 
     def _moment_args(self, what, mode, N, view_off, scale):
         """-> (mode number, offsets, V, scale as a contiguous fp64 [N] or None)"""

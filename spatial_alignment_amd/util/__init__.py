@@ -11,3 +11,4 @@ from .util import (  # noqa: F401
     polar_warp,
     rbf_kernel_numpy,
 )
+from ..image import scale_spatial_coords  # noqa: F401,E402  (the helper every script of the reference defines)
