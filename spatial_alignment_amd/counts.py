@@ -111,8 +111,9 @@ def _f32c(Y):
 # ------------------------------------------------------------------------------------------------------------------------
 # the steps over an ops backend ``o`` (HipOps; the tests drive the same code through a fake of their own)
 # ------------------------------------------------------------------------------------------------------------------------
-def _stats(o, Y):
-    rs, cs, rn, cn, bad = o.count_margins(Y)
+def _stats(o, src):
+    """the margins of a source of counts (_DenseCounts / _SparseCounts below)"""
+    rs, cs, rn, cn, bad = src.margins(o)
     return Prediction(row_sum=rs, col_sum=cs, row_nnz=rn, col_nnz=cn, n_invalid=int(bad.item()), total=float(rs.sum()))
 
 
@@ -130,8 +131,8 @@ def _log_size_factors(row_sum, what):
     return lrs - lrs.mean()
 
 
-def _deviance(o, Y, col_sum, log_sz):
-    return _close_deviance(*o.count_deviance(Y, log_sz), col_sum, log_sz)
+def _deviance(o, src, col_sum, log_sz):
+    return _close_deviance(*src.deviance_sums(o, log_sz), col_sum, log_sz)
 
 
 def _close_deviance(ll_sat, abs_sat, col_sum, log_sz):
@@ -325,93 +326,31 @@ def _check_moment_transform(transform, target_sum, what):
             raise ValueError(f"{what}: target_sum goes with transform='normalize', not with {transform!r}")
 
 
-def _moment_input(Y, what):
-    """-> (A, Y): the CSRCounts behind a sparse Y (scipy matrices are uploaded) or the dense matrix, checked"""
-    if _is_scipy_sparse(Y):
-        return csr_counts(Y, _what=what), None
-    A = _sparse_arg(Y, what)
-    if A is None:
-        _matrix(Y, what)
-        _on_device(what, Y=Y)
-    return A, Y
-
-
-def _moments(o, A, Y, ns, transform, target_sum, what):
+def _moments(o, src, ns, transform, target_sum, what):
     """the sums of one read of the matrix (two for "normalize": the row sums first), closed -> Prediction"""
     scale = None
     if transform == "normalize":
-        st = _stats(o, Y) if A is None else _stats_csr(o, A)
+        st = _stats(o, src)
         _refuse_invalid(st, what)
         scale = _scale(st.row_sum, _target(st.row_sum, target_sum, what))
-    if A is None:
-        s1, s2, ab, bad = o.column_moments(Y, transform, _offsets(ns), scale)
-    else:
-        s1, s2, ab, bad = o.column_moments_csr(A.crow, A.col, A.values, A.shape[0], A.shape[1], transform, _offsets(ns),
-                                               scale)
+    s1, s2, ab, bad = src.moments(o, transform, _offsets(ns), scale)
     mean, var = _close_moments(s1, s2, ns)
     return Prediction(mean=mean, var=var, n_nonfinite=int(bad.item()), abs_sum=ab)
 
 
-def _prepare_seurat(o, moments, n_rows, row_sum, passed, n_top_genes, what):
-    """step 3 of prepare_counts with selection="seurat": pooled over the kept rows, from the raw counts (mode
-    "normalize": the row sums over all genes, their median as the target) -> (genes, dispersions_norm)"""
+def _prepare_seurat(o, src, row_sum, passed, n_top_genes, what):
+    """step 3 of prepare_counts with selection="seurat": pooled over the rows of ``src`` (the kept ones), from the raw
+    counts (mode "normalize": the row sums over all genes, their median as the target) -> (genes, dispersions_norm)"""
+    n_rows = src.shape[0]
     if n_rows < 2:
         raise ValueError(f"{what}: the row filter leaves {n_rows} rows; selection='seurat' needs a variance, so at least 2")
-    s1, s2, _, _ = moments(_scale(row_sum, _target(row_sum, None, what)))
+    s1, s2, _, _ = src.moments(o, "normalize", [0, n_rows], _scale(row_sum, _target(row_sum, None, what)))
     mean, var = _close_moments(s1, s2, [n_rows])
     sel = torch.ones_like(mean[0], dtype=torch.bool) if passed is None else passed
     means, _, dnorm, _ = _seurat_rank(mean[0], var[0], sel, HVG_DEFAULTS["n_bins"])
     hv = _seurat_select(means, dnorm, sel, n_top_genes, HVG_DEFAULTS["min_mean"], HVG_DEFAULTS["max_mean"],
                         HVG_DEFAULTS["min_disp"], HVG_DEFAULTS["max_disp"], what)
     return torch.nonzero(hv).flatten(), dnorm
-
-
-def _prepare(o, Y, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize,
-             selection="deviance"):
-    what = "prepare_counts"
-    N, P = (int(s) for s in Y.shape)
-    # 1. rows, on the row sums over all genes
-    st = _stats(o, Y)
-    _refuse_invalid(st, what)
-    keep = torch.ones(N, dtype=torch.bool, device=Y.device)
-    if min_counts is not None:
-        keep &= st.row_sum >= min_counts
-    if max_counts is not None:
-        keep &= st.row_sum <= max_counts
-    rows = torch.nonzero(keep).flatten()
-    ns_kept = _view_counts(keep, ns, what)
-    fresh = rows.numel() < N  # Yr is a copy of ours from here on
-    Yr = Y[rows].contiguous() if fresh else Y
-    # 2. genes, on the margins of the kept rows
-    st_r = _stats(o, Yr) if fresh else st
-    passed = None if min_cells is None else st_r.col_nnz >= min_cells
-    # 3. ranking: the deviance over all genes of the kept rows (a row without counts is refused here)
-    log_sz = _log_size_factors(st_r.row_sum, what)
-    dev, extra = None, {}
-    if selection == "seurat":  # ... or the normalised dispersion, pooled over the kept rows
-        n_rows = int(rows.numel())
-        genes, dnorm = _prepare_seurat(o, lambda scale: o.column_moments(Yr, "normalize", [0, n_rows], scale), n_rows,
-                                       st_r.row_sum, passed, n_top_genes, what)
-        extra = dict(dispersions_norm=dnorm)
-    else:
-        dev = _deviance(o, Yr, st_r.col_sum, log_sz).deviance
-        if n_top_genes is None and passed is None:
-            genes = torch.arange(P, device=Y.device)
-        else:
-            genes = torch.sort(_order(dev, passed, n_top_genes)).values
-    if genes.numel() < 1:
-        raise ValueError(f"{what}: no gene passes min_cells = {min_cells!r}" if selection == "deviance" else
-                         f"{what}: no gene is selected (min_cells = {min_cells!r}, n_top_genes = {n_top_genes!r})")
-    if genes.numel() < P:
-        Ysel, fresh = Yr[:, genes].contiguous(), True
-    else:
-        Ysel = Yr
-    # 4. the transform, 5. the z-score per view
-    margins = (lambda: _stats(o, Ysel)) if genes.numel() < P else (lambda: st_r)
-    outputs, log_offset, n_constant = _transform_selected(o, Ysel, fresh, margins, st_r.row_sum, log_sz, ns_kept, transform,
-                                                          theta, standardize, what)
-    return Prediction(outputs=outputs, log_offset=log_offset, rows=rows, genes=genes, n_samples_list=ns_kept,
-                      deviance=dev, n_constant=n_constant, **extra)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -443,6 +382,10 @@ def _is_scipy_sparse(m):
 
 def _is_sparse_tensor(Y):
     return torch.is_tensor(Y) and Y.layout != torch.strided
+
+
+def _is_sparse(Y):
+    return isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)
 
 
 def _upload_device(device, what):
@@ -562,14 +505,9 @@ def _sparse_arg(Y, what):
 
 
 def _refuse_sparse(Y, what):
-    if isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y):
+    if _is_sparse(Y):
         raise ValueError(f"{what}: Y is sparse, and the result of {what} is a dense N x P matrix; use prepare_counts, which "
                          "makes only the selected block dense, or densify(csr, rows, genes) first")
-
-
-def _stats_csr(o, A, keep=None):
-    rs, cs, rn, cn, bad = o.count_margins_csr(A.crow, A.col, A.values, A.shape[0], A.shape[1], keep)
-    return Prediction(row_sum=rs, col_sum=cs, row_nnz=rn, col_nnz=cn, n_invalid=int(bad.item()), total=float(rs.sum()))
 
 
 def _index_list(idx, n, name, what, device, unique):
@@ -606,57 +544,126 @@ def densify(csr, rows=None, genes=None):
     return _gather(_ops(), A, rows, genes)
 
 
-def _prepare_sparse(o, A, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize,
-                    selection="deviance"):
-    """_prepare on a CSRCounts: steps 1-3 on the CSR with the row filter as a mask, one gather of the selected block,
-    steps 4-5 by the dense code"""
+# ------------------------------------------------------------------------------------------------------------------------
+# one source of counts: what the pipeline asks of the matrix, answered by a dense fp32 matrix or by a CSRCounts.
+# ``restrict(rows, keep)`` is the source of the kept rows (``rows`` = nonzero(``keep``), fewer than all); row vectors go in
+# and come out by kept row.
+# ------------------------------------------------------------------------------------------------------------------------
+class _DenseCounts:
+    """a contiguous fp32 [N, P] on the device; ``fresh``: a copy of ours, which a transform may overwrite.  The kept rows
+    are a copy."""
+
+    def __init__(self, Y, fresh=False):
+        self.Y, self.fresh, self.shape, self.device = Y, fresh, (int(Y.shape[0]), int(Y.shape[1])), Y.device
+
+    def restrict(self, rows, keep):
+        return _DenseCounts(self.Y[rows].contiguous(), True)
+
+    def margins(self, o):
+        return o.count_margins(self.Y)
+
+    def deviance_sums(self, o, log_sz):
+        return o.count_deviance(self.Y, log_sz)
+
+    def moments(self, o, mode, off, scale):
+        return o.column_moments(self.Y, mode, off, scale)
+
+    def block(self, o, genes):
+        """-> (the columns ``genes`` as a dense matrix, whether it is a copy of ours)"""
+        if genes.numel() < self.shape[1]:
+            return self.Y[:, genes].contiguous(), True
+        return self.Y, self.fresh
+
+
+class _SparseCounts:
+    """a CSRCounts.  The kept rows are the kernels' mask over the same matrix, not a copy: a row vector is scattered to
+    the original rows on its way in (a masked row's entry is not read), row outputs are indexed by ``rows``, and only
+    ``block`` makes anything dense - by one gather."""
+
+    def __init__(self, A, rows=None, keep=None):
+        self.A, self.rows, self.keep, self.device = A, rows, keep, A.device
+        self.shape = (A.shape[0] if rows is None else int(rows.numel()), A.shape[1])
+        self.csr = (A.crow, A.col, A.values, A.shape[0], A.shape[1])
+
+    def restrict(self, rows, keep):
+        return _SparseCounts(self.A, rows, keep)
+
+    def _by_row(self, v):
+        if self.keep is None or v is None:
+            return v
+        return torch.zeros(self.A.shape[0], dtype=f64, device=self.device).index_copy_(0, self.rows, v)
+
+    def margins(self, o):
+        rs, cs, rn, cn, bad = o.count_margins_csr(*self.csr, self.keep)
+        return (rs, cs, rn, cn, bad) if self.keep is None else (rs[self.rows], cs, rn[self.rows], cn, bad)
+
+    def deviance_sums(self, o, log_sz):
+        return o.count_deviance_csr(*self.csr, self._by_row(log_sz), self.keep)
+
+    def moments(self, o, mode, off, scale):
+        if self.keep is not None:  # the views' bounds by original row: a kept row's own index, the ends 0 and N
+            off = [0] + self.rows[off[1:-1]].tolist() + [self.A.shape[0]]
+        return o.column_moments_csr(*self.csr, mode, off, self._by_row(scale), self.keep)
+
+    def block(self, o, genes):
+        rows = torch.arange(self.shape[0], device=self.device) if self.rows is None else self.rows
+        return _gather(o, self.A, rows, genes), True
+
+
+def _counts_source(Y, what, upload=False):
+    """the source behind ``Y``: a CSRCounts or a torch.sparse_csr tensor (checked here, on entry), or a dense matrix on the
+    device, taken to contiguous fp32; ``upload``: a scipy.sparse matrix is uploaded, not refused"""
+    A = csr_counts(Y, _what=what) if upload and _is_scipy_sparse(Y) else _sparse_arg(Y, what)
+    if A is not None:
+        return _SparseCounts(A)
+    _matrix(Y, what)
+    _on_device(what, Y=Y)
+    return _DenseCounts(_f32c(Y))
+
+
+def _prepare(o, src, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize,
+             selection="deviance"):
+    """``src``: a source of counts, a contiguous fp32 matrix or a CSRCounts"""
     what = "prepare_counts"
-    N, P = A.shape
-    dev = A.device
+    if not isinstance(src, (_DenseCounts, _SparseCounts)):
+        src = _SparseCounts(src) if isinstance(src, CSRCounts) else _DenseCounts(src)
+    N, P = src.shape
     # 1. rows, on the row sums over all genes
-    st = _stats_csr(o, A)
+    st = _stats(o, src)
     _refuse_invalid(st, what)
-    keep = torch.ones(N, dtype=torch.bool, device=dev)
+    keep = torch.ones(N, dtype=torch.bool, device=src.device)
     if min_counts is not None:
         keep &= st.row_sum >= min_counts
     if max_counts is not None:
         keep &= st.row_sum <= max_counts
     rows = torch.nonzero(keep).flatten()
     ns_kept = _view_counts(keep, ns, what)
-    masked = rows.numel() < N
-    # 2. genes, on the margins of the kept rows: the filter is the kernels' mask, not a copy
-    st_r = _stats_csr(o, A, keep) if masked else st
-    row_sum = st_r.row_sum[rows] if masked else st.row_sum
+    # 2. genes, on the margins of the kept rows
+    kept = src.restrict(rows, keep) if rows.numel() < N else src
+    st_r = _stats(o, kept) if kept is not src else st
     passed = None if min_cells is None else st_r.col_nnz >= min_cells
-    # 3. ranking (log_sz is indexed by the original row in the kernel; a masked row's entry is not read)
-    log_sz = _log_size_factors(row_sum, what)
-    by_row = lambda v: torch.zeros(N, dtype=f64, device=dev).index_copy_(0, rows, v) if masked else v
-    dev_g, extra = None, {}
-    if selection == "seurat":  # ... or the normalised dispersion, pooled over the kept rows (the mask again)
-        moments = lambda scale: o.column_moments_csr(A.crow, A.col, A.values, N, P, "normalize", [0, N], by_row(scale),
-                                                     keep if masked else None)
-        genes, dnorm = _prepare_seurat(o, moments, int(rows.numel()), row_sum, passed, n_top_genes, what)
+    # 3. ranking: the deviance over all genes of the kept rows (a row without counts is refused here)
+    log_sz = _log_size_factors(st_r.row_sum, what)
+    dev, extra = None, {}
+    if selection == "seurat":  # ... or the normalised dispersion, pooled over the kept rows
+        genes, dnorm = _prepare_seurat(o, kept, st_r.row_sum, passed, n_top_genes, what)
         extra = dict(dispersions_norm=dnorm)
     else:
-        sat = o.count_deviance_csr(A.crow, A.col, A.values, N, P, by_row(log_sz), keep if masked else None)
-        dev_g = _close_deviance(*sat, st_r.col_sum, log_sz).deviance
+        dev = _deviance(o, kept, st_r.col_sum, log_sz).deviance
         if n_top_genes is None and passed is None:
-            genes = torch.arange(P, device=dev)
+            genes = torch.arange(P, device=src.device)
         else:
-            genes = torch.sort(_order(dev_g, passed, n_top_genes)).values
+            genes = torch.sort(_order(dev, passed, n_top_genes)).values
     if genes.numel() < 1:
         raise ValueError(f"{what}: no gene passes min_cells = {min_cells!r}" if selection == "deviance" else
                          f"{what}: no gene is selected (min_cells = {min_cells!r}, n_top_genes = {n_top_genes!r})")
-    Ysel = _gather(o, A, rows, genes)
-    # 4. the transform, 5. the z-score per view: the dense code on the dense block
-    if genes.numel() < P:
-        margins = lambda: _stats(o, Ysel)
-    else:
-        margins = lambda: Prediction(row_sum=row_sum, col_sum=st_r.col_sum, total=float(row_sum.sum()))
-    outputs, log_offset, n_constant = _transform_selected(o, Ysel, True, margins, row_sum, log_sz, ns_kept, transform, theta,
-                                                          standardize, what)
+    Ysel, fresh = kept.block(o, genes)
+    # 4. the transform, 5. the z-score per view: on the dense block
+    margins = (lambda: _stats(o, _DenseCounts(Ysel))) if genes.numel() < P else (lambda: st_r)
+    outputs, log_offset, n_constant = _transform_selected(o, Ysel, fresh, margins, st_r.row_sum, log_sz, ns_kept, transform,
+                                                          theta, standardize, what)
     return Prediction(outputs=outputs, log_offset=log_offset, rows=rows, genes=genes, n_samples_list=ns_kept,
-                      deviance=dev_g, n_constant=n_constant, **extra)
+                      deviance=dev, n_constant=n_constant, **extra)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -667,13 +674,8 @@ def count_stats(Y):
     """The margins of ``Y`` [N, P] in one read: a ``Prediction`` with ``row_sum`` [N] and ``col_sum`` [P] (fp64, exact
     for counts), ``row_nnz`` [N] and ``col_nnz`` [P] (int64: the entries > 0), ``total`` (float) and ``n_invalid`` (int:
     the entries that are NaN, infinite or negative - reported here, refused by every other call)."""
-    what = "count_stats"
-    A = _sparse_arg(Y, what)
-    if A is not None:
-        return _stats_csr(_ops(), A)
-    _matrix(Y, what)
-    _on_device(what, Y=Y)
-    return _stats(_ops(), _f32c(Y))
+    src = _counts_source(Y, "count_stats")
+    return _stats(_ops(), src)
 
 
 @torch.no_grad()
@@ -682,11 +684,8 @@ def size_factors(Y, log=False):
     [N] fp64; ``log=True`` returns their logs (what ``log_offset`` takes).  A row without counts raises a ``ValueError``
     that states how many there are: remove them with ``prepare_counts(min_counts=1)``."""
     what = "size_factors"
-    A = _sparse_arg(Y, what)
-    if A is None:
-        _matrix(Y, what)
-        _on_device(what, Y=Y)
-    st = _stats(_ops(), _f32c(Y)) if A is None else _stats_csr(_ops(), A)
+    src = _counts_source(Y, what)
+    st = _stats(_ops(), src)
     _refuse_invalid(st, what)
     lsz = _log_size_factors(st.row_sum, what)
     return lsz if log else torch.exp(lsz)
@@ -705,7 +704,7 @@ def poisson_deviance(Y, log_sz=None, return_parts=False):
 
 def _poisson_deviance(what, Y, log_sz=None):
     """the checks and the two reads behind poisson_deviance and deviance_feature_selection, refusing under ``what``"""
-    sparse = isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)
+    sparse = _is_sparse(Y)
     if not sparse:
         _matrix(Y, what)
     if log_sz is not None and (not torch.is_tensor(log_sz) or tuple(log_sz.shape) != (Y.shape[0],)
@@ -714,20 +713,17 @@ def _poisson_deviance(what, Y, log_sz=None):
     if sparse:
         if log_sz is not None:
             _on_device(what, log_sz=log_sz)
-        A, o = _sparse_arg(Y, what), _ops()
-        if log_sz is not None and log_sz.device != A.device:
-            raise ValueError(f"{what}: the tensors are on different devices: Y on {A.device}, log_sz on {log_sz.device}")
-        st = _stats_csr(o, A)
-        _refuse_invalid(st, what)
-        lsz = _log_size_factors(st.row_sum, what) if log_sz is None else log_sz.detach().to(f64).contiguous()
-        sat = o.count_deviance_csr(A.crow, A.col, A.values, A.shape[0], A.shape[1], lsz)
-        return _close_deviance(*sat, st.col_sum, lsz)
-    _on_device(what, Y=Y, log_sz=log_sz)
-    o, Y = _ops(), _f32c(Y)
-    st = _stats(o, Y)
+        src = _counts_source(Y, what)
+        if log_sz is not None and log_sz.device != src.device:
+            raise ValueError(f"{what}: the tensors are on different devices: Y on {src.device}, log_sz on {log_sz.device}")
+    else:
+        _on_device(what, Y=Y, log_sz=log_sz)
+        src = _DenseCounts(_f32c(Y))
+    o = _ops()
+    st = _stats(o, src)
     _refuse_invalid(st, what)
     lsz = _log_size_factors(st.row_sum, what) if log_sz is None else log_sz.detach().to(f64).contiguous()
-    return _deviance(o, Y, st.col_sum, lsz)
+    return _deviance(o, src, st.col_sum, lsz)
 
 
 @torch.no_grad()
@@ -774,7 +770,7 @@ def _residual_call(what, kind, Y, theta, clipping, inplace):
     out = _inplace_ok(Y, inplace, what)
     _on_device(what, Y=Y)
     o, Y = _ops(), _f32c(Y)
-    st = _stats(o, Y)
+    st = _stats(o, _DenseCounts(Y))
     _refuse_invalid(st, what)
     try:
         return _residuals(o, Y, st, kind, theta, math.sqrt(Y.shape[0]) if clipping else 0.0, out)
@@ -795,7 +791,7 @@ def normalize_log1p(Y, target_sum=None, inplace=False):
     out = _inplace_ok(Y, inplace, what)
     _on_device(what, Y=Y)
     o, Y = _ops(), _f32c(Y)
-    st = _stats(o, Y)
+    st = _stats(o, _DenseCounts(Y))
     _refuse_invalid(st, what)
     return o.count_transform(Y, "log1p", st.row_sum, target=_target(st.row_sum, target_sum, what), out=out)
 
@@ -839,11 +835,11 @@ def column_moments(Y, n_samples_list=None, *, transform="identity", target_sum=N
     summed in fp64 in a fixed order (csrc/moments.hip).  In a sparse matrix the unstored entries count as zeros."""
     what = "column_moments"
     _check_moment_transform(transform, target_sum, what)
-    if not (isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)):
+    if not _is_sparse(Y):
         _matrix(Y, what)
     ns = _check_moment_views(n_samples_list, int(Y.shape[0]), what)
-    A, Y = _moment_input(Y, what)
-    return _moments(_ops(), A, None if A is not None else _f32c(Y), ns, transform, target_sum, what)
+    src = _counts_source(Y, what, upload=True)
+    return _moments(_ops(), src, ns, transform, target_sum, what)
 
 
 @torch.no_grad()
@@ -869,7 +865,7 @@ def highly_variable_genes(Y, n_samples_list=None, *, transform="expm1", target_s
     what = "highly_variable_genes"
     _check_moment_transform(transform, target_sum, what)
     _check_hvg(what, n_top_genes, min_mean, max_mean, min_disp, max_disp, n_bins, combine)
-    if not (isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)):
+    if not _is_sparse(Y):
         _matrix(Y, what)
     N, P = (int(s) for s in Y.shape)
     ns = _check_moment_views(n_samples_list, N, what)
@@ -877,8 +873,8 @@ def highly_variable_genes(Y, n_samples_list=None, *, transform="expm1", target_s
         gene_mask = torch.as_tensor(gene_mask)
         if gene_mask.dtype != torch.bool or tuple(gene_mask.shape) != (P,):
             raise ValueError(f"{what}: gene_mask must be a bool [{P}], not {gene_mask.dtype} {tuple(gene_mask.shape)}")
-    A, Y = _moment_input(Y, what)
-    mom = _moments(_ops(), A, None if A is not None else _f32c(Y), ns, transform, target_sum, what)
+    src = _counts_source(Y, what, upload=True)
+    mom = _moments(_ops(), src, ns, transform, target_sum, what)
     return _hvg_from_moments(mom, gene_mask, n_top_genes, min_mean, max_mean, min_disp, max_disp, n_bins, combine, what)
 
 
@@ -926,8 +922,7 @@ def prepare_counts(Y, n_samples_list, *, min_counts=None, max_counts=None, min_c
     kept rows) and ``n_constant`` ([V] int64 or None).  ``Y`` itself is never modified, and ``outputs`` never shares its
     memory (a copy even where no row or gene is dropped)."""
     what = "prepare_counts"
-    sparse = isinstance(Y, CSRCounts) or _is_sparse_tensor(Y) or _is_scipy_sparse(Y)
-    if not sparse:
+    if not _is_sparse(Y):
         _matrix(Y, what)
     N, P = (int(s) for s in Y.shape)
     ns = _check_views(n_samples_list, N, what)
@@ -940,10 +935,6 @@ def prepare_counts(Y, n_samples_list, *, min_counts=None, max_counts=None, min_c
     theta = _check_theta(theta, what, True)
     if selection not in SELECTIONS:
         raise ValueError(f"{what}: selection must be one of {SELECTIONS}, not {selection!r}")
-    if sparse:
-        A = _sparse_arg(Y, what)  # (a torch.sparse_csr tensor is checked here)
-        return _prepare_sparse(_ops(), A, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta,
-                               bool(standardize), selection)
-    _on_device(what, Y=Y)
-    return _prepare(_ops(), _f32c(Y), ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta,
-                    bool(standardize), selection)
+    src = _counts_source(Y, what)  # (a torch.sparse_csr tensor is checked here)
+    return _prepare(_ops(), src, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, bool(standardize),
+                    selection)

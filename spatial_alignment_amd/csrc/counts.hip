@@ -22,9 +22,12 @@
 //
 // The transforms are elementwise: fp64 arithmetic per element, rounded once to fp32, `out` may be Y itself (an element
 // is read and written by the same thread).
+//
+// The tile loader, the Poisson term, the meet of four partial sums and the view_off check are row_walk.hpp's, shared
+// with counts_sparse.hip and moments.hip.
 #include <math.h>
 
-#include "common.hpp"
+#include "row_walk.hpp"
 
 namespace gpsa {
 
@@ -55,32 +58,6 @@ static long long count_groups_bound(long long N) {
 static long long count_workspace_doubles(long long N, long long P) {
   const long long gb = count_groups_bound(N);
   return 2 * gb * P + gb + 2 * P;
-}
-
-// the column inside the tile of a lane's k-th value
-template <bool VEC>
-__device__ __forceinline__ int tile_col(int lane, int k) {
-  return VEC ? (k >> 2) * 256 + lane * 4 + (k & 3) : k * WAVE + lane;
-}
-
-// a lane's 8 values of the row at `row` in the tile that starts at column c0; columns beyond P read as 0
-template <bool VEC>
-__device__ __forceinline__ void load_row(const float* row, long long c0, long long P, int lane, float (&v)[COUNT_PER_LANE]) {
-  if (VEC) {
-#pragma unroll
-    for (int j = 0; j < COUNT_PER_LANE / 4; ++j) {
-      const long long c = c0 + j * 256 + lane * 4;
-      float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c < P) q = *reinterpret_cast<const float4*>(row + c);  // P % 4 == 0: c + 3 < P
-      v[4 * j] = q.x, v[4 * j + 1] = q.y, v[4 * j + 2] = q.z, v[4 * j + 3] = q.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < COUNT_PER_LANE; ++k) {
-      const long long c = c0 + k * WAVE + lane;
-      v[k] = c < P ? row[c] : 0.f;
-    }
-  }
 }
 
 // (n, mean, M2) of a set joined with (nb, mb, qb) of the rows after it
@@ -120,8 +97,7 @@ count_walk_kernel(const float* __restrict__ Y, long long n, long long P, int R, 
     __syncthreads();
   }
   if (MODE == WALK_DEVIANCE) {
-    // y log y of the integers below COUNT_LOG_TABLE, by the expression the other entries go through: the same bits
-    for (int t = threadIdx.x; t < COUNT_LOG_TABLE; t += 256) ylogy[t] = t > 0 ? (double)t * log((double)t) : 0.0;
+    ylogy_fill<COUNT_LOG_TABLE>(ylogy);
     __syncthreads();
   }
   double nbad = 0.0;
@@ -130,10 +106,10 @@ count_walk_kernel(const float* __restrict__ Y, long long n, long long P, int R, 
 #pragma unroll
     for (int k = 0; k < COUNT_PER_LANE; ++k) a[k] = 0.0, b[k] = 0.0;
     float cur[COUNT_PER_LANE] = {}, nxt[COUNT_PER_LANE] = {};
-    if (w < rows) load_row<VEC>(Yg + (long long)w * P, c0, P, lane, cur);
+    if (w < rows) load_row<VEC, COUNT_PER_LANE>(Yg + (long long)w * P, c0, P, lane, cur);
     int seen = 0;
     for (int r = w; r < rows; r += 4) {
-      if (r + 4 < rows) load_row<VEC>(Yg + (long long)(r + 4) * P, c0, P, lane, nxt);
+      if (r + 4 < rows) load_row<VEC, COUNT_PER_LANE>(Yg + (long long)(r + 4) * P, c0, P, lane, nxt);
       if (MODE == WALK_MARGINS) {
         double s = 0.0;
         float z = 0.f;
@@ -154,11 +130,9 @@ count_walk_kernel(const float* __restrict__ Y, long long n, long long P, int R, 
         const double lsz = aux[r0 + r];
 #pragma unroll
         for (int k = 0; k < COUNT_PER_LANE; ++k) {
-          const float yf = cur[k];
-          const double y = (double)yf;
-          if (y > 0.0) {
-            const int yi = yf < (float)COUNT_LOG_TABLE ? (int)yf : 0;
-            const double t1 = (yi > 0 && (float)yi == yf) ? ylogy[yi] : y * log(y), t2 = y * lsz;
+          if ((double)cur[k] > 0.0) {
+            double t1, t2;
+            poisson_terms<COUNT_LOG_TABLE>(ylogy, cur[k], lsz, t1, t2);
             a[k] += t1 - t2;
             b[k] += fabs(t1) + fabs(t2);
           }
@@ -196,8 +170,8 @@ count_walk_kernel(const float* __restrict__ Y, long long n, long long P, int R, 
           chan_join(cnt, va, vb, nu, ca[u][cc], cb[u][cc]);
         }
       } else {
-        va = ((ca[0][cc] + ca[1][cc]) + ca[2][cc]) + ca[3][cc];
-        vb = ((cb[0][cc] + cb[1][cc]) + cb[2][cc]) + cb[3][cc];
+        va = meet4(ca, cc);
+        vb = meet4(cb, cc);
       }
       pa[(long long)blockIdx.x * P + c] = va;
       pb[(long long)blockIdx.x * P + c] = vb;
@@ -254,8 +228,8 @@ count_fold_kernel(const double* __restrict__ pa, const double* __restrict__ pb, 
     oa[c] = a;
     ((double*)ob)[c] = b > 0.0 ? 1.0 / sqrt(b / (double)n) : 0.0;
   } else {
-    a = ((a + sa[1][lane]) + sa[2][lane]) + sa[3][lane];
-    b = ((b + sb[1][lane]) + sb[2][lane]) + sb[3][lane];
+    a = sum4(a, sa[1][lane], sa[2][lane], sa[3][lane]);
+    b = sum4(b, sb[1][lane], sb[2][lane], sb[3][lane]);
     oa[c] = a;
     if (MODE == WALK_MARGINS)
       ((long long*)ob)[c] = (long long)b;
@@ -465,10 +439,8 @@ int gpsa_standardize_views_f32(const float* Y, long long N, long long P, const l
                                long long* n_constant, void* workspace, long long workspace_bytes, void* stream) {
   using namespace gpsa;
   if (int rc = count_shape_check(Y, N, P)) return rc;
-  if (!view_off || !out || !n_constant || V < 1) return GPSA_EINVAL;
-  if (view_off[0] != 0 || view_off[V] != N) return GPSA_EINVAL;
-  for (int v = 0; v < V; ++v)
-    if (view_off[v + 1] <= view_off[v]) return GPSA_EINVAL;  // an empty view has no moments
+  if (!out || !n_constant) return GPSA_EINVAL;
+  if (int rc = view_off_check(view_off, V, N)) return rc;
   if (workspace == nullptr || workspace_bytes < gpsa_count_workspace(N, P)) return GPSA_EWORKSPACE;
   hipStream_t st = as_stream(stream);
   const CountWorkspace ws(workspace, N, P);

@@ -12,9 +12,9 @@
 //     columns in LDS (two doubles per column); a lane adds an entry to the plane at the entry's column.  The columns
 //     inside a row of a checked matrix are distinct, so no two lanes of the wave meet, and the rows follow each other in
 //     the wave's program order: every plane element is added to in row order;
-//   * where a row's part of the tile starts is found by a 64-way search over the row's (sorted) column indices, one load
-//     per round and lane, until 64 or fewer candidates remain; the entries are then taken 64 at a time until one at or
-//     beyond the tile's end is seen.  Every entry is consumed by exactly one tile: the matrix is read once;
+//   * a row's part of the tile is swept by row_walk.hpp's csr_row_in_tile (a 64-way search for its start, then 64
+//     entries at a time), shared with moments.hip; the Poisson term is the dense walk's function.  Every entry is
+//     consumed by exactly one tile: the matrix is read once;
 //   * the four planes meet in wave order and go to the group's row of two partial planes pa / pb [G, P];
 //   * a row's total over the tile is a wave sum, written by lane 0 to rpa / rpn [T, N] (margins only);
 //   * csr_fold_kernel folds pa / pb over the groups and rpa / rpn over the tiles, both in order, and sums the
@@ -29,7 +29,7 @@
 // honoured by the two reductions.
 #include <math.h>
 
-#include "common.hpp"
+#include "row_walk.hpp"
 
 namespace gpsa {
 
@@ -61,9 +61,6 @@ struct CsrWorkspace {
 };
 
 __device__ __forceinline__ long long cdivd(long long a, long long b) { return (a + b - 1) / b; }
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) {
-  return v < lo ? lo : (v > hi ? hi : v);
-}
 
 // block (blockIdx.x = t, blockIdx.y = g) of the matrix; see the head of the file.
 //   CSR_MARGINS:  pa = sums, pb = entries > 0 per column; rpa / rpn the same per row; bad = values NaN, +-inf or < 0
@@ -82,54 +79,28 @@ csr_walk_kernel(const long long* __restrict__ crow, const int* __restrict__ col,
   const long long c0 = t * CSR_COL_TILE, c1 = min(P, c0 + CSR_COL_TILE);
   const long long r0 = g * R, r1 = min(N, r0 + R);
   for (int cc = threadIdx.x; cc < 4 * CSR_COL_TILE; cc += 256) (&ca[0][0])[cc] = 0.0, (&cb[0][0])[cc] = 0.0;
-  if (MODE == CSR_DEVIANCE)  // by the expression the other entries go through, as in counts.hip: the same bits
-    for (int k = threadIdx.x; k < CSR_LOG_TABLE; k += 256) ylogy[k] = k > 0 ? (double)k * log((double)k) : 0.0;
+  if (MODE == CSR_DEVIANCE) ylogy_fill<CSR_LOG_TABLE>(ylogy);
   __syncthreads();
   double nbad = 0.0;
   for (long long i = r0 + w; i < r1; i += 4) {
-    const long long s = clampll(crow[i], 0, nnz), e = clampll(crow[i + 1], s, nnz);
-    const long long len = (keep != nullptr && keep[i] == 0) ? 0 : e - s;
-    // the first entry at or beyond c0 lies in [lo, hi]: 64 probes per round (wave-uniform lo, hi)
-    long long lo = 0, hi = len;
-    while (hi - lo > WAVE) {
-      const long long step = (hi - lo + WAVE - 1) / WAVE, p = lo + lane * step;
-      const bool before = p < hi && (long long)col[s + p] < c0;
-      const long long cnt = __popcll(__builtin_amdgcn_ballot_w64(before));
-      if (cnt == 0) {
-        hi = lo;
-      } else {
-        hi = min(hi, lo + cnt * step);
-        lo = lo + (cnt - 1) * step + 1;
-      }
-    }
     const double lsz = MODE == CSR_DEVIANCE ? aux[i] : 0.0;
     double srow = 0.0;
     float nrow = 0.f;
-    for (long long pos = lo; pos < len; pos += WAVE) {
-      const long long k = pos + lane;
-      long long c = c1;
-      float y = 0.f;
-      if (k < len) c = col[s + k], y = val[s + k];
-      const bool below = k < len && c < c1;
-      if (below && c >= c0) {  // c0 <= c < c1 <= P: inside the tile, inside the plane
-        const int cc = (int)(c - c0);
-        if (MODE == CSR_MARGINS) {
-          const bool positive = y > 0.f;
-          ca[w][cc] += (double)y;
-          cb[w][cc] += positive ? 1.0 : 0.0;
-          srow += (double)y;
-          nrow += positive ? 1.f : 0.f;
-          nbad += (y >= 0.f && y < INFINITY) ? 0.0 : 1.0;
-        } else if (y > 0.f) {
-          const double yd = (double)y;
-          const int yi = y < (float)CSR_LOG_TABLE ? (int)y : 0;
-          const double t1 = (yi > 0 && (float)yi == y) ? ylogy[yi] : yd * log(yd), t2 = yd * lsz;
-          ca[w][cc] += t1 - t2;
-          cb[w][cc] += fabs(t1) + fabs(t2);
-        }
+    csr_row_in_tile(crow, col, val, keep, i, nnz, c0, c1, lane, [&](int cc, float y) {
+      if (MODE == CSR_MARGINS) {
+        const bool positive = y > 0.f;
+        ca[w][cc] += (double)y;
+        cb[w][cc] += positive ? 1.0 : 0.0;
+        srow += (double)y;
+        nrow += positive ? 1.f : 0.f;
+        nbad += (y >= 0.f && y < INFINITY) ? 0.0 : 1.0;
+      } else if (y > 0.f) {
+        double t1, t2;
+        poisson_terms<CSR_LOG_TABLE>(ylogy, y, lsz, t1, t2);
+        ca[w][cc] += t1 - t2;
+        cb[w][cc] += fabs(t1) + fabs(t2);
       }
-      if (__popcll(__builtin_amdgcn_ballot_w64(below)) < WAVE) break;  // the row's end, or an entry beyond the tile
-    }
+    });
     if (MODE == CSR_MARGINS) {
       srow = wave_sum(srow);
       nrow = wave_sum(nrow);
@@ -139,8 +110,8 @@ csr_walk_kernel(const long long* __restrict__ crow, const int* __restrict__ col,
   __syncthreads();
   // the four waves' columns meet in wave order
   for (int cc = threadIdx.x; cc < (int)(c1 - c0); cc += 256) {
-    pa[g * P + c0 + cc] = ((ca[0][cc] + ca[1][cc]) + ca[2][cc]) + ca[3][cc];
-    pb[g * P + c0 + cc] = ((cb[0][cc] + cb[1][cc]) + cb[2][cc]) + cb[3][cc];
+    pa[g * P + c0 + cc] = meet4(ca, cc);
+    pb[g * P + c0 + cc] = meet4(cb, cc);
   }
   if (MODE == CSR_MARGINS) {
     const double tot = block_sum(nbad, red);
@@ -259,14 +230,6 @@ csr_gather_kernel(const long long* __restrict__ crow, const int* __restrict__ co
     for (int q = threadIdx.x; q < width; q += 256) out[j * G + g0 + q] = buf[q];
     __syncthreads();  // before the next tile's zeros
   }
-}
-
-// what every entry asks of (crow, col, val, N, P, nnz): 0 or the refusal
-static int csr_shape_check(const void* crow, const void* col, const void* val, long long N, long long P, long long nnz) {
-  if (crow == nullptr || N < 1 || P < 1 || P > 0x7fffffffLL || N > 0x7fffffffLL) return GPSA_EINVAL;
-  if (nnz < 0 || nnz > N * P) return GPSA_EINVAL;  // (N, P < 2^31: no overflow)
-  if (nnz > 0 && (col == nullptr || val == nullptr)) return GPSA_EINVAL;
-  return 0;
 }
 
 template <int MODE>

@@ -22,7 +22,8 @@
 //
 // CSR (moments_csr_walk_kernel), the structure of counts_sparse.hip's walk over a grid of (column tile, row group) per
 // view, G <= MOM_CSR_MAX_GROUPS: each wave owns a private plane of the tile's columns in LDS (three doubles per column)
-// and adds the rows' entries to it in row order; the planes meet in wave order.  Unstored entries contribute exactly 0
+// and adds the rows' entries to it in row order; the planes meet in wave order.  The tile loader and the CSR row sweep
+// are row_walk.hpp's, the ones counts.hip and counts_sparse.hip use.  Unstored entries contribute exactly 0
 // in all three modes (expm1(0) = 0), so the sums run over the stored entries; a row with keep == 0 contributes nothing.
 // Every row range is clamped to [0, nnz] and a column index outside the tile (so outside [0, P)) is skipped: a malformed
 // matrix gives wrong sums but is never followed outside its buffers.
@@ -34,7 +35,7 @@
 // launches of one call are ordered on the stream).
 #include <math.h>
 
-#include "common.hpp"
+#include "row_walk.hpp"
 
 namespace gpsa {
 
@@ -76,33 +77,6 @@ __device__ __forceinline__ double mom_value(float y, double sc) {
 }
 __device__ __forceinline__ double mom_nonfinite(double t) { return fabs(t) < INFINITY ? 0.0 : 1.0; }  // (a NaN: 1)
 
-// the column inside the tile of a lane's k-th value
-template <bool VEC>
-__device__ __forceinline__ int mom_tile_col(int lane, int k) {
-  return VEC ? (k >> 2) * 256 + lane * 4 + (k & 3) : k * WAVE + lane;
-}
-
-// a lane's 8 values of the row at `row` in the tile that starts at column c0; columns beyond P read as 0
-template <bool VEC>
-__device__ __forceinline__ void mom_load_row(const float* row, long long c0, long long P, int lane,
-                                             float (&v)[MOM_PER_LANE]) {
-  if (VEC) {
-#pragma unroll
-    for (int j = 0; j < MOM_PER_LANE / 4; ++j) {
-      const long long c = c0 + j * 256 + lane * 4;
-      float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c < P) q = *reinterpret_cast<const float4*>(row + c);  // P % 4 == 0: c + 3 < P
-      v[4 * j] = q.x, v[4 * j + 1] = q.y, v[4 * j + 2] = q.z, v[4 * j + 3] = q.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < MOM_PER_LANE; ++k) {
-      const long long c = c0 + k * WAVE + lane;
-      v[k] = c < P ? row[c] : 0.f;
-    }
-  }
-}
-
 // rows [blockIdx.x * R, ...) of the view Y [n, P] (scale: the view's first entry); see the head of the file
 template <int MODE, bool VEC>
 __global__ void __launch_bounds__(256)
@@ -121,9 +95,9 @@ moments_walk_kernel(const float* __restrict__ Y, long long n, long long P, int R
 #pragma unroll
     for (int k = 0; k < MOM_PER_LANE; ++k) a[0][k] = 0.0, a[1][k] = 0.0, a[2][k] = 0.0;
     float cur[MOM_PER_LANE] = {}, nxt[MOM_PER_LANE] = {};
-    if (w < rows) mom_load_row<VEC>(Yg + (long long)w * P, c0, P, lane, cur);
+    if (w < rows) load_row<VEC, MOM_PER_LANE>(Yg + (long long)w * P, c0, P, lane, cur);
     for (int r = w; r < rows; r += 4) {
-      if (r + 4 < rows) mom_load_row<VEC>(Yg + (long long)(r + 4) * P, c0, P, lane, nxt);
+      if (r + 4 < rows) load_row<VEC, MOM_PER_LANE>(Yg + (long long)(r + 4) * P, c0, P, lane, nxt);
       const double sc = MODE == MOM_SCALE ? scale[r0 + r] : 0.0;
 #pragma unroll
       for (int k = 0; k < MOM_PER_LANE; ++k) {
@@ -132,7 +106,7 @@ moments_walk_kernel(const float* __restrict__ Y, long long n, long long P, int R
         a[1][k] += t * t;
         a[2][k] += fabs(t);
         // a column beyond P read as 0, and 0 times a non-finite scale is a NaN that no entry of the matrix holds
-        nbad += (c0 + mom_tile_col<VEC>(lane, k) < P) ? mom_nonfinite(t) : 0.0;
+        nbad += (c0 + tile_col<VEC>(lane, k) < P) ? mom_nonfinite(t) : 0.0;
       }
 #pragma unroll
       for (int k = 0; k < MOM_PER_LANE; ++k) cur[k] = nxt[k];
@@ -141,22 +115,18 @@ moments_walk_kernel(const float* __restrict__ Y, long long n, long long P, int R
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
 #pragma unroll
-      for (int k = 0; k < MOM_PER_LANE; ++k) cs[w][mom_tile_col<VEC>(lane, k)] = a[q][k];
+      for (int k = 0; k < MOM_PER_LANE; ++k) cs[w][tile_col<VEC>(lane, k)] = a[q][k];
       __syncthreads();
       for (int cc = threadIdx.x; cc < MOM_COL_TILE; cc += 256) {
         const long long c = c0 + cc;
         if (c >= P) break;
-        planes[q][(long long)blockIdx.x * P + c] = ((cs[0][cc] + cs[1][cc]) + cs[2][cc]) + cs[3][cc];
+        planes[q][(long long)blockIdx.x * P + c] = meet4(cs, cc);
       }
       __syncthreads();  // before the next quantity lands in cs
     }
   }
   const double tot = block_sum(nbad, red);
   if (threadIdx.x == 0) bad[blockIdx.x] = tot;
-}
-
-__device__ __forceinline__ long long mom_clamp(long long v, long long lo, long long hi) {
-  return v < lo ? lo : (v > hi ? hi : v);
 }
 
 // block (blockIdx.x = column tile, blockIdx.y = row group) of the view's rows [a, a + n) of the CSR matrix; scale and
@@ -178,45 +148,21 @@ moments_csr_walk_kernel(const long long* __restrict__ crow, const int* __restric
   __syncthreads();
   double nbad = 0.0;
   for (long long i = r0 + w; i < r1; i += 4) {
-    const long long s = mom_clamp(crow[i], 0, nnz), e = mom_clamp(crow[i + 1], s, nnz);
-    const long long len = (keep != nullptr && keep[i] == 0) ? 0 : e - s;
-    // the first entry at or beyond c0 lies in [lo, hi]: 64 probes per round (wave-uniform lo, hi)
-    long long lo = 0, hi = len;
-    while (hi - lo > WAVE) {
-      const long long step = (hi - lo + WAVE - 1) / WAVE, p = lo + lane * step;
-      const bool before = p < hi && (long long)col[s + p] < c0;
-      const long long cnt = __popcll(__builtin_amdgcn_ballot_w64(before));
-      if (cnt == 0) {
-        hi = lo;
-      } else {
-        hi = min(hi, lo + cnt * step);
-        lo = lo + (cnt - 1) * step + 1;
-      }
-    }
     const double sc = MODE == MOM_SCALE ? scale[i] : 0.0;
-    for (long long pos = lo; pos < len; pos += WAVE) {
-      const long long k = pos + lane;
-      long long c = c1;
-      float y = 0.f;
-      if (k < len) c = col[s + k], y = val[s + k];
-      const bool below = k < len && c < c1;
-      if (below && c >= c0) {  // c0 <= c < c1 <= P: inside the tile, inside the plane
-        const int cc = (int)(c - c0);
-        const double tv = mom_value<MODE>(y, sc);
-        c1s[w][cc] += tv;
-        c2s[w][cc] += tv * tv;
-        c3s[w][cc] += fabs(tv);
-        nbad += mom_nonfinite(tv);
-      }
-      if (__popcll(__builtin_amdgcn_ballot_w64(below)) < WAVE) break;  // the row's end, or an entry beyond the tile
-    }
+    csr_row_in_tile(crow, col, val, keep, i, nnz, c0, c1, lane, [&](int cc, float y) {
+      const double tv = mom_value<MODE>(y, sc);
+      c1s[w][cc] += tv;
+      c2s[w][cc] += tv * tv;
+      c3s[w][cc] += fabs(tv);
+      nbad += mom_nonfinite(tv);
+    });
   }
   __syncthreads();
   // the four waves' columns meet in wave order
   for (int cc = threadIdx.x; cc < (int)(c1 - c0); cc += 256) {
-    p0[g * P + c0 + cc] = ((c1s[0][cc] + c1s[1][cc]) + c1s[2][cc]) + c1s[3][cc];
-    p1[g * P + c0 + cc] = ((c2s[0][cc] + c2s[1][cc]) + c2s[2][cc]) + c2s[3][cc];
-    p2[g * P + c0 + cc] = ((c3s[0][cc] + c3s[1][cc]) + c3s[2][cc]) + c3s[3][cc];
+    p0[g * P + c0 + cc] = meet4(c1s, cc);
+    p1[g * P + c0 + cc] = meet4(c2s, cc);
+    p2[g * P + c0 + cc] = meet4(c3s, cc);
   }
   const double tot = block_sum(nbad, red);
   if (threadIdx.x == 0) bad[g * gridDim.x + t] = tot;
@@ -248,9 +194,9 @@ moments_fold_kernel(const double* __restrict__ p0, const double* __restrict__ p1
   s0[seg][lane] = x0, s1[seg][lane] = x1, s2[seg][lane] = x2;
   __syncthreads();
   if (seg != 0 || c >= P) return;
-  o0[c] = ((x0 + s0[1][lane]) + s0[2][lane]) + s0[3][lane];
-  o1[c] = ((x1 + s1[1][lane]) + s1[2][lane]) + s1[3][lane];
-  o2[c] = ((x2 + s2[1][lane]) + s2[2][lane]) + s2[3][lane];
+  o0[c] = sum4(x0, s0[1][lane], s0[2][lane], s0[3][lane]);
+  o1[c] = sum4(x1, s1[1][lane], s1[2][lane], s1[3][lane]);
+  o2[c] = sum4(x2, s2[1][lane], s2[2][lane], s2[3][lane]);
 }
 
 // one workgroup: the views' counts (whole numbers held as doubles: exact in any order) -> the one int64
@@ -267,11 +213,8 @@ moments_finish_kernel(const double* __restrict__ slot, int V, long long* __restr
 static int mom_args_check(int mode, const void* scale, const long long* view_off, int V, long long N, const void* s1,
                           const void* s2, const void* abs1, const void* n_nonfinite) {
   if (mode < MOM_IDENTITY || mode > MOM_SCALE || (mode == MOM_SCALE && scale == nullptr)) return GPSA_EINVAL;
-  if (!view_off || V < 1 || !s1 || !s2 || !abs1 || !n_nonfinite) return GPSA_EINVAL;
-  if (view_off[0] != 0 || view_off[V] != N) return GPSA_EINVAL;
-  for (int v = 0; v < V; ++v)
-    if (view_off[v + 1] <= view_off[v]) return GPSA_EINVAL;  // an empty view has no moments
-  return 0;
+  if (!s1 || !s2 || !abs1 || !n_nonfinite) return GPSA_EINVAL;
+  return view_off_check(view_off, V, N);
 }
 
 static int mom_fold(hipStream_t st, const MomWorkspace& ws, long long G, long long P, long long nbad, int v, double* s1,
@@ -361,9 +304,7 @@ int gpsa_column_moments_csr_f32(int mode, const long long* crow, const int* col,
                                 const long long* view_off, int V, double* s1, double* s2, double* abs1,
                                 long long* n_nonfinite, void* workspace, long long workspace_bytes, void* stream) {
   using namespace gpsa;
-  if (crow == nullptr || N < 1 || P < 1 || P > 0x7fffffffLL || N > 0x7fffffffLL) return GPSA_EINVAL;
-  if (nnz < 0 || nnz > N * P) return GPSA_EINVAL;  // (N, P < 2^31: no overflow)
-  if (nnz > 0 && (col == nullptr || val == nullptr)) return GPSA_EINVAL;
+  if (int rc = csr_shape_check(crow, col, val, N, P, nnz)) return rc;
   if (int rc = mom_args_check(mode, scale, view_off, V, N, s1, s2, abs1, n_nonfinite)) return rc;
   if (workspace == nullptr || workspace_bytes < gpsa_column_moments_csr_workspace(N, P, V)) return GPSA_EWORKSPACE;
   hipStream_t st = as_stream(stream);

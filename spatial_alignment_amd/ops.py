@@ -95,6 +95,16 @@ class HipOps:
     def _c(t):
         return t if t.is_contiguous() else t.contiguous()
 
+    @staticmethod
+    def _f64(t):
+        t = t if t.dtype == torch.float64 else t.double()
+        return t if t.is_contiguous() else t.contiguous()
+
+    @staticmethod
+    def _f32(t):
+        t = t if t.dtype == torch.float32 else t.float()
+        return t if t.is_contiguous() else t.contiguous()
+
     # ------------------------------------------------------------------ covariance matrices
     @staticmethod
     def _cov_args(Z, X, ls_u, var_u):
@@ -893,19 +903,27 @@ class HipOps:
         nbytes = self._wsq("gpsa_count_workspace", N, P)
         return self._ws(nbytes, like), nbytes
 
+    @staticmethod
+    def _margin_outputs(N, P, dev):
+        f, i = torch.float64, torch.int64  # row_sum, col_sum, row_nnz, col_nnz, n_invalid
+        return tuple(torch.empty(n, dtype=dt, device=dev) for n, dt in ((N, f), (P, f), (N, i), (P, i), (1, i)))
+
+    @staticmethod
+    def _view_offsets(what, view_off, N):
+        off = [int(v) for v in view_off]  # V + 1 of them
+        if len(off) < 2 or off[0] != 0 or off[-1] != N or any(b <= a for a, b in zip(off, off[1:])):
+            raise ValueError(f"{what}: view_off {off} must rise strictly from 0 to N = {N}")
+        return off, len(off) - 1
+
     def count_margins(self, Y):
         """gpsa_count_margins_f32: one read of Y [N, P] fp32 -> (row_sum [N] fp64, col_sum [P] fp64, row_nnz [N] int64,
         col_nnz [P] int64, n_invalid [1] int64 on the device: the entries that are NaN, +-inf or < 0)"""
         N, P = self._count_matrix(Y, "count_margins")
-        dev = Y.device
-        rs, cs = torch.empty(N, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev)
-        rn, cn = torch.empty(N, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.int64, device=dev)
-        bad = torch.empty(1, dtype=torch.int64, device=dev)
+        out = self._margin_outputs(N, P, Y.device)
         ws, nbytes = self._count_ws(N, P, Y)
-        rc = self.lib.gpsa_count_margins_f32(_p(Y), N, P, _p(rs), _p(cs), _p(rn), _p(cn), _p(bad), _p(ws), nbytes,
-                                             self._stream(Y))
+        rc = self.lib.gpsa_count_margins_f32(_p(Y), N, P, *map(_p, out), _p(ws), nbytes, self._stream(Y))
         _lib.check(rc, "gpsa_count_margins_f32")
-        return rs, cs, rn, cn, bad
+        return out
 
     def count_deviance(self, Y, log_sz):
         """gpsa_count_deviance_f32: (ll_sat, abs_sat) [P] fp64 with ll_sat[g] = sum_i y log y - y log_sz_i and
@@ -944,10 +962,7 @@ class HipOps:
         """gpsa_standardize_views_f32: (y - mean) / std per (view, column) over the row ranges view_off (a list of V + 1
         ints, 0 ... N) -> (out [N, P] fp32, n_constant [V] int64 on the device); a column constant within a view: 0"""
         N, P = self._count_matrix(Y, "standardize_views")
-        off = [int(v) for v in view_off]
-        V = len(off) - 1
-        if V < 1 or off[0] != 0 or off[-1] != N or any(b <= a for a, b in zip(off, off[1:])):
-            raise ValueError(f"standardize_views: view_off {off} must rise strictly from 0 to N = {N}")
+        off, V = self._view_offsets("standardize_views", view_off, N)
         if out is None:
             out = torch.empty_like(Y)
         self._count_out(out, N, P, "standardize_views")
@@ -998,15 +1013,12 @@ class HipOps:
         """gpsa_count_margins_csr_f32: count_margins of the CSR matrix [N, P]; ``keep`` [N] bool: rows to take"""
         nnz = self._csr_arrays(crow, col, val, N, P, "count_margins_csr")
         keep = self._csr_keep(keep, N, "count_margins_csr")
-        dev = crow.device
-        rs, cs = torch.empty(N, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev)
-        rn, cn = torch.empty(N, dtype=torch.int64, device=dev), torch.empty(P, dtype=torch.int64, device=dev)
-        bad = torch.empty(1, dtype=torch.int64, device=dev)
+        out = self._margin_outputs(N, P, crow.device)
         ws, nbytes = self._csr_ws(N, P, crow)
-        rc = self.lib.gpsa_count_margins_csr_f32(_p(crow), _p(col), _p(val), _p(keep), N, P, nnz, _p(rs), _p(cs), _p(rn),
-                                                 _p(cn), _p(bad), _p(ws), nbytes, self._stream(crow))
+        rc = self.lib.gpsa_count_margins_csr_f32(_p(crow), _p(col), _p(val), _p(keep), N, P, nnz, *map(_p, out), _p(ws),
+                                                 nbytes, self._stream(crow))
         _lib.check(rc, "gpsa_count_margins_csr_f32")
-        return rs, cs, rn, cn, bad
+        return out
 
     def count_deviance_csr(self, crow, col, val, N, P, log_sz, keep=None):
         """gpsa_count_deviance_csr_f32: count_deviance of the CSR matrix; log_sz [N] fp64 by the original row"""
@@ -1126,10 +1138,7 @@ class HipOps:
         """-> (mode number, offsets, V, scale as a contiguous fp64 [N] or None)"""
         if mode not in self.MOMENT_MODES:
             raise ValueError(f"{what}: mode must be one of {sorted(self.MOMENT_MODES)}, not {mode!r}")
-        off = [int(v) for v in view_off]
-        V = len(off) - 1
-        if V < 1 or off[0] != 0 or off[-1] != N or any(b <= a for a, b in zip(off, off[1:])):
-            raise ValueError(f"{what}: view_off {off} must rise strictly from 0 to N = {N}")
+        off, V = self._view_offsets(what, view_off, N)
         if mode == "normalize":
             if scale is None or scale.dim() != 1 or scale.shape[0] != N:
                 raise ValueError(f"{what}: mode 'normalize' needs scale [{N}]")
@@ -1172,16 +1181,6 @@ class HipOps:
                                                   _p(ws), nbytes, self._stream(crow))
         _lib.check(rc, "gpsa_column_moments_csr_f32")
         return s1, s2, ab, bad
-
-    @staticmethod
-    def _f64(t):
-        t = t if t.dtype == torch.float64 else t.double()
-        return t if t.is_contiguous() else t.contiguous()
-
-    @staticmethod
-    def _f32(t):
-        t = t if t.dtype == torch.float32 else t.float()
-        return t if t.is_contiguous() else t.contiguous()
 
     def warp_sample_fwd(self, meanT, v, q, var_u, X, slopes, intercept, eps):
         """-> Gmean [n,D], Gs [S,n,D] (fp32), bad [blocks] (int32 flags), Gs64 [S,n,D] (the draws unrounded)"""

@@ -87,6 +87,7 @@ def test_the_entries_are_declared_and_bound(name, res, n_args):
     src = open(os.path.join(ROOT, "spatial_alignment_amd", "csrc", "counts.hip")).read()
     assert re.search(r"\b" + res + r"\s+" + name + r"\s*\(", src)
     assert "atomic" not in src.lower()  # comments included
+    assert "atomic" not in open(os.path.join(ROOT, "spatial_alignment_amd", "csrc", "row_walk.hpp")).read().lower()  # ... and the header the count units share
 
 
 def test_the_constants_python_exports_are_the_kernels():

@@ -52,6 +52,7 @@ def test_the_entries_are_declared_bound_and_defined(name, res, n_args):
     src = _source()
     assert re.search(r"\b" + res + r"\s+" + name + r"\s*\(", src)
     assert "atomic" not in src.lower()  # comments included
+    assert "atomic" not in open(os.path.join(ROOT, "spatial_alignment_amd", "csrc", "row_walk.hpp")).read().lower()  # ... and the header the count units share
     assert "defence in depth" in raw.lower()
 
 
@@ -259,7 +260,7 @@ def _run(Y, ns, index=i64, **kw):
     crow, col, val = _to_csr(Y, index)
     A = counts._checked(fake, crow.to(i64), col.to(i32), val, Y.shape, "csr_counts")
     before = [t.clone() for t in (A.crow, A.col, A.values)]
-    res = counts._prepare_sparse(fake, A, ns, **args)
+    res = counts._prepare(fake, A, ns, **args)
     assert all(torch.equal(a, b) for a, b in zip(before, (A.crow, A.col, A.values)))
     return fake, res, cu.prepare(Y, ns, **args)
 

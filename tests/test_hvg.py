@@ -143,6 +143,7 @@ def test_the_entries_are_declared_bound_and_defined(name, res, n_args):
     src = _source()
     assert re.search(r"\b" + res + r"\s+" + name + r"\s*\(", src)
     assert "atomic" not in src.lower()  # comments included
+    assert "atomic" not in open(os.path.join(ROOT, "spatial_alignment_amd", "csrc", "row_walk.hpp")).read().lower()  # ... and the header the count units share
 
 
 def test_the_constants_python_exports_are_the_kernels():
@@ -385,7 +386,7 @@ def test_prepare_counts_seurat_follows_the_yardsticks_pipeline(transform, n_top)
     fake = FakeMomentOps()
     crow, col, val = _to_csr(Y)
     A = counts._checked(fake, crow, col.to(i32), val, Y.shape, "csr_counts")
-    res2 = counts._prepare_sparse(fake, A, ns, selection="seurat", **kw)
+    res2 = counts._prepare(fake, A, ns, selection="seurat", **kw)
     _check_prepared(res2, want, Y)
     assert torch.equal(res2.outputs, res.outputs) and torch.equal(res2.genes, res.genes)
     assert len(fake.calls) == 1 and fake.calls[0][:4] == ("moments_csr", (120, 60), "normalize", [0, 120])
