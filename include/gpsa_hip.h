@@ -279,7 +279,11 @@ int gpsa_whiten_f64(const double* Kinv, int in_dtype, const void* Kuf, int M, lo
 
 /* Y = op(P) X with P [M,M] (stored as p_dtype, op = transpose when transP), X [M,C] and Y in dtype
  * (+ optional colsq[c] = sum_m Y[m,c]^2, may be NULL).
- * The whitening products beta = L^-1 K_uf, alpha = L^-T beta of vgpsa.py:177-180 and their adjoints. */
+ * The whitening products beta = L^-1 K_uf, alpha = L^-T beta of vgpsa.py:177-180 and their adjoints.
+ * workspace: fp32 with M <= 256 (the matrix-core kernel; MP = M rounded up to 32, 64, 112, 208 or 256 rows) takes
+ * 4 MP (MP + 64) bytes - the packed operand and four 16-column chunks of slack that its staging ring requests and never
+ * multiplies - and returns GPSA_EWORKSPACE below that; every other case takes a copy of P in dtype (M M elements,
+ * rounded up to 256 bytes) when p_dtype != dtype and nothing else. */
 int gpsa_panel_mm(int dtype, int p_dtype, int transP, const void* P, const void* X, int M, long long C,
                   void* Y, void* colsq, void* workspace, long long workspace_bytes, void* stream);
 

@@ -835,6 +835,10 @@ static inline PanelWs keep_ws(int MB, int L) {
   const long long pk = packed_bytes(MB, L), slack = 4LL * MB * 16 * 16 * 4;
   return {pk, slack, pk + slack};
 }
+// gpsa_panel_mm (MB <= 16, one matrix): the same ring behind the same packed operand, so the same slack.  The entry used
+// to accept a workspace of packed_bytes(MB, 1) alone, and every workgroup of panel_mfma_kernel<STORE> then requested the
+// chunk behind it (tests/test_contraction_shapes.py holds the refusal one byte below this total).
+static inline PanelWs store_ws(int MB) { return keep_ws(MB, 1); }
 // gpsa_quadform_elbo_f32 / _x3_f32 (total 0: no fused kernel for this shape).  fp32: slabs for two workgroups per CU,
 // whatever the shape's own grid (gpsa_quadform_elbo_parts).  x3: the packed operand is pack_x3_kernel's three-plane bf16
 // image, one workgroup per CU, and two chunks of slack for the ring stages that walk past the last chunk.
@@ -1713,7 +1717,7 @@ int gpsa_panel_mm(int dtype, int p_dtype, int transP, const void* P, const void*
   if (dtype == GPSA_F32) {
     const int MB = mfma_mb_for(M);
     if (MB && MB <= MB_MAX_STORE && !force_generic()) {
-      if (workspace_bytes < packed_bytes(MB, 1)) return GPSA_EWORKSPACE;
+      if (workspace_bytes < store_ws(MB).total) return GPSA_EWORKSPACE;
       return panel_mfma_launch<MODE_STORE>(MB, p_dtype, P, tp, (float*)workspace, (const float*)X, nullptr, M, C, 1,
                                            (float*)Y, (float*)colsq, 1.f, nullptr, st);
     }
