@@ -1352,6 +1352,62 @@ int gpsa_image_sample_u8(const unsigned char* img, long long H, long long W, int
 int gpsa_image_sample_f32(const float* img, long long H, long long W, int C, const double* xy, long long n, int order,
                           float fill, float* out, unsigned char* valid, void* stream);
 
+/* ---- spatial autocorrelation (csrc/autocorr.hip): the weight graph, its sums, the permuted Moran / Geary numerators ------
+ * The graph is CSR on the device: crow [n + 1] int64, col [nnz] int32 ascending within a row, w [nnz] fp64 (col and w may
+ * be NULL when nnz == 0).  No atomics, every sum fp64 in a fixed order, one writer per output element, the same bits on
+ * a repeated call; nothing of n x n is allocated; the *_workspace queries are pure host functions (0 for sizes an entry
+ * refuses).
+ *
+ * gpsa_graph_merge_count / _write: the graph out of kNN lists.  out [n, k] int32: every row's k neighbours ASCENDING by
+ *   index (the caller sorts the kNN lists), no self entry; in_src [n k] int32 / in_ptr [n + 1] int64: the rows that list
+ *   row i are in_src[in_ptr[i] .. in_ptr[i + 1]), ascending (a stable sort of the flattened lists by target).  kind 0: the
+ *   row is its out-list (in_ptr / in_src may be NULL); 1: the union of the two lists; 2: their intersection (a row may be
+ *   empty).  _count writes crow [n + 1] (row lengths, then one workgroup's prefix sum); the caller reads nnz = crow[n] and
+ *   _write fills col (ascending) and w = 1, or 1 / (row length) when row_standardize != 0.  One thread merges one row.
+ * gpsa_graph_check_f64: out [5] int64 on the device = the number of crow violations (crow[0] != 0, a decrease, crow[n] !=
+ *   nnz); of columns outside [0, n); of places inside a row where the column does not strictly increase; of self edges;
+ *   of weights that are NaN, infinite or < 0.  Every read is bounded: row ranges are clamped to [0, nnz].
+ * gpsa_graph_sums_f64: out [3] fp64 on the device = S0 = sum w;  S1 = 1/2 sum_ij (w_ij + w_ji)^2, per stored edge
+ *   1/2 (w_ij + w_ji)^2 where the reverse edge is stored (binary search in row j) and w_ij^2 where it is not;  S2 =
+ *   sum_i (w_i. + w_.i)^2, the column sum over the transposed structure: tperm [nnz] int64 = the positions of the entries
+ *   in the order of a stable sort by column, tptr [n + 1] int64 = where each column starts in it.  A thread per row, the
+ *   rows of a workgroup (256) added in row order, the workgroups in order.  Indices outside their arrays are skipped.
+ * gpsa_graph_check_f64 and gpsa_graph_sums_f64 take workspace >= gpsa_graph_workspace(n) bytes.
+ *
+ * gpsa_autocorr_perm_f64: Z [n, P] fp64 row-major (a column-centred matrix), perms [R, n] int32, mode 0 | 1 ->
+ *   mode 0 (Moran):  num[r, p] = sum_i Z[pi_r(i), p] * sum_{j in row i} w_ij Z[pi_r(j), p]
+ *   mode 1 (Geary):  num[r, p] = sum_i sum_{j in row i} w_ij (Z[pi_r(i), p] - Z[pi_r(j), p])^2
+ *   num [R, P] fp64.  The permuted matrix never exists: rows of Z are gathered through perms, a wave's lanes run over 64
+ *   consecutive genes (a gathered row is one coalesced read), it carries 4 permutations (4 rows in flight per neighbour
+ *   position) and a workgroup 16, which share one read of the rows' crow / col / w.  Within a row j runs in CSR order
+ *   (explicit fma), the rows ascend within a row group, the row groups - ceil(n / max(32, ceil(n / 32))) of them, a
+ *   function of n alone - are added in ascending order by a second kernel: num[r, p] is the same bits whatever R, P
+ *   or the other rows of perms are, so an identity row anywhere equals the observed statistic exactly.  A row longer
+ *   than a wave is walked 64 positions at a time; an empty row contributes nothing.
+ *   No read outside Z: an entry of perms or col outside [0, n) is not followed (a bad pi_r(i) drops row i of permutation
+ *   r, a bad col or pi_r(j) drops that edge) and *n_bad (one int64 on the device) is the number of such entries of perms
+ *   and col, each counted once.  Row ranges are clamped to [0, nnz].  perms is not checked to hold permutations.
+ *   workspace >= gpsa_autocorr_perm_workspace(n, P, R) bytes: the groups' partials, 8 G R P, and 2 KiB.
+ *
+ * GPSA_EINVAL: a NULL pointer (in_ptr / in_src with kind 0, col / w with nnz == 0 excepted), n, k, P or R < 1, nnz < 0,
+ * an unknown kind or mode;  GPSA_EUNSUPPORTED: n or P >= 2^31, R > 16 * 65535;  GPSA_EWORKSPACE: a workspace that is NULL
+ * or short.  Every check runs before the first launch. */
+long long gpsa_graph_workspace(long long n);
+int gpsa_graph_merge_count(const int* out, const long long* in_ptr, const int* in_src, long long n, int k, int kind,
+                           long long* crow, void* stream);
+int gpsa_graph_merge_write(const int* out, const long long* in_ptr, const int* in_src, long long n, int k, int kind,
+                           int row_standardize, const long long* crow, long long nnz, int* col, double* w,
+                           void* stream);
+int gpsa_graph_check_f64(const long long* crow, const int* col, const double* w, long long n, long long nnz,
+                         long long* out, void* workspace, long long workspace_bytes, void* stream);
+int gpsa_graph_sums_f64(const long long* crow, const int* col, const double* w, const long long* tptr,
+                        const long long* tperm, long long n, long long nnz, double* out, void* workspace,
+                        long long workspace_bytes, void* stream);
+long long gpsa_autocorr_perm_workspace(long long n, long long P, long long R);
+int gpsa_autocorr_perm_f64(const double* Z, long long n, long long P, const long long* crow, const int* col,
+                           const double* w, long long nnz, const int* perms, long long R, int mode, double* num,
+                           long long* n_bad, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

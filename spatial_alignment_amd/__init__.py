@@ -2,6 +2,7 @@
 
 Same public names as the reference package (gpsa/__init__.py:1-10) for the parts on the hot path.
 """
+from .autocorr import SpatialGraph, fdr_bh, spatial_autocorr, spatial_graph
 from .counts import (
     CSRCounts,
     column_moments,
@@ -57,6 +58,10 @@ __all__ = [
     "kth_neighbor_distance",
     "moran_i",
     "alignment_score",
+    "spatial_graph",
+    "SpatialGraph",
+    "spatial_autocorr",
+    "fdr_bh",
     "count_stats",
     "size_factors",
     "poisson_deviance",

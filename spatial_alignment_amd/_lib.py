@@ -280,6 +280,14 @@ SIGNATURES.update({
                                          _vp]),
     "gpsa_image_sample_u8": (_i, [_vp, _ll, _ll, _i, _vp, _ll, _i, C.c_float, _vp, _vp, _vp]),
     "gpsa_image_sample_f32": (_i, [_vp, _ll, _ll, _i, _vp, _ll, _i, C.c_float, _vp, _vp, _vp]),
+    # spatial autocorrelation: the weight graph in CSR, its sums, the permuted Moran / Geary numerators (csrc/autocorr.hip)
+    "gpsa_graph_workspace": (_ll, [_ll]),
+    "gpsa_graph_merge_count": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp, _vp]),
+    "gpsa_graph_merge_write": (_i, [_vp, _vp, _vp, _ll, _i, _i, _i, _vp, _ll, _vp, _vp, _vp]),
+    "gpsa_graph_check_f64": (_i, [_vp, _vp, _vp, _ll, _ll, _vp, _vp, _ll, _vp]),
+    "gpsa_graph_sums_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _ll, _vp]),
+    "gpsa_autocorr_perm_workspace": (_ll, [_ll, _ll, _ll]),
+    "gpsa_autocorr_perm_f64": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _vp, _ll, _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

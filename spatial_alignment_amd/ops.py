@@ -1051,6 +1051,113 @@ class HipOps:
         _lib.check(rc, "gpsa_csr_gather_dense_f32")
         return out
 
+    # ------------------------------------------------------------------ spatial autocorrelation (csrc/autocorr.hip)
+    GRAPH_KINDS = {"none": 0, "union": 1, "mutual": 2}
+    AUTOCORR_MODES = {"moran": 0, "geary": 1}
+
+    @staticmethod
+    def _graph_arrays(crow, col, w, n, what):
+        """crow [n + 1] int64, col [nnz] int32, w [nnz] fp64, contiguous, on a device -> nnz"""
+        n = int(n)
+        ok = (n >= 1 and all(torch.is_tensor(t) for t in (crow, col, w)) and crow.dtype == torch.int64
+              and tuple(crow.shape) == (n + 1,) and col.dtype == torch.int32 and col.dim() == 1
+              and w.dtype == torch.float64 and w.shape == col.shape
+              and crow.is_contiguous() and col.is_contiguous() and w.is_contiguous())
+        if not ok:
+            sh = lambda t: f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"{what}: a graph on {n} rows needs contiguous crow int64 [{n + 1}], col int32 [nnz] and "
+                             f"w fp64 [nnz], not {sh(crow)}, {sh(col)}, {sh(w)}")
+        for name, t in (("crow", crow), ("col", col), ("w", w)):
+            if not t.is_cuda:
+                raise ValueError(f"{what}: {name} is on device {str(t.device)!r}; the graph kernels run on the GPU only")
+        return int(col.numel())
+
+    def graph_merge(self, out_sorted, in_ptr, in_src, kind="none", row_standardize=True):
+        """gpsa_graph_merge_count / _write: the kNN lists out_sorted [n, k] int32 (each row ascending) and, for "union" /
+        "mutual", the in-lists in_src [n k] int32 at in_ptr [n + 1] int64 -> (crow [n + 1] int64, col [nnz] int32,
+        w [nnz] fp64).  One host read (nnz) between the two passes."""
+        if kind not in self.GRAPH_KINDS:
+            raise ValueError(f"graph_merge: kind must be 'none', 'union' or 'mutual', not {kind!r}")
+        code = self.GRAPH_KINDS[kind]
+        if out_sorted.dim() != 2 or out_sorted.dtype != torch.int32 or not out_sorted.is_contiguous() \
+                or out_sorted.shape[0] < 1 or out_sorted.shape[1] < 1:
+            raise ValueError(f"graph_merge: out_sorted must be a contiguous int32 [n >= 1, k >= 1], not {out_sorted.dtype} "
+                             f"{tuple(out_sorted.shape)}")
+        n, k = (int(s) for s in out_sorted.shape)
+        if code:
+            if (in_ptr is None or in_src is None or in_ptr.dtype != torch.int64 or tuple(in_ptr.shape) != (n + 1,)
+                    or in_src.dtype != torch.int32 or tuple(in_src.shape) != (n * k,) or not in_ptr.is_contiguous()
+                    or not in_src.is_contiguous()):
+                raise ValueError(f"graph_merge: kind {kind!r} needs in_ptr int64 [{n + 1}] and in_src int32 [{n * k}]")
+        else:
+            in_ptr = in_src = None
+        dev, st = out_sorted.device, self._stream(out_sorted)
+        crow = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        rc = self.lib.gpsa_graph_merge_count(_p(out_sorted), _p(in_ptr), _p(in_src), n, k, code, _p(crow), st)
+        _lib.check(rc, "gpsa_graph_merge_count")
+        nnz = int(crow[n])
+        col = torch.empty(nnz, dtype=torch.int32, device=dev)
+        w = torch.empty(nnz, dtype=torch.float64, device=dev)
+        rc = self.lib.gpsa_graph_merge_write(_p(out_sorted), _p(in_ptr), _p(in_src), n, k, code, int(bool(row_standardize)),
+                                             _p(crow), nnz, _p(col), _p(w), st)
+        _lib.check(rc, "gpsa_graph_merge_write")
+        return crow, col, w
+
+    def graph_check(self, crow, col, w, n):
+        """gpsa_graph_check_f64 -> [5] int64 on the device: crow violations, columns outside [0, n), places where the
+        column does not strictly increase within a row, self edges, weights that are not finite or < 0"""
+        nnz = self._graph_arrays(crow, col, w, n, "graph_check")
+        out = torch.empty(5, dtype=torch.int64, device=crow.device)
+        nbytes = self._wsq("gpsa_graph_workspace", int(n))
+        ws = self._ws(nbytes, crow)
+        rc = self.lib.gpsa_graph_check_f64(_p(crow), _p(col), _p(w), int(n), nnz, _p(out), _p(ws), nbytes, self._stream(crow))
+        _lib.check(rc, "gpsa_graph_check_f64")
+        return out
+
+    def graph_sums(self, crow, col, w, n, tptr, tperm):
+        """gpsa_graph_sums_f64 -> [3] fp64 on the device: S0, S1, S2; tperm [nnz] int64: the entries' positions in the
+        order of a stable sort by column, tptr [n + 1] int64: where each column starts in it"""
+        nnz = self._graph_arrays(crow, col, w, n, "graph_sums")
+        n = int(n)
+        if (tptr.dtype != torch.int64 or tuple(tptr.shape) != (n + 1,) or tperm.dtype != torch.int64
+                or tuple(tperm.shape) != (nnz,) or not tptr.is_contiguous() or not tperm.is_contiguous()):
+            raise ValueError(f"graph_sums: tptr must be int64 [{n + 1}] and tperm int64 [{nnz}], not {tptr.dtype} "
+                             f"{tuple(tptr.shape)}, {tperm.dtype} {tuple(tperm.shape)}")
+        out = torch.empty(3, dtype=torch.float64, device=crow.device)
+        nbytes = self._wsq("gpsa_graph_workspace", n)
+        ws = self._ws(nbytes, crow)
+        rc = self.lib.gpsa_graph_sums_f64(_p(crow), _p(col), _p(w), _p(tptr), _p(tperm), n, nnz, _p(out), _p(ws), nbytes,
+                                          self._stream(crow))
+        _lib.check(rc, "gpsa_graph_sums_f64")
+        return out
+
+    def autocorr_perm(self, Z, crow, col, w, perms, mode="moran", out=None):
+        """gpsa_autocorr_perm_f64: Z [n, P] fp64 (centred columns), the graph in CSR, perms [R, n] int32 ->
+        (num [R, P] fp64, n_bad [1] int64 on the device: the entries of perms and col outside [0, n), none of which is
+        followed).  ``mode`` "moran": sum_i z_i sum_j w_ij z_j, "geary": sum_ij w_ij (z_i - z_j)^2, z = Z's rows taken
+        through the permutation.  ``out``: num, preallocated."""
+        if mode not in self.AUTOCORR_MODES:
+            raise ValueError(f"autocorr_perm: mode must be 'moran' or 'geary', not {mode!r}")
+        if Z.dim() != 2 or Z.dtype != torch.float64 or not Z.is_contiguous() or Z.shape[0] < 1 or Z.shape[1] < 1:
+            raise ValueError(f"autocorr_perm: Z must be a contiguous fp64 [n >= 1, P >= 1], not {Z.dtype} {tuple(Z.shape)}")
+        n, P = (int(s) for s in Z.shape)
+        nnz = self._graph_arrays(crow, col, w, n, "autocorr_perm")
+        if perms.dim() != 2 or perms.dtype != torch.int32 or not perms.is_contiguous() or perms.shape[0] < 1 \
+                or perms.shape[1] != n:
+            raise ValueError(f"autocorr_perm: perms must be a contiguous int32 [R >= 1, {n}], not {perms.dtype} "
+                             f"{tuple(perms.shape)}")
+        R = int(perms.shape[0])
+        if out is None:
+            out = torch.empty(R, P, dtype=torch.float64, device=Z.device)
+        assert tuple(out.shape) == (R, P) and out.dtype == torch.float64 and out.is_contiguous(), (R, P)
+        n_bad = torch.empty(1, dtype=torch.int64, device=Z.device)
+        nbytes = self._wsq("gpsa_autocorr_perm_workspace", n, P, R)
+        ws = self._ws(nbytes, Z)
+        rc = self.lib.gpsa_autocorr_perm_f64(_p(Z), n, P, _p(crow), _p(col), _p(w), nnz, _p(perms), R,
+                                             self.AUTOCORR_MODES[mode], _p(out), _p(n_bad), _p(ws), nbytes, self._stream(Z))
+        _lib.check(rc, "gpsa_autocorr_perm_f64")
+        return out, n_bad
+
     # ------------------------------------------------------------------ histology images (csrc/image.hip)
     @staticmethod
     def _image(img, what):

@@ -20,6 +20,8 @@ each with
        ... closed as counts (prediction)    gpsa::predict_counts                       (predict.py, scale="response")
        the warp as a function of the point  gpsa::warp_field, gpsa::warp_invert        (warp.py; csrc/warp_field.hip)
        neighbour statistics                 gpsa::knn, gpsa::knn_average               (neighbors.py; csrc/neighbors.hip)
+       spatial autocorrelation              gpsa::graph_merge, gpsa::graph_check,      (autocorr.py; csrc/autocorr.hip)
+                                            gpsa::graph_sums, gpsa::autocorr_perm
        count preprocessing                  gpsa::count_margins, gpsa::count_deviance, (counts.py; csrc/counts.hip)
                                             gpsa::count_transform, gpsa::standardize_views
        ... from a CSR matrix                gpsa::csr_check, gpsa::count_margins_csr,  (counts.py; csrc/counts_sparse.hip)
@@ -345,6 +347,59 @@ def knn_average(idx: torch.Tensor, d2: Optional[torch.Tensor], Y: torch.Tensor, 
 @knn_average.register_fake
 def _(idx, d2, Y, weights="uniform"):
     return Y.new_empty(idx.shape[0], Y.shape[1], dtype=torch.float64 if Y.dtype == torch.float64 else torch.float32)
+
+
+# ... spatial autocorrelation: the weight graph in CSR, its sums, the permuted numerators (autocorr.py; csrc/autocorr.hip)
+@torch.library.custom_op("gpsa::graph_merge", mutates_args=(), device_types="cuda")
+def graph_merge(out_sorted: torch.Tensor, in_ptr: Optional[torch.Tensor], in_src: Optional[torch.Tensor],
+                kind: str = "none", row_standardize: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the kNN lists (rows ascending) and their in-lists merged per row: "none" | "union" | "mutual" ->
+    (crow [n + 1] int64, col [nnz] int32, w [nnz] fp64); nnz depends on the data"""
+    return _o().graph_merge(out_sorted, in_ptr, in_src, kind, row_standardize)
+
+
+@graph_merge.register_fake
+def _(out_sorted, in_ptr, in_src, kind="none", row_standardize=True):
+    n, k = out_sorted.shape
+    nnz = n * k if kind == "none" else torch.library.get_ctx().new_dynamic_size()
+    return (out_sorted.new_empty(n + 1, dtype=torch.int64), out_sorted.new_empty(nnz, dtype=torch.int32),
+            out_sorted.new_empty(nnz, dtype=torch.float64))
+
+
+@torch.library.custom_op("gpsa::graph_check", mutates_args=(), device_types="cuda")
+def graph_check(crow: torch.Tensor, col: torch.Tensor, w: torch.Tensor, n: int) -> torch.Tensor:
+    """[5] int64: crow violations, columns outside [0, n), places out of order within a row, self edges, bad weights"""
+    return _o().graph_check(crow, col, w, n)
+
+
+@graph_check.register_fake
+def _(crow, col, w, n):
+    return crow.new_empty(5, dtype=torch.int64)
+
+
+@torch.library.custom_op("gpsa::graph_sums", mutates_args=(), device_types="cuda")
+def graph_sums(crow: torch.Tensor, col: torch.Tensor, w: torch.Tensor, n: int, tptr: torch.Tensor,
+               tperm: torch.Tensor) -> torch.Tensor:
+    """[3] fp64: S0, S1, S2 of the graph, fixed-order sums; tptr / tperm: the transposed structure"""
+    return _o().graph_sums(crow, col, w, n, tptr, tperm)
+
+
+@graph_sums.register_fake
+def _(crow, col, w, n, tptr, tperm):
+    return w.new_empty(3, dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::autocorr_perm", mutates_args=(), device_types="cuda")
+def autocorr_perm(Z: torch.Tensor, crow: torch.Tensor, col: torch.Tensor, w: torch.Tensor, perms: torch.Tensor,
+                  mode: str = "moran") -> tuple[torch.Tensor, torch.Tensor]:
+    """the Moran / Geary numerator of Z [n, P] fp64 under every row of perms [R, n] int32 -> (num [R, P] fp64,
+    n_bad [1] int64); the permuted matrix is never formed"""
+    return _o().autocorr_perm(Z, crow, col, w, perms, mode)
+
+
+@autocorr_perm.register_fake
+def _(Z, crow, col, w, perms, mode="moran"):
+    return Z.new_empty(perms.shape[0], Z.shape[1], dtype=torch.float64), Z.new_empty(1, dtype=torch.int64)
 
 
 # ---------------------------------------------------------------------------------------------------------
