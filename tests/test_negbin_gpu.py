@@ -407,7 +407,8 @@ def test_quadform_elbo_nb(M, delta_form, masked):
 @pytest.mark.parametrize("masked", [True, False], ids=["masked", "unmasked"])
 def test_lmc_loglik_fused_nb(masked, L, P):
     """gpsa_lmc_loglik_fused_nb_f32 at exactly the queried workspace, pre-filled with NaN patterns: one case per
-    instantiation (L <= 16, <= 32, <= 64; P = 70 walks two chunks of outputs on the middle one)"""
+    instantiation (L <= 16, <= 32, <= 64).  Every case fits one chunk of outputs: the NB kernels walk 256, 128 and 64 of
+    them at a time, so P = 70 at L = 20 is one chunk of 128 (more than one chunk: tests/test_lmc_lik_gpu.py)"""
     lib = _build()
     N, S = 77, 2
     gen = torch.Generator().manual_seed(SEED + 3 + L)
