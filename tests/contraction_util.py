@@ -255,26 +255,27 @@ def split_cases(MB):
 
 
 # ---- named edge indices ------------------------------------------------------------------------------------------------
-def named_rows(M):
+def named_rows(M, extra=()):
     """rows of the contracted dimension at which a row-tile kernel can go wrong: the last row, the first row of the last
-    tile, both sides of its 8-row edge (RL = 2 against 4), and both sides of the first tile edge"""
+    tile, both sides of its 8-row edge (RL = 2 against 4), and both sides of the first tile edge; ``extra``: a kernel's own"""
     base = 16 * (mb_for(M) - 1) if mb_for(M) else 0
-    return sorted({r for r in (M - 1, base, base + 7, base + 8, 15, 16) if 0 <= r < M})
+    return sorted({r for r in (M - 1, base, base + 7, base + 8, 15, 16) + tuple(extra) if 0 <= r < M})
 
 
-def named_cols_gram(M, C, L, extra=()):
+def named_cols_gram(M, C, L, extra=(), chunk=GR_KC, bounds=None):
     """columns of the Gram sum's contracted dimension: the last column and the last aligned group's first, the first
     chunk edge, and both sides of (at most four, evenly spread) split boundaries.  At most 13 columns: every named
     column weighs four times the whole unnamed panel (col_scale), so each carries about 1/13 of an element's absolute
     sum, against a bound of at most 1/500 of it - with 510 named columns (both sides of 255 boundaries) none of them
-    would be visible"""
-    _, _, ns, bounds = gram_plan(M, C, L)
+    would be visible.  chunk, bounds: another Gram kernel's chunk width and split boundaries (in chunks)"""
+    if bounds is None:
+        bounds = gram_plan(M, C, L)[3]
     inner = bounds[1:-1]
     if len(inner) > 4:
         inner = [inner[i * (len(inner) - 1) // 3] for i in range(4)]
-    cols = {C - 1, C - 4, 0, GR_KC - 1, GR_KC} | set(extra)
+    cols = {C - 1, C - 4, 0, chunk - 1, chunk} | set(extra)
     for b in inner:
-        cols |= {b * GR_KC - 1, b * GR_KC}
+        cols |= {b * chunk - 1, b * chunk}
     return sorted(c for c in cols if 0 <= c < C)
 
 
@@ -323,20 +324,22 @@ def _base(M, C, L, seed):
     return al, Om, _randn(seed + 2, L, C), _randn(seed + 3, L, C), _randn(seed + 4, M, L)
 
 
-def make_inputs(M, C, L, family, out="rows", seed=0, gram_cols=None, outputs=None):
+def make_inputs(M, C, L, family, out="rows", seed=0, gram_cols=None, outputs=None, rows=None, col_floor=0.5):
     """dict of CPU fp64 tensors: al [M,C], Om [L,M,M] (symmetric), g, dm [L,C], dc [M,L].  family: "plain", "edge"
     (named rows of al and the matching rows and columns of Om scaled by row_scale; the columns ``gram_cols`` of g and dm
     by col_scale(C), with al's entries in those columns at least 0.5 / sqrt(M); the rows ``outputs`` of g by col_scale(L):
     a sum over hundreds of outputs hides one of them as a long Gram sum hides a column), "graded" (powers of two 2^U{-10..10} such that the output named by ``out`` scales with them and its
     bound likewise: "rows" - dalpha: Om -> D Om D, al -> D^-1 al, dc -> D dc; "gram" - dOmega, ddelta: al -> D al;
-    "cols" - v: al -> al D_c).  Every scaling is a power of two, so rounding to fp32 commutes with it."""
+    "cols" - v: al -> al D_c).  Every scaling is a power of two, so rounding to fp32 commutes with it.  rows: the edge
+    family's named rows where they are not named_rows(M); col_floor: al's entries in the named columns are at least
+    col_floor / sqrt(M)."""
     al, Om, g, dm, dc = [t.clone() for t in _base(M, C, L, 1000 * seed + 7 * M + C % 997 + 13 * L)]
     if family == "edge":
-        rows, s = named_rows(M), row_scale(M)
+        rows, s = (named_rows(M) if rows is None else list(rows)), row_scale(M)
         if gram_cols:
             _weigh(g, gram_cols, col_scale(C))
             _weigh(dm, gram_cols, col_scale(C))
-            _weigh(al, gram_cols, 1.0, floor=0.5 / M ** 0.5)
+            _weigh(al, gram_cols, 1.0, floor=col_floor / M ** 0.5)
         if outputs:
             _weigh(g, outputs, col_scale(L), dim=0)
         al[rows] *= s
@@ -429,11 +432,14 @@ def drop_row_mm(P, X, transP, r):
     return Pm[:, r][:, None] * X.double()[r][None, :]
 
 
-def ref_gram(al, g, stored32):
+def ref_gram(al, g, stored32, prod_bar=None):
+    """prod_bar(C, S): another contraction's bound of a C-term element (its partial sums' additions included)"""
     a, g = al.double(), g.double()
     C = a.shape[1]
     want = torch.stack([(a * g[l][None, :]) @ a.t() for l in range(g.shape[0])])
     ab = torch.stack([(a.abs() * g[l].abs()[None, :]) @ a.abs().t() for l in range(g.shape[0])])
+    if prod_bar is not None:
+        return want, prod_bar(C, ab) + (U32 * want.abs() if stored32 else 0.0)
     return want, bar(C + NSPLIT_MAX, ab, u=U32, want32=want if stored32 else None)
 
 
@@ -442,10 +448,11 @@ def drop_col_gram(al, g, c):
     return g.double()[:, c][:, None, None] * (a[:, None] * a[None, :])[None]
 
 
-def ref_ddelta(al, dm, dd0=None, dbeta=0.0):
+def ref_ddelta(al, dm, dd0=None, dbeta=0.0, prod_bar=None):
     a, d = al.double(), dm.double()
     want = a @ d.t()
-    bound = bar(a.shape[1] + NSPLIT_MAX, a.abs() @ d.abs().t(), u=U32)
+    S = a.abs() @ d.abs().t()
+    bound = bar(a.shape[1] + NSPLIT_MAX, S, u=U32) if prod_bar is None else prod_bar(a.shape[1], S)
     if dd0 is not None and dbeta != 0.0:
         want = want + dbeta * dd0.double()
         bound = bound + abs(dbeta) * U32 * dd0.double().abs()
@@ -522,24 +529,27 @@ def np_mm(P, X, transP, other=False):
     return Y, (Y * Y).sum(0, dtype=np.float32)
 
 
-def _chunks(C, other):
-    edges = list(range(0, C, GR_KC)) + [C]
+def _chunks(C, other, chunk=GR_KC):
+    edges = list(range(0, C, chunk)) + [C]
     pairs = list(zip(edges[:-1], edges[1:]))
     return pairs[::-1] if other else [(0, C)]
 
 
-def np_gram(al, g, other=False):
+def np_gram(al, g, other=False, chunk=GR_KC, matmul=None):
+    """matmul(A, B): the product of two fp32 arrays as another contraction forms it (default: NumPy's)"""
+    mm = matmul or (lambda A, B: A @ B)
     a, g = al.numpy(), g.numpy()
     out = np.zeros((g.shape[0], a.shape[0], a.shape[0]), np.float32)
-    for (c0, c1) in _chunks(a.shape[1], other):  # other: 64-column chunks, last first
+    for (c0, c1) in _chunks(a.shape[1], other, chunk):  # other: chunks, last first
         for l in range(g.shape[0]):
-            out[l] += (a[:, c0:c1] * g[l, c0:c1][None, :]) @ a[:, c0:c1].T
+            out[l] += mm(a[:, c0:c1] * g[l, c0:c1][None, :], a[:, c0:c1].T)
     return out
 
 
-def np_ddelta(al, dm, other=False):
+def np_ddelta(al, dm, other=False, chunk=GR_KC, matmul=None):
+    mm = matmul or (lambda A, B: A @ B)
     a, d = al.numpy(), dm.numpy()
     out = np.zeros((a.shape[0], d.shape[0]), np.float32)
-    for (c0, c1) in _chunks(a.shape[1], other):
-        out += a[:, c0:c1] @ d[:, c0:c1].T
+    for (c0, c1) in _chunks(a.shape[1], other, chunk):
+        out += mm(a[:, c0:c1], d[:, c0:c1].T)
     return out

@@ -184,9 +184,9 @@ def lmc_outputs(L, nb=False):
 
 
 # ---- named edge indices ----------------------------------------------------------------------------------------------------
-def elbo_named_rows(M):
+def elbo_named_rows(M, extra=()):
     base = 16 * (mb_for(M) - 1)
-    return sorted({r for r in (M - 1, base, base + 7, base + 8) if 0 <= r < M})
+    return sorted({r for r in (M - 1, base, base + 7, base + 8) + tuple(extra) if 0 <= r < M})
 
 
 def elbo_named_cols(C, N):
@@ -344,23 +344,25 @@ def _counts(g, eta):
 
 
 @functools.lru_cache(maxsize=2)
-def _elbo_base(M, C, L, family):
+def _elbo_base(M, C, L, family, rows=None):
     """alpha, Omega (both precisions) of contraction_util's family, and the fp64 pieces every closing of the shape shares:
     v = alpha^T Omega alpha and its absolute sum, from the fp32 Omega"""
-    inp = cu.make_inputs(M, C, L, family)
+    inp = cu.make_inputs(M, C, L, family, rows=rows)
     a, Om = inp["al"].double(), inp["Om32"].double()
     v = torch.stack([((Om[l] @ a) * a).sum(0) for l in range(L)])
     return inp["al"], inp["Om32"], inp["Om64"], v
 
 
-def elbo_inputs(M, C, L, lik, family, delta=False, offs=True, miss=None, seed=0):
+def elbo_inputs(M, C, L, lik, family, delta=False, offs=True, miss=None, seed=0, rows=None):
     """dict of CPU tensors as stored (fp32; q fp64) and the scalars S, N.  family "plain" / "edge": contraction_util's
     alpha and Omega (edge: the named rows of alpha, rows and columns of Omega scaled by row_scale), delta's named rows
     likewise; eps is drawn N(0, 1) / max(1, sd) so that the draw's random part stays of order one whatever the variance (a
     log rate must stay below ETA_MAX) and doubled at the named columns (edge).  q is chosen so that exp(var_u) - q lies in
-    [0.3, 0.5]: Omega is positive semi-definite, so the variance is at least 0.3.  miss: None, or a fraction of Y set NaN"""
+    [0.3, 0.5]: Omega is positive semi-definite, so the variance is at least 0.3.  miss: None, or a fraction of Y set NaN.
+    rows: the edge family's named rows (of alpha, Omega and delta) where another kernel names its own (default:
+    contraction_util's for alpha and Omega, elbo_named_rows for delta)"""
     S, N = sample_split(C)
-    al, Om32, Om64, v = _elbo_base(M, C, L, family)
+    al, Om32, Om64, v = _elbo_base(M, C, L, family, None if rows is None else tuple(rows))
     g = _gen(1009 * seed + 31 * M + C + 7 * L + LIKS.index(lik) + 5 * int(delta))
     var_u = torch.tensor([math.log(0.8)], dtype=f32)
     var0 = math.exp(float(var_u))
@@ -376,7 +378,7 @@ def elbo_inputs(M, C, L, lik, family, delta=False, offs=True, miss=None, seed=0)
     if delta:
         d = 0.25 * _randn(g, M, L) / M ** 0.5
         if family == "edge":
-            d[elbo_named_rows(M)] *= cu.row_scale(M)
+            d[elbo_named_rows(M) if rows is None else list(rows)] *= cu.row_scale(M)
         out["delta"] = d.float()
         mean = out["delta"].double().t() @ al.double()
     else:
@@ -401,15 +403,16 @@ def elbo_inputs(M, C, L, lik, family, delta=False, offs=True, miss=None, seed=0)
 
 
 # ---- fused ELBO: reference, stage by stage ----------------------------------------------------------------------------------
-def elbo_reference(inp, M, C, L, lik, om="Om32", delta=False, skip=False):
+def elbo_reference(inp, M, C, L, lik, om="Om32", delta=False, skip=False, prod_bar=None):
     """stage 1 from the inputs alone: dict F, E_F, sd, E_sd, var (all [L, C] fp64), W, absW ([L, M, C]: Omega_l alpha and its
-    absolute counterpart) and the per-(l, c) views of Y, the offsets and the observed mask"""
+    absolute counterpart) and the per-(l, c) views of Y, the offsets and the observed mask.  prod_bar(K, S): the bound of
+    one element of Omega_l alpha where the contraction is not the fp32 one (the closing's M-term dot product stays fp32)"""
     a, Om = inp["al"].double(), inp[om].double()
     N, cm = inp["N"], col_maps(C, inp["N"])
     W = torch.stack([Om[l] @ a for l in range(L)])
     absW = torch.stack([Om[l].abs() @ a.abs() for l in range(L)])
     v, absv = (W * a[None]).sum(1), (absW * a.abs()[None]).sum(1)
-    E_v = bar(2 * M, absv, u=U)
+    E_v = bar(2 * M, absv, u=U) if prod_bar is None else prod_bar(M, absv) + bar(M, absv + prod_bar(M, absv), u=U)
     resid = (math.exp(float(inp["var_u"])) - inp["q"]).float().double()[None, :]  # formed in fp64, rounded once
     t1 = resid + v
     var = t1 + float(np.float32(2e-5))
@@ -422,7 +425,7 @@ def elbo_reference(inp, M, C, L, lik, om="Om32", delta=False, skip=False):
     e = inp["eps"].double().t()
     if delta:
         dl = inp["delta"].double()
-        mean, E_mean = dl.t() @ a, bar(M, dl.abs().t() @ a.abs(), u=U)
+        mean, E_mean = dl.t() @ a, (prod_bar or (lambda K, S: bar(K, S, u=U)))(M, dl.abs().t() @ a.abs())
     else:
         mean, E_mean = inp["meanT"].double(), torch.zeros_like(var)
     se = sd * e
@@ -444,10 +447,19 @@ def elbo_closing(inp, ref, lik, F):
     return close(lik, F, ref["y"], ref["obs"], inp["S"], noise_u=inp.get("noise_u"), off=ref["off"], rho=ref["rho"])
 
 
-def elbo_stage_ratios(inp, ref, M, C, L, lik, got):
-    """error / bound of every stage against the one before it.  got: FT, dm, g, abar, part [, u, usum] on the CPU."""
+def abar_bound(M, L, abs_ab, want_ab=None, prod_bar=None):
+    """section 2e's ACCUM bound; prod_bar: M terms of another contraction per product, then the fp32 chain over the L
+    outputs and at most L slab addends (2 L roundings, which bar(L, .) covers with its factor 2)"""
+    if prod_bar is None:
+        return bar(L * (M + 2), abs_ab, u=U, want32=want_ab)
+    return prod_bar(M, abs_ab) + bar(L, abs_ab, u=U, want32=want_ab)
+
+
+def elbo_stage_ratios(inp, ref, M, C, L, lik, got, prod_bar=None, nct=None):
+    """error / bound of every stage against the one before it.  got: FT, dm, g, abar, part [, u, usum] on the CPU.
+    prod_bar, nct: another contraction's element bound (elbo_reference) and column tiles per wave"""
     FT, dm, g = got["FT"].double(), got["dm"].double(), got["g"].double()
-    NCT = ELBO_NCT[mb_for(M)]
+    NCT = ELBO_NCT[mb_for(M)] if nct is None else nct
     out = {"FT": ratio(FT, ref["F"], ref["E_F"])}
     cl = elbo_closing(inp, ref, lik, FT)
     if cl["eta"] is not None:
@@ -457,7 +469,7 @@ def elbo_stage_ratios(inp, ref, M, C, L, lik, got):
     out["g"] = ratio(g, want_g, want_g.abs() * (ref["E_sd"] / ref["sd"] + 4 * U))
     want_ab = 2 * (g[:, None, :] * ref["W"]).sum(0)
     abs_ab = 2 * (g.abs()[:, None, :] * ref["absW"]).sum(0)
-    out["abar"] = ratio(got["abar"].double(), want_ab, bar(L * (M + 2), abs_ab, u=U, want32=want_ab))
+    out["abar"] = ratio(got["abar"].double(), want_ab, abar_bound(M, L, abs_ab, want_ab, prod_bar))
     tsum, tabs = float(cl["t"].sum()), float(cl["t"].abs().sum())
     b_part = float(cl["E_t"].sum()) + NCT * U * tabs + C * L * U64 * tabs
     err = abs(float(got["part"].double().sum()) - tsum)
@@ -469,19 +481,21 @@ def elbo_stage_ratios(inp, ref, M, C, L, lik, got):
     return out, cl
 
 
-def elbo_np(inp, M, C, L, lik, om="Om32", delta=False, skip=False, other=False):
+def elbo_np(inp, M, C, L, lik, om="Om32", delta=False, skip=False, other=False, matmul=None):
     """the whole pass in plain fp32 NumPy (other: rows visited backwards, outputs backwards, the other closing formulation)
-    -> FT, dm, g, abar, part (fp64 sum of the fp32 terms), u"""
+    -> FT, dm, g, abar, part (fp64 sum of the fp32 terms), u.  matmul(A, B): the contraction Omega_l alpha (and delta^T
+    alpha) as another kernel forms it (default: NumPy's fp32 product)"""
     f = np.float32
+    mm = matmul or (lambda A, B: A @ B)
     al, Om = inp["al"].numpy(), inp[om].float().numpy()
     order = list(range(M))[::-1] if other else list(range(M))
     a_o, Om_o = al[order], Om[:, order][:, :, order]
-    W = np.stack([Om_o[l] @ a_o for l in range(L)])  # rows in ``order``
+    W = np.stack([mm(Om_o[l], a_o) for l in range(L)])  # rows in ``order``
     v = (W * a_o[None]).sum(1, dtype=f)
     resid = (math.exp(float(inp["var_u"])) - inp["q"].numpy()).astype(f)[None, :]
     sd = np.sqrt(resid + v + f(2e-5))
     e = inp["eps"].numpy().T
-    mean = (inp["delta"].numpy()[order].T @ a_o) if delta else inp["meanT"].numpy()
+    mean = mm(np.ascontiguousarray(inp["delta"].numpy()[order].T), a_o) if delta else inp["meanT"].numpy()
     F = mean + sd * e
     cm = col_maps(C, inp["N"]).numpy()
     y = inp["Y"].numpy().T[:, cm]
@@ -632,18 +646,18 @@ def sentinel_frame(src, dev, fill=SENTINEL):
 
 
 # ---- the visibility condition of the edge-weighted family, from the reference alone -----------------------------------------
-def elbo_visibility(inp, ref, cl, got, M, C, L, lik, om):
+def elbo_visibility(inp, ref, cl, got, M, C, L, lik, om, prod_bar=None, nct=None, rows=None):
     """a lost named row moves half of the draws and half of its abar entries, a lost named column the sum of the terms, by
     more than 4 x their bound.  got: the g that abar is held to (the device's, or the fp32 NumPy one)"""
     g = got["g"].double()
     abs_ab = 2 * (g.abs()[:, None, :] * ref["absW"]).sum(0)
-    b_ab = bar(L * (M + 2), abs_ab, u=U)
-    for r in elbo_named_rows(M):
+    b_ab = abar_bound(M, L, abs_ab, None, prod_bar)
+    for r in (elbo_named_rows(M) if rows is None else rows):
         if M > 1:
             assert visible(drop_row_FT(inp, ref, om, r), ref["E_F"]), ("FT", M, r)
         assert visible(cu.drop_row_dalpha(inp["al"], inp[om], g, r), b_ab), ("abar", M, r)
     tabs = float(cl["t"].abs().sum())
-    b_part = float(cl["E_t"].sum()) + ELBO_NCT[mb_for(M)] * U * tabs
+    b_part = float(cl["E_t"].sum()) + (ELBO_NCT[mb_for(M)] if nct is None else nct) * U * tabs
     lost = cl["t"][:, inp["named_cols"]].sum(0).abs()
     assert float((lost > 4 * b_part).double().mean()) >= 0.5, ("part", M, C)
 
