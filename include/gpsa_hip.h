@@ -1408,6 +1408,32 @@ int gpsa_autocorr_perm_f64(const double* Z, long long n, long long P, const long
                            const double* w, long long nnz, const int* perms, long long R, int mode, double* num,
                            long long* n_bad, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- rigid pre-registration (csrc/register.hip): the score of K candidate transforms of slice B against slice A ---------
+ * gpsa_rigid_scores_f64, D = 2: XA [m, 2] fp64 and YA [m, P] fp32 (slice A), XB [n, 2] fp64 and YB [n, P] fp32 (slice B),
+ *   T [K, 6] fp64 (per candidate R row-major, then t), all row-major.  For candidate k and row i of B
+ *     q_d = fma(R_d0, x0, fma(R_d1, x1, t_d)),   d2(j) = fma(u1, u1, fma(u0, u0, 0)) with u = q - XA[j] (gpsa_knn_f64's
+ *   accumulation), a NaN d2 counted as +inf, and nn[k, i] = the row j of A with the smallest key (d2, j): ties in d2 to
+ *   the lower index, a total order (a row of B with a NaN coordinate gets nn = 0, d2 = +inf).  Row i is MATCHED iff
+ *   d2[k, i] <= max_d2, and
+ *     sse[k] = sum_{i matched} sum_p (double(YB[i, p]) - double(YA[nn[k, i], p]))^2     fp64 [K]
+ *     d2_sum[k] = sum_{i matched} d2[k, i]                                             fp64 [K]
+ *     n_matched[k]                                                                     int64 [K]
+ *   nn [K, n] int32 and d2 [K, n] fp64 are optional outputs (both or neither NULL; without them the tables live in the
+ *   workspace).  One thread scans 8 candidates for one row of B per pass over A (A through LDS in tiles of 1024 rows,
+ *   read as a broadcast); parts: slices of the A axis scanned by separate workgroups and merged by the same key, 0 = auto.
+ *   The sums are fp64 in a fixed order: a workgroup per (candidate, row group), the row groups - ceil(n / max(32,
+ *   ceil(n / 32))) of them, a function of n alone - added in ascending order.  No atomics, one writer per output element:
+ *   candidate k's outputs depend on T[k] and (n, P) alone - the same bits whatever K, `parts`, the other rows of T or
+ *   the call's repeat.  workspace >= gpsa_rigid_scores_workspace(n, m, K, P, parts, tables) bytes, tables != 0 when the
+ *   caller passes nn / d2: 24 K G for the partials, 12 K n for the tables otherwise, 12 parts K n with parts > 1.
+ *   GPSA_EINVAL: a NULL pointer (nn / d2 together excepted), n, m, K, P < 1, parts < 0, max_d2 negative, NaN or infinite;
+ *   GPSA_EUNSUPPORTED: n or m >= 2^31, K > 65535, K n > 2^38;  GPSA_EWORKSPACE.  Every check runs before the first launch. */
+long long gpsa_rigid_scores_workspace(long long n, long long m, long long K, int P, int parts, int tables);
+int gpsa_rigid_scores_f64(const double* XA, const float* YA, long long m, const double* XB, const float* YB,
+                          long long n, int P, const double* T, long long K, double max_d2, int parts, double* sse,
+                          long long* n_matched, double* d2_sum, int* nn, double* d2, void* workspace,
+                          long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ from .neighbors import alignment_score, knn, knn_regress, kth_neighbor_distance,
 from .ot import OTAlignment, ot_align, paste_baseline, stack_slices
 from .parallel import fit
 from .predict import predict
+from .register import RigidRegistration, prealign_slices, rigid_register, rigid_scores
 from .util import (
     ConvergenceChecker,
     LossNotDecreasingChecker,
@@ -89,5 +90,9 @@ __all__ = [
     "ImagePixels",
     "histology_modality",
     "warp_image",
+    "rigid_scores",
+    "rigid_register",
+    "RigidRegistration",
+    "prealign_slices",
 ]
 __version__ = "0.1.0"

@@ -288,6 +288,10 @@ SIGNATURES.update({
     "gpsa_graph_sums_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _ll, _vp, _vp, _ll, _vp]),
     "gpsa_autocorr_perm_workspace": (_ll, [_ll, _ll, _ll]),
     "gpsa_autocorr_perm_f64": (_i, [_vp, _ll, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _i, _vp, _vp, _vp, _ll, _vp]),
+    # rigid pre-registration: the score of K candidate transforms of one slice against another (csrc/register.hip)
+    "gpsa_rigid_scores_workspace": (_ll, [_ll, _ll, _ll, _i, _i, _i]),
+    "gpsa_rigid_scores_f64": (_i, [_vp, _vp, _ll, _vp, _vp, _ll, _i, _vp, _ll, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ll,
+                                   _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

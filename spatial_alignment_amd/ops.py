@@ -677,6 +677,49 @@ class HipOps:
         _lib.check(rc, name)
         return out
 
+    # ------------------------------------------------------------------ rigid pre-registration (csrc/register.hip)
+    def rigid_scores(self, XA, YA, XB, YB, T, max_d2, parts=0, return_nn=False):
+        """gpsa_rigid_scores_f64: for every candidate k of T [K, 6] (R row-major, then t) the rows of XB [n, 2] are taken
+        to q = R x + t, matched to their nearest row of XA [m, 2] by the key (fp64 squared distance, index) where that
+        distance is <= max_d2, and scored on the expression YA [m, P] / YB [n, P] (fp32) -> (sse [K] fp64,
+        n_matched [K] int64, d2_sum [K] fp64, nn [K, n] int32 or None, d2 [K, n] fp64 or None).  ``parts``: slices of
+        the A axis, 0 = auto - the result is the same bits for every value, every K and every repeat."""
+        XA, XB, T = self._f64(XA), self._f64(XB), self._f64(T)
+        YA, YB = self._f32(YA), self._f32(YB)
+        if XA.dim() != 2 or XB.dim() != 2 or XA.shape[0] < 1 or XB.shape[0] < 1:
+            raise ValueError(f"rigid_scores: XA {tuple(XA.shape)} and XB {tuple(XB.shape)} must be [m >= 1, 2] and "
+                             "[n >= 1, 2]")
+        if XA.shape[1] != 2 or XB.shape[1] != 2:
+            raise ValueError(f"rigid_scores: D = {int(XA.shape[1])} and {int(XB.shape[1])}; the candidates are transforms "
+                             "of the plane, D = 2 is needed")
+        m, n = int(XA.shape[0]), int(XB.shape[0])
+        if YA.dim() != 2 or YB.dim() != 2 or YA.shape[0] != m or YB.shape[0] != n or YA.shape[1] < 1 \
+                or YA.shape[1] != YB.shape[1]:
+            raise ValueError(f"rigid_scores: YA {tuple(YA.shape)} and YB {tuple(YB.shape)} must be [{m}, P] and [{n}, P] "
+                             "with one P >= 1")
+        P = int(YA.shape[1])
+        if T.dim() != 2 or T.shape[0] < 1 or T.shape[1] != 6:
+            raise ValueError(f"rigid_scores: T has shape {tuple(T.shape)}; [K >= 1, 6] (R row-major, then t) is needed")
+        K, parts, max_d2 = int(T.shape[0]), int(parts), float(max_d2)
+        if K > 65535 or K * n > 2**38:
+            raise ValueError(f"rigid_scores: K = {K} candidates of {n} rows; at most 65535 candidates and 2^38 (candidate, "
+                             "row) pairs per call are supported - pass the table in chunks")
+        if not (0.0 <= max_d2 < float("inf")):
+            raise ValueError(f"rigid_scores: max_d2 must be finite and >= 0, not {max_d2}")
+        if parts < 0:
+            raise ValueError(f"rigid_scores: parts must be >= 0, not {parts}")
+        dev, i64, f64 = XB.device, torch.int64, torch.float64
+        sse, d2_sum = torch.empty(K, dtype=f64, device=dev), torch.empty(K, dtype=f64, device=dev)
+        n_matched = torch.empty(K, dtype=i64, device=dev)
+        nn = torch.empty(K, n, dtype=torch.int32, device=dev) if return_nn else None
+        d2 = torch.empty(K, n, dtype=f64, device=dev) if return_nn else None
+        nbytes = self._wsq("gpsa_rigid_scores_workspace", n, m, K, P, parts, 1 if return_nn else 0)
+        ws = self._ws(nbytes, XB)
+        rc = self.lib.gpsa_rigid_scores_f64(_p(XA), _p(YA), m, _p(XB), _p(YB), n, P, _p(T), K, max_d2, parts, _p(sse),
+                                            _p(n_matched), _p(d2_sum), _p(nn), _p(d2), _p(ws), nbytes, self._stream(XB))
+        _lib.check(rc, "gpsa_rigid_scores_f64")
+        return sse, n_matched, d2_sum, nn, d2
+
     # ------------------------------------------------------------------ exact GP regression (csrc/gpr.hip)
     def _gpr_args(self, what, kind, theta, *coords):
         """-> (kind code, theta, D) after the checks the three gpr entries share: the kernel's name, theta = three fp64

@@ -22,6 +22,7 @@ each with
        neighbour statistics                 gpsa::knn, gpsa::knn_average               (neighbors.py; csrc/neighbors.hip)
        spatial autocorrelation              gpsa::graph_merge, gpsa::graph_check,      (autocorr.py; csrc/autocorr.hip)
                                             gpsa::graph_sums, gpsa::autocorr_perm
+       rigid pre-registration               gpsa::rigid_scores                         (register.py; csrc/register.hip)
        count preprocessing                  gpsa::count_margins, gpsa::count_deviance, (counts.py; csrc/counts.hip)
                                             gpsa::count_transform, gpsa::standardize_views
        ... from a CSR matrix                gpsa::csr_check, gpsa::count_margins_csr,  (counts.py; csrc/counts_sparse.hip)
@@ -400,6 +401,29 @@ def autocorr_perm(Z: torch.Tensor, crow: torch.Tensor, col: torch.Tensor, w: tor
 @autocorr_perm.register_fake
 def _(Z, crow, col, w, perms, mode="moran"):
     return Z.new_empty(perms.shape[0], Z.shape[1], dtype=torch.float64), Z.new_empty(1, dtype=torch.int64)
+
+
+# ... rigid pre-registration: K candidate transforms of one slice scored against another (register.py; csrc/register.hip)
+@torch.library.custom_op("gpsa::rigid_scores", mutates_args=(), device_types="cuda")
+def rigid_scores(XA: torch.Tensor, YA: torch.Tensor, XB: torch.Tensor, YB: torch.Tensor, T: torch.Tensor, max_d2: float,
+                 parts: int = 0, return_nn: bool = False
+                 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """per row of T [K, 6]: B's rows at R x + t matched to their nearest row of A within max_d2 -> (sse [K] fp64,
+    n_matched [K] int64, d2_sum [K] fp64, nn [K, n] int32, d2 [K, n] fp64; the last two empty without ``return_nn``);
+    the same bits for every ``parts``, K and repeat"""
+    sse, n_matched, d2_sum, nn, d2 = _o().rigid_scores(XA, YA, XB, YB, T, max_d2, parts, return_nn)
+    if not return_nn:
+        nn, d2 = XB.new_empty(0, dtype=torch.int32), XB.new_empty(0, dtype=torch.float64)
+    return sse, n_matched, d2_sum, nn, d2
+
+
+@rigid_scores.register_fake
+def _(XA, YA, XB, YB, T, max_d2, parts=0, return_nn=False):
+    K, n = T.shape[0], XB.shape[0]
+    f64 = torch.float64
+    return (XB.new_empty(K, dtype=f64), XB.new_empty(K, dtype=torch.int64), XB.new_empty(K, dtype=f64),
+            XB.new_empty((K, n) if return_nn else (0,), dtype=torch.int32),
+            XB.new_empty((K, n) if return_nn else (0,), dtype=f64))
 
 
 # ---------------------------------------------------------------------------------------------------------
