@@ -1434,6 +1434,40 @@ int gpsa_rigid_scores_f64(const double* XA, const float* YA, long long m, const 
                           long long* n_matched, double* d2_sum, int* nn, double* d2, void* workspace,
                           long long workspace_bytes, void* stream);
 
+/* ---- expression PCA (csrc/pca.hip): the covariance's Gram and the projection on the components ------------------------
+ * What scanpy's sc.tl.pca / sklearn's PCA compute on the host before an alignment on a few components (the reference's
+ * ST scripts select n_top_genes = 3000 and standardise per slice, experiments/expression/st/st_prediction.py); the
+ * solver on top is built from gpsa_gemm and gpsa_chol_inv_f64 (pca.py).  Y [N, P] fp32 row-major; mean [V, P] and
+ * inv_scale [V, P] fp64 on the device (inv_scale NULL: no scaling); view_off [V + 1] is a HOST array, 0 = view_off[0] <
+ * ... < view_off[V] = N, as gpsa_column_moments_f32 takes it.  Both entries form
+ *   z_ia = (double(y_ia) - mean[v(i), a]) * inv_scale[v(i), a]
+ * in fp64 from the stored fp32 value as the operand is staged: no centred and no fp64 copy of Y exists.  The views are
+ * walked one after the other (a launch per view), so no K chunk and no row block mixes two views' means.  fp64 sums in
+ * a fixed order, no atomics, one writer per output element per launch, the same bits on a repeated call.
+ * gpsa_pca_gram_f32: G [P, P] fp64 = sum_i z_ia z_ib on v_mfma_f64_16x16x4_f64, tiles of 64 x 64 columns, rows in chunks
+ *   of 32.  Only tile pairs with column tile >= row tile are computed and every element (a <= b) is written to both
+ *   places: G is symmetric to the bit.  A view's rows are cut into at most Gr = gpsa_pca_gram_groups(N, P) groups of
+ *   ceil(ceil(n / Gr) / 32) * 32 rows whose partials are added in ascending order (views inside a group in view order);
+ *   Gr = 1 once the ceil(P / 64) (ceil(P / 64) + 1) / 2 tile pairs are 256 or more, else min(32, ceil(256 / pairs),
+ *   ceil(N / 32)): a function of (N, P) alone, not of the device.  workspace >= gpsa_pca_gram_workspace(N, P, V) bytes, a
+ *   pure host query (0 for N, P or V < 1): 8 Gr P^2 for Gr > 1, and 0 for Gr = 1 (the partial is G itself; workspace may
+ *   be NULL then).
+ * gpsa_pca_project_f32: scores [N, k] = sum_a z_ia comp[j, a] with comp [k, P] fp64, k <= 128; fp64 accumulation on the
+ *   MFMA pipe (the vector pipe forms z), Y read once; stored as fp32 rounded once (out_f64 = 0) or as fp64 (1).  A
+ *   row's sum runs over the columns in one fixed order: the same bits whatever rows are passed together.
+ * Refusals, all before the first launch and with nothing written: GPSA_EINVAL for a NULL pointer (inv_scale, and the
+ * workspace when the query is 0, excepted), N < 2 (Gram) or N < 1 (projection), P < 1, P >= 2^21 (Gram) or 2^31, k outside
+ * 1..128, out_f64 outside {0, 1}, V < 1, offsets that do not partition [0, N) or an empty view; GPSA_EWORKSPACE for a NULL
+ * or short workspace when the query is not 0. */
+int gpsa_pca_gram_groups(long long N, long long P);
+long long gpsa_pca_gram_workspace(long long N, long long P, int V);
+int gpsa_pca_gram_f32(const float* Y, long long N, long long P, const double* mean, const double* inv_scale,
+                      const long long* view_off, int V, double* G, void* workspace, long long workspace_bytes,
+                      void* stream);
+int gpsa_pca_project_f32(const float* Y, long long N, long long P, const double* mean, const double* inv_scale,
+                         const long long* view_off, int V, const double* comp, int k, void* scores, int out_f64,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

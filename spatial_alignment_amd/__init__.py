@@ -26,6 +26,7 @@ from .models import GPSA, VariationalGPSA
 from .neighbors import alignment_score, knn, knn_regress, kth_neighbor_distance, moran_i, spatial_r2
 from .ot import OTAlignment, ot_align, paste_baseline, stack_slices
 from .parallel import fit
+from .pca import ExpressionPCA, expression_pca, init_lmc_from_pca
 from .predict import predict
 from .register import RigidRegistration, prealign_slices, rigid_register, rigid_scores
 from .util import (
@@ -94,5 +95,8 @@ __all__ = [
     "rigid_register",
     "RigidRegistration",
     "prealign_slices",
+    "expression_pca",
+    "ExpressionPCA",
+    "init_lmc_from_pca",
 ]
 __version__ = "0.1.0"

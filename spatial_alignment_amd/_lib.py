@@ -292,6 +292,11 @@ SIGNATURES.update({
     "gpsa_rigid_scores_workspace": (_ll, [_ll, _ll, _ll, _i, _i, _i]),
     "gpsa_rigid_scores_f64": (_i, [_vp, _vp, _ll, _vp, _vp, _ll, _i, _vp, _ll, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ll,
                                    _vp]),
+    # expression PCA: the covariance's Gram and the projection on the components (csrc/pca.hip); view_off is a HOST array
+    "gpsa_pca_gram_groups": (_i, [_ll, _ll]),
+    "gpsa_pca_gram_workspace": (_ll, [_ll, _ll, _i]),
+    "gpsa_pca_gram_f32": (_i, [_vp, _ll, _ll, _vp, _vp, C.POINTER(_ll), _i, _vp, _vp, _ll, _vp]),
+    "gpsa_pca_project_f32": (_i, [_vp, _ll, _ll, _vp, _vp, C.POINTER(_ll), _i, _vp, _i, _vp, _i, _vp]),
     # count outputs (model.likelihood): the Poisson term
     "gpsa_lgamma_sum_workspace": (_ll, []),
     "gpsa_lgamma_sum": (_i, [_i, _pp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _pp, _i, _pp, _vp, _ll, _vp]),

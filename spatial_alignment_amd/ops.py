@@ -1302,15 +1302,16 @@ class HipOps:
         s1, s2, ab = (torch.empty(V, P, dtype=torch.float64, device=dev) for _ in range(3))
         return s1, s2, ab, torch.empty(1, dtype=torch.int64, device=dev)
 
-    def column_moments(self, Y, mode, view_off, scale=None):
+    def column_moments(self, Y, mode, view_off, scale=None, own_workspace=False):
         """gpsa_column_moments_f32: Y [N, P] fp32, ``mode`` "identity" | "expm1" | "normalize" (t = y, expm1(y), y scale_i),
         view_off a list of V + 1 ints 0 ... N -> (s1, s2, abs1 [V, P] fp64: the sums of t, t^2, |t| per (view, column),
-        n_nonfinite [1] int64 on the device)"""
+        n_nonfinite [1] int64 on the device).  ``own_workspace``: the planes live in a buffer of this call, freed with it,
+        not in the stream's shared scratch (which keeps its largest size)."""
         N, P = self._count_matrix(Y, "column_moments")
         m, off, V, scale = self._moment_args("column_moments", mode, N, view_off, scale)
         s1, s2, ab, bad = self._moment_outputs(V, P, Y.device)
         nbytes = self._wsq("gpsa_column_moments_workspace", N, P, V)
-        ws = self._ws(nbytes, Y)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=Y.device) if own_workspace else self._ws(nbytes, Y)
         rc = self.lib.gpsa_column_moments_f32(m, _p(Y), N, P, _p(scale), (C.c_longlong * (V + 1))(*off), V, _p(s1), _p(s2),
                                               _p(ab), _p(bad), _p(ws), nbytes, self._stream(Y))
         _lib.check(rc, "gpsa_column_moments_f32")
@@ -1331,6 +1332,68 @@ class HipOps:
                                                   _p(ws), nbytes, self._stream(crow))
         _lib.check(rc, "gpsa_column_moments_csr_f32")
         return s1, s2, ab, bad
+
+    # ------------------------------------------------------------------ expression PCA (csrc/pca.hip)
+    # the Gram kernel's tile edge, the rows of its chunk, the cap on its row groups, the tile pairs from which the row
+    # split is off; the projection's cap on the components
+    PCA_TILE, PCA_ROW_CHUNK, PCA_MAX_GROUPS, PCA_FILL, PCA_MAX_K = 64, 32, 32, 256, 128
+
+    def _pca_args(self, what, Y, mean, inv_scale, view_off):
+        """-> (N, P, offsets, V, mean, inv_scale): mean / inv_scale contiguous fp64 [V, P] on Y's device"""
+        N, P = self._count_matrix(Y, what)
+        off, V = self._view_offsets(what, view_off, N)
+        for t, name in ((mean, "mean"), (inv_scale, "inv_scale")):
+            if t is None and name == "inv_scale":
+                continue
+            if not torch.is_tensor(t) or tuple(t.shape) != (V, P) or t.dtype != torch.float64 or not t.is_contiguous() \
+                    or t.device != Y.device:
+                got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"{what}: {name} must be a contiguous fp64 [{V}, {P}] on {Y.device}, not {got}")
+        return N, P, off, V, mean, inv_scale
+
+    def pca_gram_groups(self, N, P):
+        """the row groups gpsa_pca_gram_f32 cuts a view into, at most: a function of (N, P) alone"""
+        return self._wsq("gpsa_pca_gram_groups", int(N), int(P))
+
+    def pca_gram_workspace(self, N, P, V=1):
+        return self._wsq("gpsa_pca_gram_workspace", int(N), int(P), int(V))
+
+    def pca_gram(self, Y, mean, view_off, inv_scale=None, out=None):
+        """gpsa_pca_gram_f32: G [P, P] fp64 = sum_i z_ia z_ib with z = (y - mean[v]) * inv_scale[v] formed in fp64 from
+        Y [N, P] fp32; mean / inv_scale [V, P] fp64, view_off a list of V + 1 ints 0 ... N.  Symmetric to the bit, the
+        same bits on a repeated call.  The workspace is this call's own and is freed with it."""
+        N, P, off, V, mean, inv_scale = self._pca_args("pca_gram", Y, mean, inv_scale, view_off)
+        if N < 2:
+            raise ValueError(f"pca_gram: Y has {N} row; at least 2 are needed")
+        if out is None:
+            out = torch.empty(P, P, dtype=torch.float64, device=Y.device)
+        assert tuple(out.shape) == (P, P) and out.dtype == torch.float64 and out.is_contiguous(), (P, P)
+        nbytes = self.pca_gram_workspace(N, P, V)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=Y.device) if nbytes else None
+        rc = self.lib.gpsa_pca_gram_f32(_p(Y), N, P, _p(mean), _p(inv_scale), (C.c_longlong * (V + 1))(*off), V, _p(out),
+                                        _p(ws), nbytes, self._stream(Y))
+        _lib.check(rc, "gpsa_pca_gram_f32")
+        return out
+
+    def pca_project(self, Y, mean, view_off, comp, inv_scale=None, out_dtype=torch.float32, out=None):
+        """gpsa_pca_project_f32: scores [N, k] = z comp^T with z as in ``pca_gram`` and comp [k <= 128, P] fp64; fp64
+        accumulation, stored as fp32 (rounded once) or fp64.  A row's result does not depend on the other rows."""
+        N, P, off, V, mean, inv_scale = self._pca_args("pca_project", Y, mean, inv_scale, view_off)
+        if not torch.is_tensor(comp) or comp.dim() != 2 or comp.shape[1] != P or not 1 <= comp.shape[0] <= self.PCA_MAX_K \
+                or comp.dtype != torch.float64 or not comp.is_contiguous() or comp.device != Y.device:
+            got = f"{comp.dtype} {tuple(comp.shape)}" if torch.is_tensor(comp) else type(comp).__name__
+            raise ValueError(f"pca_project: comp must be a contiguous fp64 [1 <= k <= {self.PCA_MAX_K}, {P}] on "
+                             f"{Y.device}, not {got}")
+        if out_dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"pca_project: out_dtype must be torch.float32 or torch.float64, not {out_dtype}")
+        k = int(comp.shape[0])
+        if out is None:
+            out = torch.empty(N, k, dtype=out_dtype, device=Y.device)
+        assert tuple(out.shape) == (N, k) and out.dtype == out_dtype and out.is_contiguous(), (N, k)
+        rc = self.lib.gpsa_pca_project_f32(_p(Y), N, P, _p(mean), _p(inv_scale), (C.c_longlong * (V + 1))(*off), V,
+                                           _p(comp), k, _p(out), int(out_dtype == torch.float64), self._stream(Y))
+        _lib.check(rc, "gpsa_pca_project_f32")
+        return out
 
     def warp_sample_fwd(self, meanT, v, q, var_u, X, slopes, intercept, eps):
         """-> Gmean [n,D], Gs [S,n,D] (fp32), bad [blocks] (int32 flags), Gs64 [S,n,D] (the draws unrounded)"""

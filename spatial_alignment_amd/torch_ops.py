@@ -560,6 +560,32 @@ def _(crow, col, val, N, P, mode, view_off, scale=None, keep=None):
     return tuple(val.new_empty(V, P, dtype=torch.float64) for _ in range(3)) + (val.new_empty(1, dtype=torch.int64),)
 
 
+# ... and expression PCA's two passes over the data (csrc/pca.hip)
+@torch.library.custom_op("gpsa::pca_gram", mutates_args=(), device_types="cuda")
+def pca_gram(Y: torch.Tensor, mean: torch.Tensor, view_off: list[int], inv_scale: Optional[torch.Tensor] = None
+             ) -> torch.Tensor:
+    """G [P, P] fp64 = sum_i z_ia z_ib, z = (y - mean[v]) * inv_scale[v] in fp64 from Y [N, P] fp32; mean / inv_scale
+    [V, P] fp64, view_off [V + 1]; symmetric to the bit"""
+    return _o().pca_gram(Y, mean, view_off, inv_scale)
+
+
+@pca_gram.register_fake
+def _(Y, mean, view_off, inv_scale=None):
+    return Y.new_empty(Y.shape[1], Y.shape[1], dtype=torch.float64)
+
+
+@torch.library.custom_op("gpsa::pca_project", mutates_args=(), device_types="cuda")
+def pca_project(Y: torch.Tensor, mean: torch.Tensor, view_off: list[int], comp: torch.Tensor,
+                inv_scale: Optional[torch.Tensor] = None, out_f64: bool = False) -> torch.Tensor:
+    """scores [N, k] = z comp^T with z as in gpsa::pca_gram and comp [k <= 128, P] fp64; fp32 (rounded once) or fp64"""
+    return _o().pca_project(Y, mean, view_off, comp, inv_scale, torch.float64 if out_f64 else torch.float32)
+
+
+@pca_project.register_fake
+def _(Y, mean, view_off, comp, inv_scale=None, out_f64=False):
+    return Y.new_empty(Y.shape[0], comp.shape[0], dtype=torch.float64 if out_f64 else torch.float32)
+
+
 # ---------------------------------------------------------------------------------------------------------
 # (4g) exact GP regression: covariance assembly, the LML gradient's reduction, the predictive mean (gpr.py)
 # ---------------------------------------------------------------------------------------------------------
