@@ -22,6 +22,7 @@ import math
 import torch
 
 from . import neighbors as _nb
+from ._args import as_device, coords, describe, on_device, ops as _ops, values
 from .predict import Prediction
 
 f64, f32, i32, i64 = torch.float64, torch.float32, torch.int32, torch.int64
@@ -29,10 +30,6 @@ SYMMETRIC = ("none", "union", "mutual")
 MODES = ("moran", "geary")
 _RULES = ("crow is not 0 = crow[0] <= ... <= crow[n] = nnz", "col outside [0, n)", "col not ascending within a row",
           "self edge", "w not finite or < 0")
-
-
-def _ops():
-    return _nb._ops()
 
 
 class SpatialGraph:
@@ -71,13 +68,12 @@ class SpatialGraph:
                             ("col", col, lambda t: not t.is_floating_point() and t.dim() == 1),
                             ("w", w, lambda t: t.is_floating_point() and t.dim() == 1)):
             if not torch.is_tensor(t) or t.dtype == torch.bool or not ok(t):
-                got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-                raise ValueError(f"{what}: {name} is {got}; crow integer [{n + 1}], col integer [nnz] and w floating-point "
-                                 "[nnz] are needed")
+                raise ValueError(f"{what}: {name} is {describe(t)}; crow integer [{n + 1}], col integer [nnz] and w "
+                                 "floating-point [nnz] are needed")
         if col.shape != w.shape:
             raise ValueError(f"{what}: col has {col.numel()} entries and w {w.numel()}")
-        _nb._on_device(what, crow=crow, col=col, w=w)
-        crow, col, w = crow.detach().to(i64).contiguous(), col.detach().to(i32).contiguous(), w.detach().to(f64).contiguous()
+        on_device(what, "neighbour", crow=crow, col=col, w=w)
+        crow, col, w = as_device(crow, i64), as_device(col, i32), as_device(w, f64)
         bad = _ops().graph_check(crow, col, w, n).tolist()
         if any(bad):
             raise ValueError(f"{what}: the graph is malformed: "
@@ -96,14 +92,14 @@ def spatial_graph(X, k=6, symmetric="none", row_standardize=True, rows_per_chunk
     row.  The in-neighbour lists come from a stable sort of the flattened lists; the per-row merge of the two sorted
     lists is HIP (count, scan, write), without atomics and without anything of n x n."""
     what = "spatial_graph"
-    _nb._coords(X, "X", what)
+    coords(X, "X", what, _nb.MAX_D)
     n = int(X.shape[0])
     _nb._check_k(k, n - 1, what, True)
     if symmetric not in SYMMETRIC:
         raise ValueError(f"{what}: symmetric must be 'none', 'union' or 'mutual', not {symmetric!r}")
     c = _nb._chunk(rows_per_chunk, n, what)
-    _nb._on_device(what, X=X)
-    R = _nb._wide(X)
+    on_device(what, "neighbour", X=X)
+    R = as_device(X, f64)
     idx = torch.empty(n, k, dtype=i32, device=R.device)
     for a, ia, _ in _nb._knn_chunks(R, R, k, True, c):
         idx[a: a + c] = ia
@@ -123,8 +119,7 @@ def fdr_bh(p):
     a sort, ``p_(i) m / i``, a reversed cumulative minimum, a clip at 1
     (``scipy.stats.false_discovery_control(p, method="bh")`` on complete input).  fp64, on ``p``'s device."""
     if not torch.is_tensor(p) or p.dim() != 1 or not p.is_floating_point():
-        got = f"{p.dtype} {tuple(p.shape)}" if torch.is_tensor(p) else type(p).__name__
-        raise ValueError(f"fdr_bh: p must be a floating-point [m], not {got}")
+        raise ValueError(f"fdr_bh: p must be a floating-point [m], not {describe(p)}")
     p = p.detach().to(f64)
     finite = torch.isfinite(p)
     m = finite.sum()
@@ -145,8 +140,8 @@ def _folded_tail(z, two_tailed):
 def _check_perms(perms, n, what):
     if not torch.is_tensor(perms) or perms.dim() != 2 or perms.is_floating_point() or perms.dtype == torch.bool \
             or perms.shape[0] < 1 or perms.shape[1] != n:
-        got = f"{perms.dtype} {tuple(perms.shape)}" if torch.is_tensor(perms) else type(perms).__name__
-        raise ValueError(f"{what}: perms is {got}; an integer [R >= 1, {n}] is needed, every row a permutation of 0..{n - 1}")
+        raise ValueError(f"{what}: perms is {describe(perms)}; an integer [R >= 1, {n}] is needed, every row a permutation "
+                         f"of 0..{n - 1}")
 
 
 @torch.no_grad()
@@ -187,7 +182,7 @@ def spatial_autocorr(X_or_graph, Y, mode="moran", n_perms=100, two_tailed=False,
         raise ValueError(f"{what}: mode must be 'moran' or 'geary', not {mode!r}")
     graph = X_or_graph if isinstance(X_or_graph, SpatialGraph) else None
     if graph is None:
-        _nb._coords(X_or_graph, "X", what)
+        coords(X_or_graph, "X", what, _nb.MAX_D)
         n = int(X_or_graph.shape[0])
         _nb._check_k(k, n - 1, what, True)
         if symmetric not in SYMMETRIC:
@@ -196,7 +191,7 @@ def spatial_autocorr(X_or_graph, Y, mode="moran", n_perms=100, two_tailed=False,
         n = graph.n
     if n < 3:
         raise ValueError(f"{what}: {n} points; the moments need at least 3")
-    _nb._values(Y, "Y", what, n)
+    values(Y, "Y", what, n)
     if isinstance(n_perms, bool) or not isinstance(n_perms, int) or n_perms < 0:
         raise ValueError(f"{what}: n_perms must be a non-negative integer, not {n_perms!r}")
     if perms is not None:
@@ -207,8 +202,8 @@ def spatial_autocorr(X_or_graph, Y, mode="moran", n_perms=100, two_tailed=False,
         raise ValueError(f"{what}: perms_per_chunk must be a positive integer, not {perms_per_chunk!r}")
     if bool(torch.isnan(Y).any()):
         raise ValueError(f"{what}: Y has NaN entries; the statistic is defined on complete columns (drop or fill them first)")
-    _nb._on_device(what, X=None if graph is not None else X_or_graph, graph=graph.crow if graph is not None else None,
-                   Y=Y, perms=perms)
+    on_device(what, "neighbour", X=None if graph is not None else X_or_graph,
+              graph=graph.crow if graph is not None else None, Y=Y, perms=perms)
     if graph is None:
         graph = spatial_graph(X_or_graph, k=k, symmetric=symmetric, row_standardize=row_standardize,
                               rows_per_chunk=rows_per_chunk)

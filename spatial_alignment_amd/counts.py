@@ -32,6 +32,7 @@ import math
 
 import torch
 
+from ._args import as_device, describe, on_device, ops as _ops, view_offsets
 from .predict import Prediction
 
 f64, f32 = torch.float64, torch.float32
@@ -56,19 +57,13 @@ HVG_DEFAULTS = dict(min_mean=0.0125, max_mean=3, min_disp=0.5, max_disp=math.inf
 def _matrix(Y, what):
     if not torch.is_tensor(Y) or Y.dim() != 2 or Y.shape[0] < 1 or Y.shape[1] < 1 or Y.dtype == torch.bool \
             or Y.is_complex():
-        shape = f"{Y.dtype} {tuple(Y.shape)}" if torch.is_tensor(Y) else type(Y).__name__
-        raise ValueError(f"{what}: Y has shape {shape}; a real [N >= 1, P >= 1] matrix of counts is needed")
+        raise ValueError(f"{what}: Y has shape {describe(Y)}; a real [N >= 1, P >= 1] matrix of counts is needed")
     return Y
 
 
 def _on_device(what, **tensors):
-    devs = {name: t.device for name, t in tensors.items() if t is not None}
-    for name, d in devs.items():
-        if d.type != "cuda":
-            raise ValueError(f"{what}: {name} is on device {str(d)!r}; the count kernels run on the GPU only and there is "
-                             "no host path - move the tensors to the device first")
-    if len(set(devs.values())) > 1:
-        raise ValueError(f"{what}: the tensors are on different devices: " + ", ".join(f"{n} on {d}" for n, d in devs.items()))
+    """(a name of this module: the tests that drive it through a fake backend on the host replace it)"""
+    on_device(what, "count", **tensors)
 
 
 def _check_theta(theta, what, allow_inf):
@@ -96,16 +91,6 @@ def _bound(v, name, what):
     if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or v < 0:
         raise ValueError(f"{what}: {name} must be None or a number >= 0, not {v!r}")
     return v
-
-
-def _ops():
-    from . import engine as E
-
-    return E.ops()
-
-
-def _f32c(Y):
-    return Y.detach().to(f32).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -179,13 +164,6 @@ def _target(row_sum, target_sum, what):
     return float(target_sum)
 
 
-def _offsets(ns):
-    off = [0]
-    for n in ns:
-        off.append(off[-1] + n)
-    return off
-
-
 def _transform_selected(o, Ysel, fresh, margins, row_sum, log_sz, ns_kept, transform, theta, standardize, what):
     """steps 4 and 5 of prepare_counts on the selected dense block ``Ysel`` (``fresh``: a copy of ours, transformed in
     place).  ``margins()``: the margins of Ysel itself; ``row_sum``: of the kept rows over ALL genes
@@ -204,13 +182,13 @@ def _transform_selected(o, Ysel, fresh, margins, row_sum, log_sz, ns_kept, trans
         except ValueError as e:
             raise ValueError(f"{what}: {e}") from None
     if transform != "counts" and standardize:
-        outputs, n_constant = o.standardize_views(outputs, _offsets(ns_kept), out=outputs)
+        outputs, n_constant = o.standardize_views(outputs, view_offsets(ns_kept), out=outputs)
     return outputs, log_offset, n_constant
 
 
 def _view_counts(keep, ns, what):
     """the rows each view keeps under the mask ``keep``; every view needs one"""
-    off = _offsets(ns)
+    off = view_offsets(ns)
     kept = torch.cat([keep.new_zeros(1, dtype=torch.int64), torch.cumsum(keep.to(torch.int64), 0)])[off].tolist()
     ns_kept = [b - a for a, b in zip(kept, kept[1:])]
     if min(ns_kept) < 1:
@@ -333,7 +311,7 @@ def _moments(o, src, ns, transform, target_sum, what):
         st = _stats(o, src)
         _refuse_invalid(st, what)
         scale = _scale(st.row_sum, _target(st.row_sum, target_sum, what))
-    s1, s2, ab, bad = src.moments(o, transform, _offsets(ns), scale)
+    s1, s2, ab, bad = src.moments(o, transform, view_offsets(ns), scale)
     mean, var = _close_moments(s1, s2, ns)
     return Prediction(mean=mean, var=var, n_nonfinite=int(bad.item()), abs_sum=ab)
 
@@ -420,8 +398,7 @@ def _csr_parts(matrix, what):
         raise ValueError(f"{what}: shape {shape!r} must be (N, P) with 1 <= N, P < 2^31")
     for name, t in (("crow", crow), ("col", col), ("values", val)):
         if not torch.is_tensor(t) or t.dim() != 1 or t.layout != torch.strided:
-            raise ValueError(f"{what}: {name} must be a 1-D tensor, not "
-                             + (f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__))
+            raise ValueError(f"{what}: {name} must be a 1-D tensor, not {describe(t)}")
     for name, t in (("crow", crow), ("col", col)):
         if t.dtype not in (torch.int32, torch.int64):
             raise ValueError(f"{what}: {name} has dtype {t.dtype}; the index dtypes are int32 and int64")
@@ -488,8 +465,7 @@ def csr_counts(matrix, device=None, _what="csr_counts"):
             raise ValueError(f"{what}: device is for scipy input; tensors stay where they are")
         parts = _csr_parts(matrix, what)
     crow, col, val, shape = parts
-    crow, col, val = crow.detach().to(torch.int64).contiguous(), col.detach().to(torch.int32).contiguous(), \
-        val.detach().to(f32).contiguous()
+    crow, col, val = as_device(crow, torch.int64), as_device(col, torch.int32), as_device(val, f32)
     return _checked(_ops(), crow, col, val, shape, what)
 
 
@@ -618,7 +594,7 @@ def _counts_source(Y, what, upload=False):
         return _SparseCounts(A)
     _matrix(Y, what)
     _on_device(what, Y=Y)
-    return _DenseCounts(_f32c(Y))
+    return _DenseCounts(as_device(Y, f32))
 
 
 def _prepare(o, src, ns, min_counts, max_counts, min_cells, n_top_genes, transform, theta, standardize,
@@ -718,11 +694,11 @@ def _poisson_deviance(what, Y, log_sz=None):
             raise ValueError(f"{what}: the tensors are on different devices: Y on {src.device}, log_sz on {log_sz.device}")
     else:
         _on_device(what, Y=Y, log_sz=log_sz)
-        src = _DenseCounts(_f32c(Y))
+        src = _DenseCounts(as_device(Y, f32))
     o = _ops()
     st = _stats(o, src)
     _refuse_invalid(st, what)
-    lsz = _log_size_factors(st.row_sum, what) if log_sz is None else log_sz.detach().to(f64).contiguous()
+    lsz = _log_size_factors(st.row_sum, what) if log_sz is None else as_device(log_sz, f64)
     return _deviance(o, src, st.col_sum, lsz)
 
 
@@ -769,7 +745,7 @@ def _residual_call(what, kind, Y, theta, clipping, inplace):
     _matrix(Y, what)
     out = _inplace_ok(Y, inplace, what)
     _on_device(what, Y=Y)
-    o, Y = _ops(), _f32c(Y)
+    o, Y = _ops(), as_device(Y, f32)
     st = _stats(o, _DenseCounts(Y))
     _refuse_invalid(st, what)
     try:
@@ -790,7 +766,7 @@ def normalize_log1p(Y, target_sum=None, inplace=False):
         _target(None, target_sum, what)
     out = _inplace_ok(Y, inplace, what)
     _on_device(what, Y=Y)
-    o, Y = _ops(), _f32c(Y)
+    o, Y = _ops(), as_device(Y, f32)
     st = _stats(o, _DenseCounts(Y))
     _refuse_invalid(st, what)
     return o.count_transform(Y, "log1p", st.row_sum, target=_target(st.row_sum, target_sum, what), out=out)
@@ -809,12 +785,12 @@ def standardize_views(Y, n_samples_list, inplace=False):
     ns = _check_views(n_samples_list, int(Y.shape[0]), what)
     out = _inplace_ok(Y, inplace, what)
     _on_device(what, Y=Y)
-    o, Y = _ops(), _f32c(Y)
+    o, Y = _ops(), as_device(Y, f32)
     # the margins' fp64 row sums: a NaN or an infinite entry makes its row's sum non-finite, finite fp32 values cannot
     bad_rows = int((~torch.isfinite(o.count_margins(Y)[0])).sum())
     if bad_rows:
         raise ValueError(f"{what}: Y holds NaN or infinite entries (in {bad_rows} rows); their columns' moments would be NaN")
-    outputs, n_constant = o.standardize_views(Y, _offsets(ns), out=out)
+    outputs, n_constant = o.standardize_views(Y, view_offsets(ns), out=out)
     return Prediction(outputs=outputs, n_constant=n_constant)
 
 

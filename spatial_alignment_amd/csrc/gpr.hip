@@ -25,7 +25,7 @@
 //                    (w0 + w1) + (w2 + w3): one order for every row, whatever rows the caller passes together.
 #include <math.h>
 
-#include "common.hpp"
+#include "toolbox.hpp"
 
 namespace gpsa {
 
@@ -61,16 +61,6 @@ __device__ __forceinline__ double gpr_d2(const double* __restrict__ u, const dou
   return s;
 }
 
-// rows [r0, r0 + 64) of X [n, D] into LDS, padded with zeros to MAXD coordinates and beyond n; threads t0 .. t0 + 63
-__device__ __forceinline__ void gpr_stage_x(const double* __restrict__ X, long long n, int D, long long r0, int t,
-                                            double (*xs)[MAXD]) {
-  if (t >= 0 && t < GPR_T) {
-    const long long r = r0 + t;
-#pragma unroll
-    for (int d = 0; d < MAXD; ++d) xs[t][d] = (r < n && d < D) ? X[r * D + d] : 0.0;
-  }
-}
-
 template <int KIND>
 __global__ void __launch_bounds__(256)
 gpr_cov_kernel(const double* __restrict__ XA, long long na, const double* __restrict__ XB, long long nb, int D,
@@ -81,8 +71,8 @@ gpr_cov_kernel(const double* __restrict__ XA, long long na, const double* __rest
   if (same && bj > bi) return;  // block-uniform: the mirror of (bj, bi) writes this tile
   const long long i0 = (long long)bi * GPR_T, j0 = (long long)bj * GPR_T;
   const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
-  gpr_stage_x(XA, na, D, i0, tid, xa);
-  gpr_stage_x(XB, nb, D, j0, tid - GPR_T, xb);
+  stage_rows64(XA, na, D, i0, tid, xa);
+  stage_rows64(XB, nb, D, j0, tid - GPR_T, xb);
   __syncthreads();
   const double a = amplitude ? exp(theta[0]) : 1.0, inv_l = exp(-theta[1]), tau2 = exp(theta[2]);
   const long long j = j0 + tx;
@@ -120,8 +110,8 @@ gpr_grad_kernel(const double* __restrict__ X, long long N, int D, const double* 
   const long long i0 = bi * GPR_T, j0 = bj * GPR_T;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = (w >> 1) * 32, wn = (w & 1) * 32, j = lane & 15, kq = lane >> 4;
-  gpr_stage_x(X, N, D, i0, tid, xi);
-  gpr_stage_x(X, N, D, j0, tid - GPR_T, xj);
+  stage_rows64(X, N, D, i0, tid, xi);
+  stage_rows64(X, N, D, j0, tid - GPR_T, xj);
   __syncthreads();
 
   // alpha_I alpha_J^T: A operand lane (row j, k kq) = alpha[row][p0 + kq], B operand lane (k kq, col j) the same of J
@@ -180,16 +170,8 @@ __global__ void __launch_bounds__(256)
 gpr_grad_close_kernel(const double* __restrict__ part, long long nblk, const double* __restrict__ theta, int amplitude,
                       double* __restrict__ out) {
   __shared__ double red[3][256];
-  const int tid = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (long long b = tid; b < nblk; b += 256) s0 += part[b * 3], s1 += part[b * 3 + 1], s2 += part[b * 3 + 2];
-  red[0][tid] = s0, red[1][tid] = s1, red[2][tid] = s2;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) red[0][tid] += red[0][tid + h], red[1][tid] += red[1][tid + h], red[2][tid] += red[2][tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) {
+  fold3_partials(part, nblk, red);
+  if (threadIdx.x == 0) {
     const double a = amplitude ? exp(theta[0]) : 1.0, tau2 = exp(theta[2]);
     out[0] = 0.5 * a * red[0][0];
     out[1] = 0.5 * a * red[1][0];
@@ -216,7 +198,7 @@ gpr_mean_kernel(const double* __restrict__ XS, long long ns, const double* __res
   for (int tj = 0; tj < 4; ++tj) acc[tj] = (gpr_acc_t){0.0, 0.0, 0.0, 0.0};
   for (long long n0 = 0; n0 < N; n0 += GPR_T) {
     __syncthreads();  // the previous chunk has been read
-    gpr_stage_x(X, N, D, n0, tid, xt);
+    stage_rows64(X, N, D, n0, tid, xt);
     for (int e = tid; e < GPR_T * GPR_T; e += 256) {
       const int r = e >> 6, c = e & 63;
       al[r][c] = (n0 + r < N && c0 + c < P) ? alpha[(n0 + r) * P + c0 + c] : 0.0;  // rows beyond N contribute k * 0

@@ -21,18 +21,13 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "toolbox.hpp"
 
 namespace gpsa {
 
 constexpr int KNN_TILE = 512;     // references staged in LDS at a time (D = 4: 16 KB)
 constexpr int KNN_MAXK = 32;      // the largest list kept in registers
 constexpr int KNN_MAXPARTS = 256;
-
-// (d, j) < (bd, bj) in the key's order
-__device__ __forceinline__ bool knn_less(double d, int j, double bd, int bj) {
-  return d < bd || (d == bd && j < bj);
-}
 
 // the sorted list of one thread.  Every loop over its slots is fully unrolled: bd / bi are registers.
 template <int K>
@@ -46,7 +41,7 @@ struct KnnList {
       bi[s] = INT_MAX;  // above every row index: a real candidate at distance +inf still enters before a spare slot
     }
   }
-  __device__ __forceinline__ bool takes(double d, int j) const { return knn_less(d, j, bd[K - 1], bi[K - 1]); }
+  __device__ __forceinline__ bool takes(double d, int j) const { return key_less(d, j, bd[K - 1], bi[K - 1]); }
   // (d, j) is known to be below the worst key.  With c[s] = (d, j) < slot s (false ... false true ... true), the new
   // slot s is slot s-1 where c[s-1], else the candidate where c[s], else itself; walked from the last slot down so that
   // slot s-1 is still the old one.
@@ -54,7 +49,7 @@ struct KnnList {
     bool cs = true;
 #pragma unroll
     for (int s = K - 1; s >= 1; --s) {
-      const bool cp = knn_less(d, j, bd[s - 1], bi[s - 1]);
+      const bool cp = key_less(d, j, bd[s - 1], bi[s - 1]);
       bd[s] = cp ? bd[s - 1] : (cs ? d : bd[s]);
       bi[s] = cp ? bi[s - 1] : (cs ? j : bi[s]);
       cs = cp;
@@ -147,18 +142,9 @@ knn_merge_kernel(const double* __restrict__ pd, const int* __restrict__ pi, long
     }
 }
 
-// the number of slices a call runs with: the caller's (at most one per reference row), or for 0 enough of them that
-// about four workgroups per compute unit are in flight, each slice at least one LDS tile long
+// the number of slices of the reference axis a call runs with (slice_parts): a slice's scan is cdiv(nq, 256) workgroups
 static int knn_parts(long long nq, long long nr, int parts) {
-  long long p = parts;
-  if (p == 0) {
-    const long long qblocks = cdiv(nq, 256), want = 4LL * num_cus();
-    p = qblocks >= want ? 1 : cdiv(want, qblocks);
-    p = min(p, cdiv(nr, (long long)KNN_TILE));
-  }
-  p = min(p, nr);
-  p = min(p, (long long)KNN_MAXPARTS);
-  return (int)max(p, 1LL);
+  return slice_parts(cdiv(nq, 256), nr, KNN_TILE, KNN_MAXPARTS, parts);
 }
 
 static long long knn_workspace_bytes(long long nq, int k, int parts) {

@@ -21,7 +21,7 @@
 // overflows nor gives a NaN.  e is read from a device double.  Nothing of n m elements is allocated here.
 #include <math.h>
 
-#include "common.hpp"
+#include "toolbox.hpp"
 
 namespace gpsa {
 
@@ -38,14 +38,6 @@ static long long ot_rows_per_group(long long n) {
 static long long ot_groups(long long n) { return cdiv(n, ot_rows_per_group(n)); }
 static long long ot_col_tiles(long long m) { return cdiv(m, (long long)OT_T); }
 static long long ot_cost_blocks(long long n) { return n < OT_COST_BLOCKS ? n : OT_COST_BLOCKS; }
-
-__device__ __forceinline__ double ot_wave_max(double v) {
-  v = fmax(v, dpp_move<0xB1>(v));
-  v = fmax(v, dpp_move<0x4E>(v));
-  v = fmax(v, dpp_move<0x141>(v));
-  v = fmax(v, dpp_move<0x140>(v));
-  return fmax(fmax(lane_value(v, 0), lane_value(v, 16)), fmax(lane_value(v, 32), lane_value(v, 48)));
-}
 
 // one more term v of a running log-sum-exp held as (mx, s): the sum of exp(. - mx)
 __device__ __forceinline__ void ot_lse_add(double v, double& mx, double& s) {
@@ -68,7 +60,7 @@ ot_dist_kernel(const double* __restrict__ X, long long n, int D, double* __restr
   if (bj > bi) return;  // block-uniform: the mirror of (bj, bi) writes this tile
   const long long i0 = (long long)bi * OT_T, j0 = (long long)bj * OT_T;
   const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
-  if (tid < 2 * OT_T) {
+  if (tid < 2 * OT_T) {  // what stage_rows64 writes, both tiles in one branch: two calls change this kernel's registers
     const int t = tid & 63;
     const long long r = (tid < OT_T ? i0 : j0) + t;
     double(*xs)[MAXD] = tid < OT_T ? xa : xb;
@@ -206,16 +198,8 @@ ot_cost_kernel(double* __restrict__ G, const double* __restrict__ M, const doubl
 __global__ void __launch_bounds__(256)
 ot_close3_kernel(const double* __restrict__ part, long long nblk, double* __restrict__ out) {
   __shared__ double red[3][256];
-  const int tid = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (long long b = tid; b < nblk; b += 256) s0 += part[b * 3], s1 += part[b * 3 + 1], s2 += part[b * 3 + 2];
-  red[0][tid] = s0, red[1][tid] = s1, red[2][tid] = s2;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) red[0][tid] += red[0][tid + h], red[1][tid] += red[1][tid + h], red[2][tid] += red[2][tid + h];
-    __syncthreads();
-  }
-  if (tid < 3) out[tid] = red[tid][0];
+  fold3_partials(part, nblk, red);
+  if (threadIdx.x < 3) out[threadIdx.x] = red[threadIdx.x][0];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -241,7 +225,7 @@ ot_sink_row_kernel(const double* __restrict__ cost, long long n, long long m, co
     ot_lse_add((g[j + 3 * WAVE] - c3) / eps + logb[j + 3 * WAVE], mx, s);
   }
   for (; j < m; j += WAVE) ot_lse_add((g[j] - c[j]) / eps + logb[j], mx, s);
-  const double top = ot_wave_max(mx);               // finite: m >= 1, lane 0 holds a column
+  const double top = wave_max(mx);                  // finite: m >= 1, lane 0 holds a column
   s = wave_sum(s == 0.0 ? 0.0 : s * exp(mx - top)); // (a lane without a column: s = 0, mx = -inf)
   if (lane == 0) f[row] = -eps * (top + log(s));
 }
@@ -353,12 +337,7 @@ ot_plan_close_kernel(const double* __restrict__ rowsum, const double* __restrict
   for (long long k = tid; k < n; k += 256) s0 += fabs(rowsum[k] - a[k]);
   for (long long k = tid; k < m; k += 256) s1 += fabs(colsum[k] - b[k]);
   for (long long k = tid; k < nchg; k += 256) s2 += chg[k];
-  red[0][tid] = s0, red[1][tid] = s1, red[2][tid] = s2;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) red[0][tid] += red[0][tid + h], red[1][tid] += red[1][tid + h], red[2][tid] += red[2][tid + h];
-    __syncthreads();
-  }
+  fold3_256(s0, s1, s2, red);
   if (tid < 3) out[tid] = red[tid][0];
 }
 

@@ -25,7 +25,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "toolbox.hpp"
 
 namespace gpsa {
 
@@ -108,7 +108,7 @@ rigid_merge_kernel(const double* __restrict__ pd, const int* __restrict__ pi, lo
   for (int p = 1; p < parts; ++p) {
     const double d = pd[p * total + e];
     const int j = pi[p * total + e];
-    const bool take = d < bd || (d == bd && j < bi);
+    const bool take = key_less(d, j, bd, bi);
     bd = take ? d : bd;
     bi = take ? j : bi;
   }
@@ -144,17 +144,7 @@ rigid_close_kernel(const float* __restrict__ YA, long long m, const float* __res
       cnt += 1.0;
     }
   }
-  red[0][threadIdx.x] = sse;
-  red[1][threadIdx.x] = dsum;
-  red[2][threadIdx.x] = cnt;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (threadIdx.x < w) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+  fold3_256(sse, dsum, cnt, red);
   if (threadIdx.x < 3) part[(k * gridDim.x + g) * 3 + threadIdx.x] = red[threadIdx.x][0];
 }
 
@@ -176,18 +166,9 @@ rigid_fold_kernel(const double* __restrict__ part, long long K, int G, double* _
   n_matched[k] = (long long)c;
 }
 
-// slices of the A axis: the caller's (at most one per row of A), or for 0 enough of them that about four workgroups
-// per compute unit are in flight, each slice at least one LDS tile long
+// slices of the A axis (slice_parts): a slice's scan is cdiv(n, RG_ROWS) x cdiv(K, RG_C) workgroups
 static int rg_parts(long long n, long long m, long long K, int parts) {
-  long long p = parts;
-  if (p == 0) {
-    const long long blocks = cdiv(n, RG_ROWS) * cdiv(K, RG_C), want = 4LL * num_cus();
-    p = blocks >= want ? 1 : cdiv(want, blocks);
-    p = min(p, cdiv(m, (long long)RG_TILE));
-  }
-  p = min(p, m);
-  p = min(p, (long long)RG_MAXPARTS);
-  return (int)max(p, 1LL);
+  return slice_parts(cdiv(n, RG_ROWS) * cdiv(K, RG_C), m, RG_TILE, RG_MAXPARTS, parts);
 }
 
 // the workspace, in this order (every piece a multiple of 8 bytes): the partials [K][G][3] fp64;  d2 then nn [K n] where

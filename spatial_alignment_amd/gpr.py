@@ -30,11 +30,14 @@ import math
 import numpy as np
 import torch
 
+from ._args import as_device, chunk_rows, coords, on_device, require_finite, values, view_counts, view_offsets
+from ._args import ops as _ops
 from .predict import Prediction
 
 f64 = torch.float64
 KERNELS = ("rbf", "matern32", "matern12")
 MAX_D = 4  # csrc/gpr.hip: MAXD
+NOT_FINITE = "{name} has NaN or infinite entries"
 ARMIJO_C = 1e-4
 MAX_STEP = 2.0       # log units, per coordinate and step
 VAR_CHUNK = 4096     # test rows per chunk of the predictive variance (two [N, chunk] panels)
@@ -43,38 +46,10 @@ VAR_CHUNK = 4096     # test rows per chunk of the predictive variance (two [N, c
 # ------------------------------------------------------------------------------------------------------------------------
 # argument checks (all of them before any device work)
 # ------------------------------------------------------------------------------------------------------------------------
-def _shape(t):
-    return f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-
-
-def _coords(t, name, what, D=None):
-    if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point() or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{what}: {name} has shape {_shape(t)}; a floating-point [n >= 1, D] with 1 <= D <= {MAX_D} is needed")
-    if t.shape[1] > MAX_D:
-        raise ValueError(f"{what}: {name} has D = {t.shape[1]} coordinates; at most {MAX_D} are supported")
-    if D is not None and t.shape[1] != D:
-        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}; D = {D} coordinates are needed")
-    return t
-
-
-def _values(t, name, what, rows):
-    if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point() or t.shape[0] != rows or t.shape[1] < 1:
-        raise ValueError(f"{what}: {name} has shape {_shape(t)}; a floating-point [{rows}, P >= 1] is needed")
-    return t
-
-
 def _kernel(kernel, what):
     if kernel not in KERNELS:
         raise ValueError(f"{what}: kernel must be one of {KERNELS}, not {kernel!r}")
     return kernel
-
-
-def _chunk(rows_per_chunk, what):
-    if rows_per_chunk is None:
-        return None
-    if isinstance(rows_per_chunk, bool) or int(rows_per_chunk) != rows_per_chunk or rows_per_chunk < 1:
-        raise ValueError(f"{what}: rows_per_chunk must be a positive integer, not {rows_per_chunk!r}")
-    return int(rows_per_chunk)
 
 
 def _bounds(bounds, what):
@@ -96,33 +71,6 @@ def _theta(theta, name, what):
     if th.shape != (3,) or not np.all(np.isfinite(th)):
         raise ValueError(f"{what}: {name} must be three finite log values (log a, log l, log tau2), not {theta!r}")
     return th
-
-
-def _on_device(what, **tensors):
-    """every tensor on one HIP device"""
-    devs = {name: t.device for name, t in tensors.items() if t is not None}
-    for name, d in devs.items():
-        if d.type != "cuda":
-            raise ValueError(f"{what}: {name} is on device {str(d)!r}; the GP regression kernels run on the GPU only and "
-                             "there is no host path - move the tensors to the device first")
-    if len(set(devs.values())) > 1:
-        raise ValueError(f"{what}: the tensors are on different devices: " + ", ".join(f"{n} on {d}" for n, d in devs.items()))
-
-
-def _finite(what, **tensors):
-    for name, t in tensors.items():
-        if not bool(torch.isfinite(t).all()):
-            raise ValueError(f"{what}: {name} has NaN or infinite entries")
-
-
-def _ops():
-    from . import engine as E
-
-    return E.ops()
-
-
-def _wide(t):
-    return t.detach().to(f64).contiguous()
 
 
 def gpr_bytes(N, P):
@@ -314,11 +262,11 @@ class GPRegression:
         on ``rows_per_chunk``, bit for bit; the variance goes by chunks of rows (4096 by default) through a
         cross-covariance panel and the dense product with L^-1."""
         what = "GPRegression.predict"
-        _coords(Xs, "Xs", what, int(self.X.shape[1]))
-        c = _chunk(rows_per_chunk, what)
-        _finite(what, Xs=Xs)
-        _on_device(what, X_train=self.X, Xs=Xs)
-        Q = _wide(Xs)
+        coords(Xs, "Xs", what, MAX_D, int(self.X.shape[1]), own_max_message=True)
+        c = chunk_rows(rows_per_chunk, what)
+        require_finite(what, NOT_FINITE, Xs=Xs)
+        on_device(what, "GP regression", X_train=self.X, Xs=Xs)
+        Q = as_device(Xs, f64)
         o = _ops()
         n, P = int(Q.shape[0]), int(self.alpha.shape[1])
         mean = torch.empty(n, P, dtype=f64, device=Q.device)
@@ -355,9 +303,9 @@ def gp_regress(X, Y, kernel="rbf", amplitude=False, optimize=True, theta0=None, 
     Returns a ``GPRegression``.  Raises ValueError for a bad shape, D > 4, NaN or infinite entries, tensors on the CPU, an
     unknown kernel, or a size whose matrices do not fit the device's free memory (the message states the bytes needed)."""
     what = "gp_regress"
-    _coords(X, "X", what)
+    coords(X, "X", what, MAX_D, own_max_message=True)
     N = int(X.shape[0])
-    _values(Y, "Y", what, N)
+    values(Y, "Y", what, N)
     _kernel(kernel, what)
     lo, hi = _bounds(bounds, what)
     th0 = np.zeros(3) if theta0 is None else _theta(theta0, "theta0", what)
@@ -367,10 +315,10 @@ def gp_regress(X, Y, kernel="rbf", amplitude=False, optimize=True, theta0=None, 
         raise ValueError(f"{what}: gtol must be > 0, not {gtol!r}")
     if not (float(jitter) >= 0.0) or not math.isfinite(float(jitter)):
         raise ValueError(f"{what}: jitter must be >= 0 and finite, not {jitter!r}")
-    _finite(what, X=X, Y=Y)
-    _on_device(what, X=X, Y=Y)
+    require_finite(what, NOT_FINITE, X=X, Y=Y)
+    on_device(what, "GP regression", X=X, Y=Y)
     _refuse_if_too_large(what, N, int(Y.shape[1]), _free_bytes(X.device))  # before the fit's first allocation
-    Xd, Yd = _wide(X), _wide(Y)
+    Xd, Yd = as_device(X, f64), as_device(Y, f64)
 
     amplitude = bool(amplitude)
     if not amplitude:
@@ -394,13 +342,13 @@ def gp_regress(X, Y, kernel="rbf", amplitude=False, optimize=True, theta0=None, 
 
 def _view_rows(n_samples_list, total, name, what):
     try:
-        ns = [int(v) for v in n_samples_list]
+        ns, ok = view_counts(n_samples_list, total, least_rows=0)
     except (TypeError, ValueError):
         raise ValueError(f"{what}: {name} must be a list of row counts, not {n_samples_list!r}") from None
-    if len(ns) < 1 or any(v < 0 for v in ns) or sum(ns) != total:
+    if not ok:
         raise ValueError(f"{what}: {name} = {ns} does not partition the {total} rows")
-    off = np.concatenate([[0], np.cumsum(ns)])
-    return [(int(off[v]), int(off[v + 1])) for v in range(len(ns))]
+    off = view_offsets(ns)
+    return list(zip(off, off[1:]))
 
 
 def _mse(pred, Y):
@@ -420,11 +368,11 @@ def prediction_baselines(X_train, Y_train, X_test, Y_test, n_samples_list_train,
     ``preds_separate`` [rows of the views that were not skipped, P] fp64, ``fit_union`` and ``fits_separate`` (a list with
     one ``GPRegression`` per view, None for a skipped one), ``views`` (the views scored)."""
     what = "prediction_baselines"
-    _coords(X_train, "X_train", what)
+    coords(X_train, "X_train", what, MAX_D, own_max_message=True)
     D = int(X_train.shape[1])
-    _values(Y_train, "Y_train", what, int(X_train.shape[0]))
-    _coords(X_test, "X_test", what, D)
-    _values(Y_test, "Y_test", what, int(X_test.shape[0]))
+    values(Y_train, "Y_train", what, int(X_train.shape[0]))
+    coords(X_test, "X_test", what, MAX_D, D, own_max_message=True)
+    values(Y_test, "Y_test", what, int(X_test.shape[0]))
     if Y_test.shape[1] != Y_train.shape[1]:
         raise ValueError(f"{what}: Y_test has shape {tuple(Y_test.shape)} and Y_train {tuple(Y_train.shape)}: the same P "
                          "is needed")
@@ -438,9 +386,9 @@ def prediction_baselines(X_train, Y_train, X_test, Y_test, n_samples_list_train,
             raise ValueError(f"{what}: view {v} has test rows and no training rows")
     if all(d == c for c, d in te):
         raise ValueError(f"{what}: no view has test rows")
-    _finite(what, X_train=X_train, Y_train=Y_train, X_test=X_test, Y_test=Y_test)
-    _on_device(what, X_train=X_train, Y_train=Y_train, X_test=X_test, Y_test=Y_test)
-    Xtr, Ytr, Xte, Yte = _wide(X_train), _wide(Y_train), _wide(X_test), _wide(Y_test)
+    require_finite(what, NOT_FINITE, X_train=X_train, Y_train=Y_train, X_test=X_test, Y_test=Y_test)
+    on_device(what, "GP regression", X_train=X_train, Y_train=Y_train, X_test=X_test, Y_test=Y_test)
+    Xtr, Ytr, Xte, Yte = (as_device(t, f64) for t in (X_train, Y_train, X_test, Y_test))
 
     fit_union = gp_regress(Xtr, Ytr, kernel=kernel, amplitude=amplitude)
     preds_union = fit_union.predict(Xte)

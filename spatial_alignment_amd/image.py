@@ -24,6 +24,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from ._args import ops as _ops
+
 f32, f64 = torch.float32, torch.float64
 GRAY_PIXEL_VAL = 0.7  # the reference's background: visium_multimodal_alignment.py:27
 DEFAULT_CHUNK_PIXELS = 1 << 20  # warp_image: output pixels per chunk of rows by default
@@ -120,12 +122,6 @@ class ImagePixels(NamedTuple):
     n_background: int
     n_outside: int
     shape: tuple
-
-
-def _ops():
-    from . import engine as E
-
-    return E.ops()
 
 
 def _check_image(img, what):

@@ -22,6 +22,7 @@ import math
 
 import torch
 
+from ._args import as_device, chunk_rows, coords, on_device, ops as _ops, values
 from .predict import Prediction
 
 f64, f32 = torch.float64, torch.float32
@@ -32,21 +33,6 @@ WEIGHTS = ("uniform", "distance")
 # ------------------------------------------------------------------------------------------------------------------------
 # argument checks (all of them before any device work)
 # ------------------------------------------------------------------------------------------------------------------------
-def _coords(t, name, what):
-    if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point() or t.shape[0] < 1 \
-            or not 1 <= t.shape[1] <= MAX_D:
-        shape = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-        raise ValueError(f"{what}: {name} has shape {shape}; a floating-point [n >= 1, D] with 1 <= D <= {MAX_D} is needed")
-    return t
-
-
-def _values(t, name, what, rows):
-    if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point() or t.shape[0] != rows or t.shape[1] < 1:
-        shape = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-        raise ValueError(f"{what}: {name} has shape {shape}; a floating-point [{rows}, P >= 1] is needed")
-    return t
-
-
 def _check_k(k, available, what, excluded=False):
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
         raise ValueError(f"{what}: k must be an integer in [1, {MAX_K}], not {k!r}")
@@ -63,32 +49,8 @@ def _check_weights(weights, what):
 
 
 def _chunk(rows_per_chunk, n, what):
-    if rows_per_chunk is None:
-        return max(n, 1)
-    if isinstance(rows_per_chunk, bool) or int(rows_per_chunk) != rows_per_chunk or rows_per_chunk < 1:
-        raise ValueError(f"{what}: rows_per_chunk must be a positive integer, not {rows_per_chunk!r}")
-    return int(rows_per_chunk)
-
-
-def _on_device(what, **tensors):
-    """the last check: every tensor on one HIP device"""
-    devs = {name: t.device for name, t in tensors.items() if t is not None}
-    for name, d in devs.items():
-        if d.type != "cuda":
-            raise ValueError(f"{what}: {name} is on device {str(d)!r}; the neighbour kernels run on the GPU only and there "
-                             "is no host path - move the tensors to the device first")
-    if len(set(devs.values())) > 1:
-        raise ValueError(f"{what}: the tensors are on different devices: " + ", ".join(f"{n} on {d}" for n, d in devs.items()))
-
-
-def _ops():
-    from . import engine as E
-
-    return E.ops()
-
-
-def _wide(t):
-    return t.detach().to(f64).contiguous()
+    c = chunk_rows(rows_per_chunk, what)
+    return max(n, 1) if c is None else c
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -124,17 +86,17 @@ def knn(query, ref=None, k=10, exclude_self=None, rows_per_chunk=None):
     distance go to the lower index.  1 <= D <= 4, 1 <= k <= 32.  rows_per_chunk: query rows per launch (default: all;
     the result does not depend on it, bit for bit)."""
     what = "knn"
-    _coords(query, "query", what)
+    coords(query, "query", what, MAX_D)
     if ref is not None:
-        _coords(ref, "ref", what)
+        coords(ref, "ref", what, MAX_D)
         if ref.shape[1] != query.shape[1]:
             raise ValueError(f"{what}: query has shape {tuple(query.shape)} and ref {tuple(ref.shape)}: the same D is needed")
     ref_t, excl = _self_or_ref(query, ref, exclude_self, what)
     _check_k(k, int(ref_t.shape[0]) - excl, what, excl)
     c = _chunk(rows_per_chunk, int(query.shape[0]), what)
-    _on_device(what, query=query, ref=ref)
-    R = _wide(ref_t)
-    Q = R if ref_t is query else _wide(query)
+    on_device(what, "neighbour", query=query, ref=ref)
+    R = as_device(ref_t, f64)
+    Q = R if ref_t is query else as_device(query, f64)
     nq = int(Q.shape[0])
     idx = torch.empty(nq, k, dtype=torch.int32, device=Q.device)
     d2 = torch.empty(nq, k, dtype=f64, device=Q.device)
@@ -156,11 +118,11 @@ def knn_regress(X_train, Y_train, X_test=None, k=10, weights="uniform", exclude_
     predicted from the others.  The average is accumulated in fp64 in neighbour order and does not depend on
     ``rows_per_chunk``, bit for bit."""
     what = "knn_regress"
-    _coords(X_train, "X_train", what)
-    _values(Y_train, "Y_train", what, int(X_train.shape[0]))
+    coords(X_train, "X_train", what, MAX_D)
+    values(Y_train, "Y_train", what, int(X_train.shape[0]))
     if X_test is None:
         X_test = X_train
-    _coords(X_test, "X_test", what)
+    coords(X_test, "X_test", what, MAX_D)
     if X_test.shape[1] != X_train.shape[1]:
         raise ValueError(f"{what}: X_test has shape {tuple(X_test.shape)} and X_train {tuple(X_train.shape)}: the same D "
                          "is needed")
@@ -168,10 +130,10 @@ def knn_regress(X_train, Y_train, X_test=None, k=10, weights="uniform", exclude_
     _check_weights(weights, what)
     _check_k(k, int(X_train.shape[0]) - excl, what, excl)
     c = _chunk(rows_per_chunk, int(X_test.shape[0]), what)
-    _on_device(what, X_train=X_train, Y_train=Y_train, X_test=X_test)
-    R = _wide(X_train)
-    Q = R if X_test is X_train else _wide(X_test)
-    Y = Y_train.detach().to(f32).contiguous()
+    on_device(what, "neighbour", X_train=X_train, Y_train=Y_train, X_test=X_test)
+    R = as_device(X_train, f64)
+    Q = R if X_test is X_train else as_device(X_test, f64)
+    Y = as_device(Y_train, f32)
     out = torch.empty(int(Q.shape[0]), int(Y.shape[1]), dtype=f32, device=Q.device)
     o = _ops()
     for a, idx, d2 in _knn_chunks(Q, R, k, excl, c):
@@ -244,15 +206,15 @@ def moran_i(X, Y, k=6, row_standardize=True, rows_per_chunk=None):
     [P] = (I - expected) / sqrt(variance) and ``p_norm`` [P] = 1/2 erfc(z / sqrt 2), the upper tail.  A constant column
     is NaN.  ``Y`` with a NaN is refused (ValueError).  No permutation p-values; the graph is not symmetrised."""
     what = "moran_i"
-    _coords(X, "X", what)
+    coords(X, "X", what, MAX_D)
     n = int(X.shape[0])
-    _values(Y, "Y", what, n)
+    values(Y, "Y", what, n)
     _check_k(k, n - 1, what, True)
     c = _chunk(rows_per_chunk, n, what)
     if bool(torch.isnan(Y).any()):
         raise ValueError(f"{what}: Y has NaN entries; Moran's I is defined on complete columns (drop or fill them first)")
-    _on_device(what, X=X, Y=Y)
-    R = _wide(X)
+    on_device(what, "neighbour", X=X, Y=Y)
+    R = as_device(X, f64)
     y = Y.detach().to(f32).to(f64)
     zc = (y - y.mean(0)).contiguous()
     idx = torch.empty(n, k, dtype=torch.int32, device=R.device)
@@ -354,7 +316,7 @@ def alignment_score(model, X_spatial, Y, view_idx=None, *, k=10, weights="unifor
     c = None if rows_per_chunk is None else _chunk(rows_per_chunk, 1, what)
     if G is None and any(not model._is_fixed(v) for v in range(V)):
         _check_kind(model, what)
-    _on_device(what, **tensors, model=model.Xtilde)
+    on_device(what, "neighbour", **tensors, model=model.Xtilde)
 
     out = {}
     for m in mods:

@@ -10,6 +10,7 @@ import os
 import torch
 
 from . import _lib
+from ._args import describe
 
 F32, F64 = 0, 1
 KINDS = {"rbf": 0, "matern12": 1, "matern32": 2}
@@ -104,6 +105,18 @@ class HipOps:
     def _f32(t):
         t = t if t.dtype == torch.float32 else t.float()
         return t if t.is_contiguous() else t.contiguous()
+
+    @staticmethod
+    def _contiguous(what, dtype, **tensors):
+        """name=(tensor, shape): every tensor contiguous, of ``dtype`` (fp64 or fp32) and of the named shape; an extent
+        given as a string ("n >= 1", "P >= 1": how the refusal writes it) stands for any extent >= 1"""
+        for name, (t, shape) in tensors.items():
+            ok = torch.is_tensor(t) and t.dtype == dtype and t.is_contiguous() and t.dim() == len(shape) and all(
+                (s == want) if isinstance(want, int) else (s >= 1) for s, want in zip(t.shape, shape))
+            if not ok:
+                want = ", ".join(str(s) for s in shape)
+                raise ValueError(f"{what}: {name} must be a contiguous {'fp64' if dtype == torch.float64 else 'fp32'} "
+                                 f"[{want}], not {describe(t)}")
 
     # ------------------------------------------------------------------ covariance matrices
     @staticmethod
@@ -758,11 +771,7 @@ class HipOps:
         Kinv [N, N]: 1/2 sum_ij (alpha alpha^T - P Kinv)_ij dK_ij, fused (nothing of N x N is written), fixed order."""
         kd, theta, D = self._gpr_args("gpr_lml_grad", kind, theta, X)
         N = int(X.shape[0])
-        for t, name, sh in ((alpha, "alpha", (N, None)), (Kinv, "Kinv", (N, N))):
-            if t.dim() != 2 or t.shape[0] != sh[0] or (sh[1] is not None and t.shape[1] != sh[1]) or t.shape[1] < 1 \
-                    or t.dtype != torch.float64 or not t.is_contiguous():
-                raise ValueError(f"gpr_lml_grad: {name} must be a contiguous fp64 [{N}, {sh[1] or 'P >= 1'}], not {t.dtype} "
-                                 f"{tuple(t.shape)}")
+        self._contiguous("gpr_lml_grad", torch.float64, alpha=(alpha, (N, "P >= 1")), Kinv=(Kinv, (N, N)))
         P = int(alpha.shape[1])
         if out is None:
             out = torch.empty(3, dtype=torch.float64, device=X.device)
@@ -779,10 +788,7 @@ class HipOps:
         [ns, N] matrix); a row's result does not depend on the rows passed with it."""
         kd, theta, D = self._gpr_args("gpr_mean", kind, theta, XS, X)
         ns, N = int(XS.shape[0]), int(X.shape[0])
-        if alpha.dim() != 2 or alpha.shape[0] != N or alpha.shape[1] < 1 or alpha.dtype != torch.float64 \
-                or not alpha.is_contiguous():
-            raise ValueError(f"gpr_mean: alpha must be a contiguous fp64 [{N}, P >= 1], not {alpha.dtype} "
-                             f"{tuple(alpha.shape)}")
+        self._contiguous("gpr_mean", torch.float64, alpha=(alpha, (N, "P >= 1")))
         P = int(alpha.shape[1])
         if out is None:
             out = torch.empty(ns, P, dtype=torch.float64, device=XS.device)
@@ -795,34 +801,23 @@ class HipOps:
     # ------------------------------------------------------------------ optimal-transport alignment (csrc/ot.hip)
     OT_MODES = {"kl": 0, "euclidean": 1}
 
-    @staticmethod
-    def _ot_f64(what, **tensors):
-        """every tensor a contiguous fp64 of the named shape (None in a shape: any extent >= 1)"""
-        for name, (t, shape) in tensors.items():
-            ok = torch.is_tensor(t) and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == len(shape) and all(
-                (s >= 1) if want is None else (s == want) for s, want in zip(t.shape, shape))
-            if not ok:
-                got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-                want = "[" + ", ".join("n >= 1" if s is None else str(s) for s in shape) + "]"
-                raise ValueError(f"{what}: {name} must be a contiguous fp64 {want}, not {got}")
-
     def ot_dist(self, X, out=None):
         """gpsa_ot_dist_f64: X [n, D <= 4] fp64 -> [n, n] Euclidean distances, symmetric to the bit, zero diagonal"""
-        self._ot_f64("ot_dist", X=(X, (None, None)))
+        self._contiguous("ot_dist", torch.float64, X=(X, ("n >= 1", "n >= 1")))
         n, D = int(X.shape[0]), int(X.shape[1])
         if D > 4:
             raise ValueError(f"ot_dist: D = {D}; 1 to 4 coordinates are supported")
         if out is None:
             out = torch.empty(n, n, dtype=torch.float64, device=X.device)
-        self._ot_f64("ot_dist", out=(out, (n, n)))
+        self._contiguous("ot_dist", torch.float64, out=(out, (n, n)))
         _lib.check(self.lib.gpsa_ot_dist_f64(_p(X), n, D, _p(out), self._stream(X)), "gpsa_ot_dist_f64")
         return out
 
     def ot_sqmatvec(self, Cm, v):
         """gpsa_ot_sqmatvec_f64: [n] = sum_k Cm_ik^2 v_k for Cm [n, ncol], v [ncol] fp64"""
-        self._ot_f64("ot_sqmatvec", Cm=(Cm, (None, None)))
+        self._contiguous("ot_sqmatvec", torch.float64, Cm=(Cm, ("n >= 1", "n >= 1")))
         n, ncol = int(Cm.shape[0]), int(Cm.shape[1])
-        self._ot_f64("ot_sqmatvec", v=(v, (ncol,)))
+        self._contiguous("ot_sqmatvec", torch.float64, v=(v, (ncol,)))
         out = torch.empty(n, dtype=torch.float64, device=Cm.device)
         _lib.check(self.lib.gpsa_ot_sqmatvec_f64(_p(Cm), n, ncol, _p(v), _p(out), self._stream(Cm)), "gpsa_ot_sqmatvec_f64")
         return out
@@ -832,10 +827,7 @@ class HipOps:
         "kl": Pm = (y + 0.01) / row sum, Lg = log Pm, term = sum Pm Lg; "euclidean": Pm = y, Lg is Pm, term = sum y^2"""
         if mode not in self.OT_MODES:
             raise ValueError(f"ot_expr_rows: dissimilarity must be one of {sorted(self.OT_MODES)}, not {mode!r}")
-        if not torch.is_tensor(Y) or Y.dtype != torch.float32 or Y.dim() != 2 or Y.shape[0] < 1 or Y.shape[1] < 1 \
-                or not Y.is_contiguous():
-            got = f"{Y.dtype} {tuple(Y.shape)}" if torch.is_tensor(Y) else type(Y).__name__
-            raise ValueError(f"ot_expr_rows: Y must be a contiguous fp32 [n >= 1, P >= 1], not {got}")
+        self._contiguous("ot_expr_rows", torch.float32, Y=(Y, ("n >= 1", "P >= 1")))
         n, P = int(Y.shape[0]), int(Y.shape[1])
         Pm = torch.empty(n, P, dtype=torch.float64, device=Y.device)
         Lg = torch.empty_like(Pm) if mode == "kl" else None
@@ -852,11 +844,11 @@ class HipOps:
         """gpsa_ot_expr_cost_f64, in place over G [n, m]: "kl" M = ra_i - G_ij; "euclidean" M = max(0, ra_i + rb_j - 2 G_ij)"""
         if mode not in self.OT_MODES:
             raise ValueError(f"ot_expr_cost: dissimilarity must be one of {sorted(self.OT_MODES)}, not {mode!r}")
-        self._ot_f64("ot_expr_cost", G=(G, (None, None)))
+        self._contiguous("ot_expr_cost", torch.float64, G=(G, ("n >= 1", "n >= 1")))
         n, m = int(G.shape[0]), int(G.shape[1])
-        self._ot_f64("ot_expr_cost", ra=(ra, (n,)))
+        self._contiguous("ot_expr_cost", torch.float64, ra=(ra, (n,)))
         if mode == "euclidean":
-            self._ot_f64("ot_expr_cost", rb=(rb, (m,)))
+            self._contiguous("ot_expr_cost", torch.float64, rb=(rb, (m,)))
         else:
             rb = None
         rc = self.lib.gpsa_ot_expr_cost_f64(self.OT_MODES[mode], _p(G), n, m, _p(ra), _p(rb), self._stream(G))
@@ -866,15 +858,16 @@ class HipOps:
     def ot_cost(self, G, M, T, cA, cB, cAt, cBt, alpha, sums=None):
         """gpsa_ot_cost_f64, in place over G = C1 T C2 [n, m]: cost = (1 - alpha) M + 2 alpha (cA 1^T + 1 cB^T - 2 G);
         -> (G, sums [3] fp64 on the device: sum |cost|, <M, T>, <cAt 1^T + 1 cBt^T - 2 G, T>)"""
-        self._ot_f64("ot_cost", G=(G, (None, None)))
+        self._contiguous("ot_cost", torch.float64, G=(G, ("n >= 1", "n >= 1")))
         n, m = int(G.shape[0]), int(G.shape[1])
-        self._ot_f64("ot_cost", M=(M, (n, m)), T=(T, (n, m)), cA=(cA, (n,)), cB=(cB, (m,)), cAt=(cAt, (n,)), cBt=(cBt, (m,)))
+        self._contiguous("ot_cost", torch.float64, M=(M, (n, m)), T=(T, (n, m)), cA=(cA, (n,)), cB=(cB, (m,)), cAt=(cAt, (n,)),
+                         cBt=(cBt, (m,)))
         alpha = float(alpha)
         if not 0.0 <= alpha <= 1.0:
             raise ValueError(f"ot_cost: alpha = {alpha} is outside [0, 1]")
         if sums is None:
             sums = torch.empty(3, dtype=torch.float64, device=G.device)
-        self._ot_f64("ot_cost", sums=(sums, (3,)))
+        self._contiguous("ot_cost", torch.float64, sums=(sums, (3,)))
         nbytes = self._wsq("gpsa_ot_cost_workspace", n, m)
         ws = self._ws(nbytes, G)
         rc = self.lib.gpsa_ot_cost_f64(_p(G), _p(M), _p(T), _p(cA), _p(cB), _p(cAt), _p(cBt), alpha, n, m, _p(sums), _p(ws),
@@ -884,9 +877,10 @@ class HipOps:
 
     def ot_sinkhorn(self, cost, loga, logb, eps, f, g, iters):
         """gpsa_ot_sinkhorn_f64: ``iters`` log-domain sweeps, f [n] and g [m] updated in place; eps [1] fp64 on the device"""
-        self._ot_f64("ot_sinkhorn", cost=(cost, (None, None)))
+        self._contiguous("ot_sinkhorn", torch.float64, cost=(cost, ("n >= 1", "n >= 1")))
         n, m = int(cost.shape[0]), int(cost.shape[1])
-        self._ot_f64("ot_sinkhorn", loga=(loga, (n,)), logb=(logb, (m,)), eps=(eps, (1,)), f=(f, (n,)), g=(g, (m,)))
+        self._contiguous("ot_sinkhorn", torch.float64, loga=(loga, (n,)), logb=(logb, (m,)), eps=(eps, (1,)), f=(f, (n,)),
+                         g=(g, (m,)))
         iters = int(iters)
         if iters < 0:
             raise ValueError(f"ot_sinkhorn: iters = {iters} is negative")
@@ -900,9 +894,10 @@ class HipOps:
     def ot_plan(self, cost, f, g, a, b, eps, T):
         """gpsa_ot_plan_f64: T_ij = a_i b_j exp((f_i + g_j - cost_ij) / eps) written over T (the previous plan) ->
         (T, rowsum [n], colsum [m], sums [3]: |T 1 - a|_1, |T^T 1 - b|_1, |T - T_old|_1)"""
-        self._ot_f64("ot_plan", cost=(cost, (None, None)))
+        self._contiguous("ot_plan", torch.float64, cost=(cost, ("n >= 1", "n >= 1")))
         n, m = int(cost.shape[0]), int(cost.shape[1])
-        self._ot_f64("ot_plan", f=(f, (n,)), g=(g, (m,)), a=(a, (n,)), b=(b, (m,)), eps=(eps, (1,)), T=(T, (n, m)))
+        self._contiguous("ot_plan", torch.float64, f=(f, (n,)), g=(g, (m,)), a=(a, (n,)), b=(b, (m,)), eps=(eps, (1,)),
+                         T=(T, (n, m)))
         rowsum = torch.empty(n, dtype=torch.float64, device=cost.device)
         colsum = torch.empty(m, dtype=torch.float64, device=cost.device)
         sums = torch.empty(3, dtype=torch.float64, device=cost.device)
@@ -1107,9 +1102,8 @@ class HipOps:
               and w.dtype == torch.float64 and w.shape == col.shape
               and crow.is_contiguous() and col.is_contiguous() and w.is_contiguous())
         if not ok:
-            sh = lambda t: f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
             raise ValueError(f"{what}: a graph on {n} rows needs contiguous crow int64 [{n + 1}], col int32 [nnz] and "
-                             f"w fp64 [nnz], not {sh(crow)}, {sh(col)}, {sh(w)}")
+                             f"w fp64 [nnz], not {describe(crow)}, {describe(col)}, {describe(w)}")
         for name, t in (("crow", crow), ("col", col), ("w", w)):
             if not t.is_cuda:
                 raise ValueError(f"{what}: {name} is on device {str(t.device)!r}; the graph kernels run on the GPU only")
@@ -1207,8 +1201,8 @@ class HipOps:
         """img [H, W, C] contiguous uint8 or fp32 on a device, C in 1..4 -> (H, W, C, "u8" | "f32")"""
         if (not torch.is_tensor(img) or img.dim() != 3 or img.dtype not in (torch.uint8, torch.float32)
                 or not img.is_contiguous() or min(img.shape) < 1 or img.shape[2] > 4):
-            got = f"{img.dtype} {tuple(img.shape)}" if torch.is_tensor(img) else type(img).__name__
-            raise ValueError(f"{what}: img must be a contiguous uint8 or fp32 [H >= 1, W >= 1, C in 1..4], not {got}")
+            raise ValueError(f"{what}: img must be a contiguous uint8 or fp32 [H >= 1, W >= 1, C in 1..4], not "
+                             f"{describe(img)}")
         if not img.is_cuda:
             raise ValueError(f"{what}: img is on {img.device}; the image kernels run on the device")
         H, W, Cn = (int(s) for s in img.shape)
@@ -1381,9 +1375,8 @@ class HipOps:
         N, P, off, V, mean, inv_scale = self._pca_args("pca_project", Y, mean, inv_scale, view_off)
         if not torch.is_tensor(comp) or comp.dim() != 2 or comp.shape[1] != P or not 1 <= comp.shape[0] <= self.PCA_MAX_K \
                 or comp.dtype != torch.float64 or not comp.is_contiguous() or comp.device != Y.device:
-            got = f"{comp.dtype} {tuple(comp.shape)}" if torch.is_tensor(comp) else type(comp).__name__
             raise ValueError(f"pca_project: comp must be a contiguous fp64 [1 <= k <= {self.PCA_MAX_K}, {P}] on "
-                             f"{Y.device}, not {got}")
+                             f"{Y.device}, not {describe(comp)}")
         if out_dtype not in (torch.float32, torch.float64):
             raise ValueError(f"pca_project: out_dtype must be torch.float32 or torch.float64, not {out_dtype}")
         k = int(comp.shape[0])

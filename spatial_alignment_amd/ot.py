@@ -39,6 +39,8 @@ from dataclasses import dataclass
 
 import torch
 
+from ._args import as_device, describe, on_device, ops as _ops
+
 f64 = torch.float64
 MAX_D = 4  # csrc/common.hpp: MAXD
 DISSIMILARITIES = ("kl", "euclidean")
@@ -63,30 +65,10 @@ class OTAlignment:
     g: torch.Tensor
 
 
-def _ops():
-    from . import engine as E
-
-    return E.ops()
-
-
-def _shape(t):
-    return f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-
-
 def _matrix(t, name, what):
     if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point() or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"{what}: {name} has shape {_shape(t)}; a floating-point [n >= 1, >= 1] tensor is needed")
+        raise ValueError(f"{what}: {name} has shape {describe(t)}; a floating-point [n >= 1, >= 1] tensor is needed")
     return t
-
-
-def _on_device(what, **tensors):
-    devs = {name: t.device for name, t in tensors.items() if t is not None}
-    for name, d in devs.items():
-        if d.type != "cuda":
-            raise ValueError(f"{what}: {name} is on device {str(d)!r}; the optimal-transport kernels run on the GPU only and "
-                             "there is no host path - move the tensors to the device first")
-    if len(set(devs.values())) > 1:
-        raise ValueError(f"{what}: the tensors are on different devices: " + ", ".join(f"{n} on {d}" for n, d in devs.items()))
 
 
 def _count(v, name, what, low):
@@ -98,8 +80,8 @@ def _count(v, name, what, low):
 def _marginal(w, name, what, n):
     """a strictly positive fp64 [n] that sums to 1 (one host read)"""
     if not torch.is_tensor(w) or w.dim() != 1 or w.shape[0] != n or not w.is_floating_point():
-        raise ValueError(f"{what}: marginal {name} has shape {_shape(w)}; a floating-point [{n}] is needed")
-    w = w.detach().to(f64).contiguous()
+        raise ValueError(f"{what}: marginal {name} has shape {describe(w)}; a floating-point [{n}] is needed")
+    w = as_device(w, f64)
     bad = int((~(w > 0)).sum())
     if bad:
         raise ValueError(f"{what}: marginal {name} must be strictly positive; {bad} of its {n} entries are not")
@@ -134,15 +116,15 @@ def _check_args(what, XA, YA, XB, YB, alpha, dissimilarity, epsilon, a, b, T_ini
     if tol is not None and not float(tol) >= 0.0:
         raise ValueError(f"{what}: tol = {tol!r} must be None or >= 0")
     if T_init is not None and (not torch.is_tensor(T_init) or tuple(T_init.shape) != (n, m) or not T_init.is_floating_point()):
-        raise ValueError(f"{what}: T_init has shape {_shape(T_init)}; a floating-point [{n}, {m}] is needed")
-    _on_device(what, XA=XA, YA=YA, XB=XB, YB=YB, a=a if torch.is_tensor(a) else None,
-               b=b if torch.is_tensor(b) else None, T_init=T_init)
+        raise ValueError(f"{what}: T_init has shape {describe(T_init)}; a floating-point [{n}, {m}] is needed")
+    on_device(what, "optimal-transport", XA=XA, YA=YA, XB=XB, YB=YB, a=a if torch.is_tensor(a) else None,
+              b=b if torch.is_tensor(b) else None, T_init=T_init)
     return n, m, D, P
 
 
 def spatial_cost(X, norm=False):
     """C [n, n] = |x_i - x_k| (fp64, symmetric to the bit, zero diagonal); ``norm``: divided by its smallest positive entry"""
-    C = _ops().ot_dist(X.detach().to(f64).contiguous())
+    C = _ops().ot_dist(as_device(X, f64))
     if norm:
         pos = C[C > 0]
         if pos.numel():
@@ -155,8 +137,8 @@ def expression_cost(YA, YB, dissimilarity="kl"):
     a ``ValueError`` names the count of entries "kl" cannot take (negative, NaN or infinite; "euclidean": NaN or infinite)"""
     what = "expression_cost"
     o = _ops()
-    Pa, La, ta, bad_a = o.ot_expr_rows(YA.detach().to(torch.float32).contiguous(), dissimilarity)
-    Pb, Lb, tb, bad_b = o.ot_expr_rows(YB.detach().to(torch.float32).contiguous(), dissimilarity)
+    Pa, La, ta, bad_a = o.ot_expr_rows(as_device(YA, torch.float32), dissimilarity)
+    Pb, Lb, tb, bad_b = o.ot_expr_rows(as_device(YB, torch.float32), dissimilarity)
     na, nb = (int(v) for v in torch.cat([bad_a, bad_b]).tolist())
     if na or nb:
         rule = "non-negative and finite" if dissimilarity == "kl" else "finite"
@@ -189,7 +171,7 @@ def ot_align(XA, YA, XB, YB, alpha=0.1, dissimilarity="kl", epsilon=0.01, relati
     C1, C2 = spatial_cost(XA, norm), spatial_cost(XB, norm)
     cA, cB = o.ot_sqmatvec(C1, a), o.ot_sqmatvec(C2, b)
     loga, logb = a.log(), b.log()
-    T = torch.outer(a, b) if T_init is None else T_init.detach().to(f64).contiguous().clone()
+    T = torch.outer(a, b) if T_init is None else as_device(T_init, f64).clone()
     f, g = torch.zeros(n, dtype=f64, device=dev), torch.zeros(m, dtype=f64, device=dev)
     tmp, G = torch.empty(n, m, dtype=f64, device=dev), torch.empty(n, m, dtype=f64, device=dev)
     sums = torch.empty(3, dtype=f64, device=dev)
@@ -237,16 +219,16 @@ def stack_slices(X_list, T_list, reflection=True):
     what = "stack_slices"
     if len(X_list) < 1 or len(T_list) != len(X_list) - 1:
         raise ValueError(f"{what}: {len(X_list)} slices need {max(len(X_list) - 1, 0)} couplings, not {len(T_list)}")
-    Xs = [_matrix(X, f"X_list[{k}]", what).detach().to(f64).contiguous() for k, X in enumerate(X_list)]
+    Xs = [as_device(_matrix(X, f"X_list[{k}]", what), f64) for k, X in enumerate(X_list)]
     D = Xs[0].shape[1]
     eye = torch.eye(D, dtype=f64, device=Xs[0].device)
     out, rots, trans = [Xs[0]], [eye], [torch.zeros(D, dtype=f64, device=Xs[0].device)]
     for k, T in enumerate(T_list):
         X, Y = out[k], Xs[k + 1]
         if not torch.is_tensor(T) or tuple(T.shape) != (X.shape[0], Y.shape[0]) or Y.shape[1] != D:
-            raise ValueError(f"{what}: T_list[{k}] has shape {_shape(T)}; [{X.shape[0]}, {Y.shape[0]}] is needed, and "
+            raise ValueError(f"{what}: T_list[{k}] has shape {describe(T)}; [{X.shape[0]}, {Y.shape[0]}] is needed, and "
                              f"D = {D} coordinates in every slice")
-        T = T.detach().to(f64).contiguous()
+        T = as_device(T, f64)
         tx, ty = T.sum(1) @ X, T.sum(0) @ Y
         Xc, Yc = X - tx, Y - ty
         H = _matmul(Yc, _matmul(T, Xc, transA=True), transA=True)  # Y^T (T^T X)  [D, D]

@@ -29,6 +29,7 @@ whose variance inside a view is at most ``4 n eps`` times its mean square there 
 import numpy as np
 import torch
 
+from ._args import describe, ops as _ops, view_counts, view_offsets
 from .predict import Prediction
 
 f64, f32 = torch.float64, torch.float32
@@ -37,12 +38,6 @@ SOLVERS = ("subspace", "host")
 MAX_K = 128         # components per launch of the projection (csrc/pca.hip: PCA_MAX_K)
 MAX_BLOCK = 256     # columns of the iteration's block: gpsa_chol_inv_f64 factorises up to 256 x 256 in one sweep
 EPS = float(np.finfo(np.float64).eps)
-
-
-def _ops():
-    from . import engine as E
-
-    return E.ops()
 
 
 class ExpressionPCA(Prediction):
@@ -58,7 +53,7 @@ class ExpressionPCA(Prediction):
         if len(ns) != self.n_views:
             raise ValueError(f"{what}: the decomposition was centred on {self.n_views} views; n_samples_list has "
                              f"{len(ns)}")
-        return _offs(ns)
+        return view_offsets(ns)
 
     @torch.no_grad()
     def transform(self, Y, n_samples_list=None, out_dtype=torch.float32):
@@ -88,8 +83,7 @@ class ExpressionPCA(Prediction):
         k, P = (int(s) for s in self.components.shape)
         if not torch.is_tensor(scores) or scores.dim() != 2 or scores.shape[1] != k or scores.shape[0] < 1 \
                 or not scores.is_floating_point():
-            got = f"{scores.dtype} {tuple(scores.shape)}" if torch.is_tensor(scores) else type(scores).__name__
-            raise ValueError(f"{what}: scores must be a floating [N >= 1, {k}], not {got}")
+            raise ValueError(f"{what}: scores must be a floating [N >= 1, {k}], not {describe(scores)}")
         if scores.device != self.components.device:
             raise ValueError(f"{what}: scores are on {scores.device}, the components on {self.components.device}")
         N = int(scores.shape[0])
@@ -112,8 +106,7 @@ class ExpressionPCA(Prediction):
 
 def _check_matrix(Y, what, on_device=True):
     if not torch.is_tensor(Y) or Y.dim() != 2 or Y.shape[0] < 1 or Y.shape[1] < 1:
-        got = f"{Y.dtype} {tuple(Y.shape)}" if torch.is_tensor(Y) else type(Y).__name__
-        raise ValueError(f"{what}: Y must be a dense [N, P] matrix, not {got}")
+        raise ValueError(f"{what}: Y must be a dense [N, P] matrix, not {describe(Y)}")
     if Y.dtype != f32:
         raise ValueError(f"{what}: Y is {Y.dtype}; the kernels read fp32 as stored (what prepare_counts returns)")
     if not Y.is_contiguous():
@@ -130,17 +123,10 @@ def _check_device(Y, what):
 
 
 def _views(n_samples_list, N, what):
-    ns = [N] if n_samples_list is None else [int(n) for n in n_samples_list]
-    if not ns or sum(ns) != N or min(ns) < 1:
+    ns, ok = view_counts([N] if n_samples_list is None else n_samples_list, N)
+    if not ok:
         raise ValueError(f"{what}: n_samples_list {ns} must hold positive row counts that sum to N = {N}")
     return ns
-
-
-def _offs(ns):
-    off = [0]
-    for n in ns:
-        off.append(off[-1] + n)
-    return off
 
 
 def _check_args(Y, n_samples_list, n_components, center, scale, solver, oversample, tol, max_iter, check_every, what):
@@ -267,7 +253,7 @@ def expression_pca(Y, n_samples_list=None, n_components=50, center="pooled", sca
     what = "expression_pca"
     N, P, ns = _check_args(Y, n_samples_list, n_components, center, scale, solver, oversample, tol, max_iter,
                            check_every, what)
-    V, off, k = len(ns), _offs(ns), n_components
+    V, off, k = len(ns), view_offsets(ns), n_components
     o = _ops()
     s1, s2, _, bad = o.column_moments(Y, "identity", off, own_workspace=True)
     nbad = int(bad.item())

@@ -23,11 +23,13 @@ import math
 
 import torch
 
-from .neighbors import _on_device
+from ._args import as_device, describe, on_device, require_finite, values, view_counts, view_offsets
+from ._args import ops as _ops
 from .predict import Prediction
 
 f64, f32 = torch.float64, torch.float32
 INF = float("inf")
+NOT_FINITE = "{name} has {count} entries that are NaN or infinite; drop those spots first"
 REFINE_ANGLE_OFFSETS = (-1, 0, 1)
 REFINE_SHIFT_OFFSETS = (-2, -1, 0, 1, 2)
 
@@ -58,16 +60,12 @@ class RigidRegistration(Prediction):
 def _slice_args(XA, YA, XB, YB, what):
     for name, t in (("XA", XA), ("XB", XB)):
         if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point() or t.shape[0] < 1:
-            shape = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-            raise ValueError(f"{what}: {name} has shape {shape}; a floating-point [n >= 1, 2] is needed")
+            raise ValueError(f"{what}: {name} has shape {describe(t)}; a floating-point [n >= 1, 2] is needed")
         if t.shape[1] != 2:
             raise ValueError(f"{what}: {name} has D = {int(t.shape[1])} coordinates; the candidates are transforms of the "
                              "plane (D = 2) - a 3-D stack is registered slice by slice in its plane")
-    for name, t, X in (("YA", YA, XA), ("YB", YB, XB)):
-        if not torch.is_tensor(t) or t.dim() != 2 or not t.is_floating_point() or t.shape[0] != X.shape[0] \
-                or t.shape[1] < 1:
-            shape = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
-            raise ValueError(f"{what}: {name} has shape {shape}; a floating-point [{int(X.shape[0])}, P >= 1] is needed")
+    values(YA, "YA", what, int(XA.shape[0]))
+    values(YB, "YB", what, int(XB.shape[0]))
     if YA.shape[1] != YB.shape[1]:
         raise ValueError(f"{what}: YA has P = {int(YA.shape[1])} outputs and YB P = {int(YB.shape[1])}: the two slices "
                          "must carry the same outputs, in the same order")
@@ -86,24 +84,8 @@ def _per_chunk(candidates_per_chunk, K, n, what):
     return _positive_int(candidates_per_chunk, "candidates_per_chunk", what)
 
 
-def _ops():
-    from . import engine as E
-
-    return E.ops()
-
-
 def _device_args(XA, YA, XB, YB):
-    wide = lambda t: t.detach().to(f64).contiguous()
-    narrow = lambda t: t.detach().to(f32).contiguous()
-    return wide(XA), narrow(YA), wide(XB), narrow(YB)
-
-
-def _require_finite(what, **tensors):
-    """one host read: which of the tensors holds a NaN or an infinity"""
-    bad = torch.stack([(~torch.isfinite(t)).sum() for t in tensors.values()]).tolist()
-    for (name, t), cnt in zip(tensors.items(), bad):
-        if cnt:
-            raise ValueError(f"{what}: {name} has {int(cnt)} entries that are NaN or infinite; drop those spots first")
+    return as_device(XA, f64), as_device(YA, f32), as_device(XB, f64), as_device(YB, f32)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -134,16 +116,17 @@ def rigid_scores(XA, YA, XB, YB, transforms, max_dist, return_nn=False, candidat
     _slice_args(XA, YA, XB, YB, what)
     if not torch.is_tensor(transforms) or transforms.dim() != 2 or transforms.shape[0] < 1 or transforms.shape[1] != 6 \
             or not transforms.is_floating_point():
-        shape = f"{transforms.dtype} {tuple(transforms.shape)}" if torch.is_tensor(transforms) else type(transforms).__name__
-        raise ValueError(f"{what}: transforms has shape {shape}; a floating-point [K >= 1, 6] (R row-major, then t) is needed")
+        raise ValueError(f"{what}: transforms has shape {describe(transforms)}; a floating-point [K >= 1, 6] (R row-major, "
+                         "then t) is needed")
     max_dist = float(max_dist)
     if not (0.0 <= max_dist < INF):
         raise ValueError(f"{what}: max_dist must be finite and >= 0, not {max_dist}")
     K, n = int(transforms.shape[0]), int(XB.shape[0])
     c = _per_chunk(candidates_per_chunk, K, n, what)
-    _on_device(what, XA=XA, YA=YA, XB=XB, YB=YB, transforms=transforms)
+    # ("neighbour": the noun these calls' device refusal has carried since they shared neighbors' check; kept as it reads)
+    on_device(what, "neighbour", XA=XA, YA=YA, XB=XB, YB=YB, transforms=transforms)
     XA, YA, XB, YB = _device_args(XA, YA, XB, YB)
-    T = transforms.detach().to(f64).contiguous()
+    T = as_device(transforms, f64)
     sse, n_matched, d2_sum, nn, d2 = _scores(_ops(), XA, YA, XB, YB, T, max_dist * max_dist, c, return_nn)
     return Prediction(sse=sse, n_matched=n_matched, d2_sum=d2_sum, nn=nn, d2=d2)
 
@@ -215,9 +198,9 @@ def rigid_register(XA, YA, XB, YB, *, n_angles=360, reflection=True, n_shifts=1,
     refls = (False, True) if reflection else (False,)
     K = len(refls) * n_angles * n_shifts * n_shifts
     c = _per_chunk(candidates_per_chunk, K + 1, n, what)
-    _on_device(what, XA=XA, YA=YA, XB=XB, YB=YB)
+    on_device(what, "neighbour", XA=XA, YA=YA, XB=XB, YB=YB)
     XA, YA, XB, YB = _device_args(XA, YA, XB, YB)
-    _require_finite(what, XA=XA, YA=YA, XB=XB, YB=YB)
+    require_finite(what, NOT_FINITE, XA=XA, YA=YA, XB=XB, YB=YB)
     o, dev = _ops(), XA.device
 
     # one host read: the spacing, the centroids, A's extent
@@ -301,17 +284,15 @@ def prealign_slices(X, Y, n_samples_list, reference=0, chain=False, **kw):
     if X.shape[1] != 2:
         raise ValueError(f"{what}: X has D = {int(X.shape[1])} coordinates; the candidates are transforms of the plane "
                          "(D = 2) - a 3-D stack is registered slice by slice in its plane")
-    counts = [int(v) for v in n_samples_list]
+    counts, ok = view_counts(n_samples_list, int(X.shape[0]), least_views=2)
     V = len(counts)
-    if V < 2 or min(counts) < 1 or sum(counts) != int(X.shape[0]):
+    if not ok:
         raise ValueError(f"{what}: n_samples_list = {counts} must hold two or more positive row counts that add up to "
                          f"X's {int(X.shape[0])} rows")
     if isinstance(reference, bool) or not isinstance(reference, int) or not 0 <= reference < V:
         raise ValueError(f"{what}: reference must be a view index in [0, {V}), not {reference!r}")
-    _on_device(what, X=X, Y=Y)
-    offs = [0]
-    for cnt in counts:
-        offs.append(offs[-1] + cnt)
+    on_device(what, "neighbour", X=X, Y=Y)
+    offs = view_offsets(counts)
     view = lambda t, v: t[offs[v]: offs[v + 1]]
     out = X.detach().to(f64).clone()
     regs = [None] * V
